@@ -20,11 +20,14 @@ Inputs (ids, genres, tables) are resident in HBM before the timed region.  Embed
 (trained-scale rows; Xavier over 10M rows gives +-0.0008, every tower output collapses onto the bias direction and
 the loss sits at ln 2 -- degenerate operands for a power-limited chip).
 
-Extra objects on the JSON line: `roofline` (dominant kernel = in-batch user pass, exact-f32 MFMA bound), `cpu_baseline`
-(stock torch-CPU f32 restatement of the same step on the host cores, bounded sample), `secondary` (each leg with its
-own `roofline` and `cpu_baseline`): split-bf16 modes of the same step, the sampled-negative step (the mode the
-reference trains in), the ML-1M-shaped configs[0]/[1] steps, top-500 brute-force IP retrieval on two query
-distributions, and the cfg5 serve chain.
+A plain run sets up, warms up, times the --steps headline steps and prints the JSON line, with `roofline` (dominant
+kernel = in-batch user pass, exact-f32 MFMA bound, from events recorded inside the timed steps).  --full adds
+`cpu_baseline` (stock torch-CPU f32 restatement of the same step on the host cores, bounded sample) and `secondary`
+(each leg with its own `roofline` and `cpu_baseline`): split-bf16 modes of the same step, the sampled-negative step
+(the mode the reference trains in), the ML-1M-shaped configs[0]/[1] steps, top-500 brute-force IP retrieval on two
+query distributions, the cfg5 serve chain and LambdaMART training; --no-secondary / --no-cpu-baseline drop parts of it.
+
+--dump-outputs DIR writes what the last timed step hands its caller, rank 0's view (see dump_outputs).
 """
 import argparse
 import json
@@ -232,6 +235,36 @@ def run_inbatch(tr, batches, W, K, world, precision):
     return dt, event_means(ev), float(tr.loss.item())
 
 
+DUMP_ROWS = 16384       # embedding rows per table in a dump: 2 x 16384 x 128 x 4 B = 16 MB (limit 64 MB)
+
+
+def dump_outputs(out_dir, model, tr, batch, rank, world, item_rows_sharded):
+    """What the last timed step returns to its caller: the loss and the updated parameters (MLP weights in full, the
+    embedding tables as a fixed sample of the rows the step touched -- the rows at DUMP_ROWS positions of the last
+    batch drawn with seed 0, in position order).  Float32, one .npy per array."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    u, items, _ = batch
+    pos = np.sort(np.random.default_rng(0).permutation(u.numel())[:DUMP_ROWS])
+    pos = torch.from_numpy(pos).to(u.device)
+    uid, iid = u[pos], items[pos]
+    if item_rows_sharded:   # global item row g lives on rank (g-1) % W at local row (g-1) // W + 1
+        iid = iid[(iid - 1) % world == rank]
+        iid = (iid - 1) // world + 1
+    arrays = {"loss": tr.loss.reshape(1),
+              "user_embedding_rows": tr.utab[uid], "item_embedding_rows": tr.itab[iid]}
+    for name, p in model.named_parameters():
+        if "embedding" not in name:
+            arrays[name] = p
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(out_dir / f"{name}.npy", a)
+    assert total <= 64 << 20, total
+    log(f"[bench] dumped {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}")
+
+
 def build_trainer(cfg, world, rank, B, loss_mode, seed):
     from recommendit_amd.dist_utils import broadcast_, n_local_rows
     from recommendit_amd.trainer import HipBPRTrainer
@@ -249,7 +282,7 @@ def build_trainer(cfg, world, rank, B, loss_mode, seed):
     return model, tr, n_users_local
 
 
-def headline(cfg_name, args, world, rank, dev, want_modes):
+def headline(cfg_name, args, world, rank, dev, want_modes, dump_dir=None):
     cfg = CONFIGS[cfg_name]
     G = args.global_batch
     B = G // world
@@ -257,6 +290,9 @@ def headline(cfg_name, args, world, rank, dev, want_modes):
     model, tr, n_users_local = build_trainer(cfg, world, rank, B, "inbatch", seed=rank)
     batches = make_batches(W + K, B, n_users_local, cfg["items"], dev, seed=7 + rank, sampled=False)
     dt, mean_ms, loss = run_inbatch(tr, batches, W, K, world, 0)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, model, tr, batches[(W + K - 1) % len(batches)], rank, world,
+                     cfg["item_shard"] == "rows" and world > 1)
     pairs_per_s = G * K / dt
     traffic = load_traffic()
     bgd = float(B) * G * D
@@ -608,8 +644,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--global-batch", type=int, default=GLOBAL_BATCH)
     ap.add_argument("--config", choices=["auto", "cfg3", "cfg4"], default="auto")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary legs (split-bf16 modes, sampled step, ML-1M shapes, retrieval, "
+                         "serve, LambdaMART training) and the torch-CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch-CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss and updated parameters of the last one as DIR/<name>.npy")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, rendezvous (gloo) and all-reduce a one per rank; no GPU work, no number")
     args = ap.parse_args()
@@ -667,12 +708,13 @@ def main():
         assert dist_ranks == dist.get_world_size() == world, (dist_ranks, dist.get_world_size(), world)
     assert args.global_batch % world == 0
     cfg_name = config_for(world, args.config)
-    cpu_ok = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_ok = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_secondary = args.full and not args.no_secondary
     log(f"[bench] host threads: torch.get_num_threads()={torch.get_num_threads()}, os.cpu_count()={os.cpu_count()}")
 
-    head = headline(cfg_name, args, world, rank, dev, want_modes=not args.no_secondary)
+    head = headline(cfg_name, args, world, rank, dev, want_modes=want_secondary, dump_dir=args.dump_outputs)
     secondary = dict(head.pop("modes"))
-    if not args.no_secondary:
+    if want_secondary:
         if world == 8 and cfg_name != "cfg3":
             # the strong-scaling curve's own point: the N<8 runs use the cfg3 tables
             alt = headline("cfg3", args, world, rank, dev, want_modes=False)
