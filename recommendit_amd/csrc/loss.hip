@@ -125,6 +125,43 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ U
 // ------------------------------------------------------------------------------------------
 // in-batch sweep
 // ------------------------------------------------------------------------------------------
+// B operands of the G.Y products.  Lane (r31, hh) of accumulator out[t] owns output column r31 * CT + t (not
+// t * 32 + r31), so the CT values it needs from one k-row of the row-major LDS tile are contiguous: one ds_read_b128
+// (d = 128), ds_read_b64 (d = 64) or ds_read_b32 (d = 32) per k-row, conflict-free for every lane group.  Each output
+// element still sums the same products in the same k-order, so only the lane -> column map changes.
+template <int CT>
+struct BRow {
+  float v[CT];
+};
+template <int CT>
+__device__ __forceinline__ BRow<CT> lds_brow(const float* p) {
+  BRow<CT> b;
+  if constexpr (CT == 4) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+    b.v[0] = x.x; b.v[1] = x.y; b.v[2] = x.z; b.v[3] = x.w;
+  } else if constexpr (CT == 2) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 x = *reinterpret_cast<const f32x2*>(p);
+    b.v[0] = x.x; b.v[1] = x.y;
+  } else {
+    static_assert(CT == 1, "embed_dim 32 / 64 / 128");
+    b.v[0] = p[0];
+  }
+  return b;
+}
+// Left to itself the scheduler sinks each read next to its first use (a wait on every read).  Pin the order: the
+// reads of LEAD k-rows, then per read instruction (while any are left) the MFMAs of the k-rows it covers.  The 4- and
+// 8-byte reads of two neighbouring k-rows are fused into one ds_read2_b32 / ds_read2_b64, so those count in pairs.
+template <int CT, int LEAD>
+__device__ __forceinline__ void brow_schedule(int nrows) {
+  constexpr int RPI = CT == 4 ? 1 : 2;  // k-rows per read instruction
+  __builtin_amdgcn_sched_group_barrier(0x100, LEAD / RPI, 0);  // DS read
+#pragma unroll
+  for (int j = 0; j < nrows; j += RPI) {
+    if (j + LEAD < nrows) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x8, RPI * CT, 0);    // MFMA
+  }
+}
 // GOUT (user mode only): additionally write the G tile (diagonal and ragged entries = 0) to a.gmat, so that the item
 // gradients come from a plain G^T.U product (inbatch_gt_kernel) instead of a second score sweep.
 template <int D, bool MODE_USER, bool GOUT = false, int NW = 4>
@@ -303,16 +340,21 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
     // ---- dOwner[o][c] += sum_s G[s][o] * Y[s][c]   (A operand = g registers, k = acc_row(r))
     float* gp = nullptr;
     if (GOUT) gp = a.gmat + ((size_t)tile * a.g_ub + (size_t)blockIdx.x * NW + w) * 1024 + (4 * hh) * 32 + r31;
+    // k-row of g[r] is acc_row(r) = (r & 3) + 8 (r >> 2) + 4 hh; its B operands are read LEAD k-rows ahead
+    const float* Yb = Yc + 4 * hh * LDY + r31 * CT;
+    constexpr int LEAD = 8 / CT;
+    BRow<CT> yb[16];
+#pragma unroll
+    for (int r = 0; r < LEAD; ++r) yb[r] = lds_brow<CT>(Yb + ((r & 3) + 8 * (r >> 2)) * LDY);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int krow = (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const int rn = r + LEAD;
+      if (rn < 16) yb[rn] = lds_brow<CT>(Yb + ((rn & 3) + 8 * (rn >> 2)) * LDY);
       if (GOUT) gp[((r & 3) + 8 * (r >> 2)) * 32] = g[r];  // 2 full 128 B lines per wave store
 #pragma unroll
-      for (int t = 0; t < CT; ++t) {
-        const float bv = Yc[krow * LDY + t * 32 + r31];
-        out[t] = mfma32(g[r], bv, out[t]);
-      }
+      for (int t = 0; t < CT; ++t) out[t] = mfma32(g[r], yb[r].v[t], out[t]);
     }
+    brow_schedule<CT, LEAD>(16);
     if (has_pre) store_tile(pre);
     st = sn;
     __syncthreads();
@@ -341,8 +383,8 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
 #pragma unroll
       for (int t = 0; t < CT; ++t) {
         float v = out[t][r] * a.c;
-        if (fix) v -= rs * a.Ys[drow * D + t * 32 + r31];  // G_ii = -sum_{j!=i} G_ij
-        dst[orow * D + t * 32 + r31] = v;
+        if (fix) v -= rs * a.Ys[drow * D + r31 * CT + t];  // G_ii = -sum_{j!=i} G_ij
+        dst[orow * D + r31 * CT + t] = v;
       }
     }
   }
@@ -472,16 +514,21 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void inbatch_gt_kernel(Sw
 #pragma unroll
       for (int q = 0; q < 4; ++q) gs[GA][q] = gp[(size_t)(tile + GA) * 256 + q];
     }
-    const float* Yc = Ysh[cur];
+    // lane (r31, hh) consumes k-rows 16 hh .. 16 hh + 15 in order; row j + LEAD is requested before row j's MFMAs
+    const float* Yb = Ysh[cur] + 16 * hh * LDY + r31 * CT;
+    // k-rows read ahead: 16 MFMAs (about 1000 cycles) of lead, 8 under the 168-VGPR cap of the 3-wave form and at
+    // d = 32 (where a lead of the whole tile leaves the scheduler no room and it falls back to a wait per read)
+    constexpr int LEAD = (NW == 4 || CT == 1 ? 8 : 16) / CT;
+    BRow<CT> yb[16];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int j = 0; j < LEAD; ++j) yb[j] = lds_brow<CT>(Yb + j * LDY);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int krow = 16 * hh + 4 * q + s;
+    for (int j = 0; j < 16; ++j) {
+      if (j + LEAD < 16) yb[j + LEAD] = lds_brow<CT>(Yb + (j + LEAD) * LDY);
 #pragma unroll
-        for (int t = 0; t < CT; ++t) out[t] = mfma32(gs[0][q][s], Yc[krow * LDY + t * 32 + r31], out[t]);
-      }
+      for (int t = 0; t < CT; ++t) out[t] = mfma32(gs[0][j >> 2][j & 3], yb[j].v[t], out[t]);
     }
+    brow_schedule<CT, LEAD>(16);
 #pragma unroll
     for (int j = 0; j < GA; ++j)
 #pragma unroll
@@ -501,8 +548,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void inbatch_gt_kernel(Sw
 #pragma unroll
       for (int t = 0; t < CT; ++t) {
         float v = out[t][r] * a.c;                          // the stored weights are unscaled sigma(z)
-        if (fix) v -= rs * a.Ys[drow * D + t * 32 + r31];  // G_jj = -r_j
-        dst[orow * D + t * 32 + r31] = v;
+        if (fix) v -= rs * a.Ys[drow * D + r31 * CT + t];  // G_jj = -r_j
+        dst[orow * D + r31 * CT + t] = v;
       }
     }
   }
