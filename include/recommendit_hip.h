@@ -404,6 +404,34 @@ int rihip_rank_features_build(const double* user_tab, int64_t n_user_rows, const
 int rihip_rank_topk(const double* scores, const int64_t* cand, const float* retrieval_scores, int64_t nq, int kc, int k,
                     int64_t* out_ids, double* out_scores, float* out_retrieval_scores, void* stream);
 
+/* ---- evaluation report ------------------------------------------------------------------------
+ * Replaces the per-user loop of evaluate_model (src/evaluation/metrics.py:301-384) and the component functions it
+ * calls: ndcg_at_k (:20-69, binary relevance), recall_at_k (:72-87), precision_at_k (:90-99), mrr (:104-118),
+ * coverage (:143-165), intra_list_diversity (:168-190).  rec_ids device i64 [n, K] (K <= 16384), -1 = padding
+ * anywhere in a row: a row means its entries >= 0, in order.  Ground truth as CSR: gt_offsets [n+1] into gt_items
+ * (each row's segment sorted ascending, de-duplicated), gt_raw [n] = the row's list length with duplicates (IDCG);
+ * gt_raw == 0 -> the user is not scored.  k_values: HOST array of n_k (1..64) values >= 0.  disc[i] = 1/log2(i+2)
+ * and idcg[m] = disc[0] + ... + disc[m-1] (f64, n_tab > max k entries).  Outputs vals f64 [n, n_k, 3] (ndcg,
+ * recall, precision), rr f64 [n] (reciprocal rank over the whole row), scored u8 [n].  With non-NULL flags
+ * (u8 [n_id_space], zeroed here) the ids of scored rows are marked for coverage; an id >= n_id_space sets bit 0
+ * of *err (device int, zeroed here). */
+int rihip_eval_nparts(void);
+int rihip_eval_topk(const int64_t* rec_ids, int64_t n, int K, const int64_t* gt_offsets, const int64_t* gt_items,
+                    const int64_t* gt_raw, const int* k_values, int n_k, const double* disc, const double* idcg,
+                    int n_tab, double* vals, double* rr, uint8_t* scored, uint8_t* flags, int64_t n_id_space, int* err,
+                    void* stream);
+/* intra_list_diversity of recs[:L] of every scored user: item_vectors device f32 [n_rows, g] (g <= 256),
+ * item_present u8 [n_rows] (NULL = every row; ids >= n_rows have no vector); L <= 512.  div f64 [n]. */
+int rihip_eval_diversity(const int64_t* rec_ids, int64_t n, int K, const uint8_t* scored, int L,
+                         const float* item_vectors, int64_t n_rows, int g, const uint8_t* item_present, double* div,
+                         void* stream);
+/* Fixed-order f64 means over the scored users (no float atomics: bitwise reproducible).  div, flags, err nullable.
+ * partials f64 [nparts, 3*n_k+3], cov_partials i64 [nparts] (workspace).  out f64 [3*n_k+5] = means of vals
+ * (k-major), mean rr, mean div, n_scored, distinct flagged ids / catalog_size (0 if catalog_size <= 0), *err. */
+int rihip_eval_reduce(int64_t n, int n_k, const double* vals, const double* rr, const double* div,
+                      const uint8_t* scored, const uint8_t* flags, int64_t n_id_space, int64_t catalog_size,
+                      const int* err, double* partials, int64_t* cov_partials, double* out, void* stream);
+
 /* ---- negative sampler -----------------------------------------------------------------------
  * Replaces UserItemDataset._sample_negative (src/training/train_embeddings.py:58-63) for a batch: neg_out[i] =
  * uniform draw from catalog[], re-drawn (up to max_attempts) while users[i]*key_stride + item is in the sorted

@@ -15,7 +15,7 @@ from __future__ import annotations
 import logging
 import time
 from pathlib import Path
-from typing import Dict, Iterator, List, Optional, Tuple
+from typing import Any, Dict, Iterator, List, Optional, Tuple
 
 import numpy as np
 import pandas as pd
@@ -209,11 +209,12 @@ class EmbeddingTrainer:
 
 
 def retrieval_ndcg(model: TwoTowerModel, ratings_df: pd.DataFrame, movies_df: pd.DataFrame, k_candidates: int = 500,
-                   n_eval_users: int = 200, exact: bool = True) -> Dict[str, float]:
+                   n_eval_users: int = 200, exact: bool = True, on_device: bool = False) -> Dict[str, float]:
     """The reference's `run_evaluate` protocol (src/pipelines/run_pipeline.py:153-230) in its Redis-less form
     (identical default features -> ranker scores tie -> retrieval order decides):
     test set = last N ratings per user by timestamp, N = max(1, int(len*0.1/n_users)); first 200 users;
-    ground truth = test items rated >= 4; candidates = top-500 by inner product; NDCG@{5,10,20} of the top 20."""
+    ground truth = test items rated >= 4; candidates = top-500 by inner product; NDCG@{5,10,20} of the top 20.
+    on_device=True: the candidate ids stay on the device and eval_device scores them (same report)."""
     from .faiss_index import FAISSIndex
     from .metrics import evaluate_model
     n_users = ratings_df["user_id"].nunique()
@@ -227,7 +228,48 @@ def retrieval_ndcg(model: TwoTowerModel, ratings_df: pd.DataFrame, movies_df: pd
     index = FAISSIndex(embed_dim=model.embed_dim, exact=exact)
     index.build_ivf_index(embs.astype(np.float32), item_ids)
     U = model.get_user_embeddings(eval_users.astype(np.int64))
-    _, ids = index.batch_search(U, k=k_candidates)
     truth = {int(u): g[g["rating"] >= 4]["item_id"].tolist() for u, g in test[test["user_id"].isin(eval_users)].groupby("user_id")}
+    if on_device:
+        from .eval_device import GroundTruth, evaluate_topk_device
+        # the same f32 query normalisation as batch_search, so the search sees the same queries
+        q = U.astype(np.float32)
+        q = q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), 1e-8)
+        _, ids = index.batch_search_device(torch.from_numpy(np.ascontiguousarray(q)).to(L.device()), k=k_candidates,
+                                           normalized=True)
+        users = [int(u) for u in eval_users]
+        return evaluate_topk_device(ids[:, :20], GroundTruth.from_dict(truth, users), [5, 10, 20])
+    _, ids = index.batch_search(U, k=k_candidates)
     recs = {int(u): [int(x) for x in ids[i][:20] if x >= 0] for i, u in enumerate(eval_users)}
     return evaluate_model(recs, truth, [5, 10, 20])
+
+
+def evaluate_retrieval_all_users(model: TwoTowerModel, index, test_pairs, k_candidates: int = 500, top: int = 20,
+                                 batch: int = 65536, k_values=(5, 10, 20), catalog_size: Optional[int] = None,
+                                 item_vectors: Optional[torch.Tensor] = None,
+                                 item_present: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+    """Whole-population retrieval evaluation (not in the reference, which scores 200 users): every user of
+    ``test_pairs`` (a frame with user_id / item_id columns, or a (users, items) pair of arrays: the relevant items)
+    is retrieved in batches of ``batch`` users (top ``k_candidates`` by inner product, the first ``top`` kept) into
+    one device tensor, which eval_device scores; only the report comes back to the host.  Users in order of first
+    appearance in ``test_pairs``."""
+    from .eval_device import GroundTruth, evaluate_topk_device
+    if isinstance(test_pairs, tuple):
+        pu, pi = (np.asarray(x, dtype=np.int64) for x in test_pairs)
+    else:
+        pu, pi = test_pairs["user_id"].to_numpy(np.int64), test_pairs["item_id"].to_numpy(np.int64)
+    _, first = np.unique(pu, return_index=True)
+    users = pu[np.sort(first)]
+    if users.shape[0] == 0:
+        return {"error": "No users to evaluate", "n_users": 0}
+    truth = GroundTruth.from_pairs(users, pu, pi)
+    dev = L.device()
+    top = min(top, k_candidates)
+    recs = torch.full((users.shape[0], top), -1, dtype=torch.int64, device=dev)
+    uid = torch.from_numpy(users).to(dev)
+    for s in range(0, users.shape[0], batch):
+        U = model.get_user_embeddings(uid[s:s + batch], as_tensor=True)
+        _, ids = index.batch_search_device(U, k=k_candidates)
+        recs[s:s + ids.shape[0], :min(top, ids.shape[1])] = ids[:, :top]
+    n_id = int(np.max(index.item_ids)) + 1 if catalog_size else None
+    return evaluate_topk_device(recs, truth, list(k_values), catalog_size=catalog_size, item_vectors=item_vectors,
+                                item_present=item_present, n_id_space=n_id)
