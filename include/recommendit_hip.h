@@ -432,6 +432,40 @@ int rihip_eval_reduce(int64_t n, int n_k, const double* vals, const double* rr, 
                       const uint8_t* scored, const uint8_t* flags, int64_t n_id_space, int64_t catalog_size,
                       const int* err, double* partials, int64_t* cov_partials, double* out, void* stream);
 
+/* ---- training-serving skew ------------------------------------------------------------------
+ * Replaces the per-column loop of detect_training_serving_skew and the histograms of kl_divergence_bins
+ * (src/evaluation/metrics.py:197-294) for two row-major device samples A [na, lda] and B [nb, ldb] (f32, or f64 when
+ * *_f64 != 0).  Column c is cols_a[c] of A against cols_b[c] of B (device int32 [nc]; an index outside [0, ld) gives
+ * status RIHIP_SKEW_BAD_COLUMN); ids_a / ids_b (device int64 [na] / [nb], nullable): a row whose id is < 0 is left out.
+ * Per column, in f64: edges [nc, n_bins+1] = np.linspace(min, max, n_bins + 1) of the combined non-NaN range (bit for
+ * bit), counts i64 [nc, 2, n_bins] = np.histogram of each sample on those edges (NaN never counted; zero when the
+ * range is not finite or is a single value), valid i64 [nc, 2] = non-NaN values per sample, kl f64 [nc] = sum(p *
+ * log(p / q)) of the densities + epsilon, normalised, status i32 [nc].  min_count: fewer non-NaN values on either side
+ * -> RIHIP_SKEW_TOO_FEW (the detector's skip); propagate_nan != 0: any NaN -> kl nan (kl_divergence_bins on raw
+ * input).  n_bins 1..128.  No host synchronisation; capturable in a hipGraph; bitwise repeatable (no float atomics). */
+#define RIHIP_SKEW_OK 0
+#define RIHIP_SKEW_CONSTANT 1     /* min == max: kl 0.0 */
+#define RIHIP_SKEW_INFINITE 2     /* an infinite bound: kl nan */
+#define RIHIP_SKEW_NAN 3          /* propagate_nan and a NaN in the input: kl nan */
+#define RIHIP_SKEW_TOO_FEW 4      /* fewer than min_count values on a side: kl nan, the column is not checked */
+#define RIHIP_SKEW_BAD_COLUMN 5   /* a column index outside its row: kl nan */
+int64_t rihip_skew_workspace_bytes(int nc);
+int rihip_skew_compute(const void* A, int a_f64, int64_t na, int64_t lda, const int* cols_a, const int64_t* ids_a,
+                       const void* B, int b_f64, int64_t nb, int64_t ldb, const int* cols_b, const int64_t* ids_b,
+                       int nc, int n_bins, double epsilon, int64_t min_count, int propagate_nan, void* workspace,
+                       int64_t workspace_bytes, int64_t* counts, double* edges, int64_t* valid, double* kl,
+                       int* status, void* stream);
+/* Serving feature log (the "feature DataFrame from serving (recent requests)" that detect_training_serving_skew,
+ * src/evaluation/metrics.py:234-260, compares against): appends the ranking-feature rows X f32 [n_rows, nf] of one
+ * served batch (n_rows = nq * kc; row r belongs to user_ids[r / kc] and candidate cand_ids[r], -1 = padding) to the
+ * device ring [R, nf] / ring_user [R] / ring_item [R] at slot (cursor[0] + r) % R, keeping the newest R rows of the
+ * batch; then cursor[1] = cursor[0] (the batch's start) and cursor[0] += n_rows.  cursor: device int64 [2].
+ * rewind: cursor[0] = cursor[1] (the batch is logged again, e.g. after the exactness re-do). */
+int rihip_feature_log_append(const float* X, int64_t n_rows, int nf, const int64_t* user_ids, const int64_t* cand_ids,
+                             int kc, float* ring, int64_t* ring_user, int64_t* ring_item, int64_t R, int64_t* cursor,
+                             void* stream);
+int rihip_feature_log_rewind(int64_t* cursor, void* stream);
+
 /* ---- negative sampler -----------------------------------------------------------------------
  * Replaces UserItemDataset._sample_negative (src/training/train_embeddings.py:58-63) for a batch: neg_out[i] =
  * uniform draw from catalog[], re-drawn (up to max_attempts) while users[i]*key_stride + item is in the sorted

@@ -1,13 +1,18 @@
 """Ranking metrics used by the parity harness -- same definitions as the reference's
 src/evaluation/metrics.py (ndcg_at_k :20-69, recall_at_k :72-87, precision_at_k :90-99, mrr :104-118,
 average_precision :121-136, coverage :143-165, intra_list_diversity :168-190, evaluate_model :301-384: mean over
-users that have at least one relevant item).  The device form of evaluate_model is eval_device.evaluate_topk_device."""
+users that have at least one relevant item; kl_divergence_bins :197-231 and detect_training_serving_skew :234-294).
+The device form of evaluate_model is eval_device.evaluate_topk_device, that of the skew detector
+skew_device.detect_training_serving_skew_device."""
 from __future__ import annotations
 
 import math
+import logging
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
+
+logger = logging.getLogger(__name__)
 
 
 def ndcg_at_k(recommended: Sequence[Any], relevant: Sequence[Any], k: int,
@@ -127,3 +132,62 @@ def evaluate_model(recommendations_by_user: Dict[Any, List[Any]], ground_truth_b
     if divs:
         res["avg_diversity"] = float(np.mean(divs))
     return res
+
+
+def kl_divergence_bins(p_values: np.ndarray, q_values: np.ndarray, n_bins: int = 20, epsilon: float = 1e-10) -> float:
+    """KL(P || Q) of two samples binned on the edges np.linspace(min, max, n_bins + 1) of their combined range;
+    densities + epsilon, renormalised.  0.0 when the combined range is a single value; a NaN or an infinite value gives
+    nan (numpy warns, nothing raises)."""
+    combined = np.concatenate([p_values, q_values])
+    lo, hi = combined.min(), combined.max()
+    if lo == hi:
+        return 0.0
+    edges = np.linspace(lo, hi, n_bins + 1)
+    p = np.histogram(p_values, bins=edges, density=True)[0] + epsilon
+    q = np.histogram(q_values, bins=edges, density=True)[0] + epsilon
+    p = p / p.sum()
+    q = q / q.sum()
+    return float(np.sum(p * np.log(p / q)))
+
+
+SKEW_MIN_COUNT = 10   # a column with fewer non-NaN values on either side is not checked
+
+
+def skew_columns(train_numeric: Sequence[str], serving_columns: Sequence[str],
+                 numeric_cols: Optional[Sequence[str]] = None) -> List[str]:
+    """the columns the detector checks: the given list, else train's numeric columns that serving also has, in train's
+    order"""
+    if numeric_cols is not None:
+        return list(numeric_cols)
+    have = set(serving_columns)
+    return [c for c in train_numeric if c in have]
+
+
+def skew_report(feature_kl: Dict[str, float], threshold: float) -> Dict[str, Any]:
+    """the detector's result dict from the rounded per-column KL values"""
+    flagged = [c for c, v in feature_kl.items() if v > threshold]
+    res = {"feature_kl": feature_kl, "flagged_features": flagged,
+           "max_kl": max(feature_kl.values()) if feature_kl else 0.0, "skew_detected": len(flagged) > 0,
+           "threshold": threshold, "n_features_checked": len(feature_kl)}
+    if flagged:
+        logger.warning("Training-serving skew detected in %d features: %s", len(flagged), flagged[:5])
+    else:
+        logger.info("No significant training-serving skew detected.")
+    return res
+
+
+def detect_training_serving_skew(train_features_df, serving_features_df, threshold: float = 0.1,
+                                 numeric_cols: Optional[List[str]] = None) -> Dict[str, Any]:
+    """per-column kl_divergence_bins (default bins) of train against serving, NaN dropped per column; a column with
+    fewer than SKEW_MIN_COUNT values on either side is skipped; values are stored rounded to 6 decimals and flagged
+    when > threshold"""
+    cols = skew_columns(train_features_df.select_dtypes(include=[np.number]).columns, serving_features_df.columns,
+                        numeric_cols)
+    feature_kl: Dict[str, float] = {}
+    for c in cols:
+        a = train_features_df[c].dropna().values.astype(float)
+        b = serving_features_df[c].dropna().values.astype(float)
+        if len(a) < SKEW_MIN_COUNT or len(b) < SKEW_MIN_COUNT:
+            continue
+        feature_kl[c] = round(kl_divergence_bins(a, b), 6)
+    return skew_report(feature_kl, threshold)

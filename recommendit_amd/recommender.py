@@ -165,13 +165,19 @@ def build_ranking_features_device(store: GpuFeatureStore, user_ids: torch.Tensor
 
 class GpuRecommendationPipeline:
     def __init__(self, model: TwoTowerModel, index: FAISSIndex, ranker: LightGBMRanker, store: GpuFeatureStore,
-                 top_k_candidates: int = 500, top_k_results: int = 20):
-        """defaults = settings.TOP_K_CANDIDATES / TOP_K_RESULTS (src/config.py:11-12)"""
+                 top_k_candidates: int = 500, top_k_results: int = 20, feature_log_rows: int = 0):
+        """defaults = settings.TOP_K_CANDIDATES / TOP_K_RESULTS (src/config.py:11-12).
+
+        feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
+        device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
+        serving_features(), detect_skew(), reset_feature_log().  0 leaves the chain as it is."""
         self.model, self.index, self.ranker, self.store = model, index, ranker, store
         self.top_k_candidates, self.top_k_results = top_k_candidates, top_k_results
         self._graphs: Dict[Tuple[int, int], Any] = {}
         self._pin: Dict[int, Any] = {}
         self._defer = os.environ.get("RIHIP_SERVE_DEFER", "1") != "0"   # 0: exactness check inside the search (experiments)
+        self._log: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None
+        self.reset_feature_log(feature_log_rows)
 
     @torch.no_grad()
     def recommend_batch(self, user_ids, k: Optional[int] = None, graph: bool = False
@@ -209,6 +215,8 @@ class GpuRecommendationPipeline:
         if redone:
             if uid is None:
                 uid = self._ids_to_device(user_ids)
+            if self._log is not None:       # the batch is logged again with its final candidates: drop the first rows
+                L.check(L.lib().rihip_feature_log_rewind(self._log[3].data_ptr(), L.stream_ptr()), "feature_log_rewind")
             out = self._chain(uid, k)
         return out
 
@@ -238,7 +246,8 @@ class GpuRecommendationPipeline:
         identity of the feature tables and of the three stage objects"""
         ut, it = self.store.device_tables()
         return (int(L.lib().rihip_scratch_generation()), ut.data_ptr(), it.data_ptr(), id(self.index), id(self.ranker),
-                id(self.model), self.top_k_candidates, tuple(self.ranker.feature_names))
+                id(self.model), self.top_k_candidates, tuple(self.ranker.feature_names),
+                None if self._log is None else (self._log[0].data_ptr(), self._log[0].shape[0]))
 
     def _replay(self, user_ids, k: int):
         nq = len(user_ids)
@@ -258,7 +267,7 @@ class GpuRecommendationPipeline:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):      # warm-up: scratch buffers, LDS grants, lazy module loads
                     for _ in range(2):
-                        self._chain(su, k)
+                        self._chain(su, k, log=False)
                         self.index.finish_search()
                 cur.wait_stream(side)
                 torch.cuda.synchronize()
@@ -280,13 +289,15 @@ class GpuRecommendationPipeline:
         # a replay runs no host code: the failure count of its deferred search is read here (one synchronisation)
         return out, (self.index.last_fail_count() if deferred else 0)
 
-    def _chain(self, uid: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _chain(self, uid: torch.Tensor, k: int, log: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
         rs, cand = self.index.batch_search_device(q, k=self.top_k_candidates, normalized=True)
         nq, kc = cand.shape
         X = build_ranking_features_device(self.store, uid, cand, self.ranker.feature_names)
+        if log and self._log is not None:
+            self._append_log(X, uid, cand)
         scores = self.ranker.predict_device(X)
         k = min(k, kc)
         ids = torch.empty((nq, k), dtype=torch.int64, device=cand.device)
@@ -295,6 +306,76 @@ class GpuRecommendationPipeline:
         L.check(L.lib().rihip_rank_topk(scores.data_ptr(), cand.data_ptr(), rs.data_ptr(), nq, kc, k, ids.data_ptr(),
                                         top.data_ptr(), trs.data_ptr(), L.stream_ptr()), "rank_topk")
         return ids, top, trs
+
+    # ---- serving feature log -------------------------------------------------------------------------------------
+    def reset_feature_log(self, rows: Optional[int] = None) -> None:
+        """clear the log; rows (optional) resizes the ring (0 turns logging off).  A resize re-captures graphs."""
+        R = (0 if self._log is None else self._log[0].shape[0]) if rows is None else int(rows)
+        if R < 0:
+            raise ValueError(f"feature_log_rows={R} < 0")
+        if R == 0:
+            self._log = None
+            return
+        nf = len(self.ranker.feature_names)
+        if self._log is None or self._log[0].shape != (R, nf):
+            dev = L.device()
+            self._log = (torch.zeros((R, nf), dtype=torch.float32, device=dev),
+                         torch.empty((R,), dtype=torch.int64, device=dev),
+                         torch.empty((R,), dtype=torch.int64, device=dev),
+                         torch.empty((2,), dtype=torch.int64, device=dev))
+        ring, ru, ri, cur = self._log
+        ru.fill_(-1)
+        ri.fill_(-1)                  # never-written slots read as padding: the detector skips them
+        cur.zero_()
+
+    @property
+    def feature_log_rows(self) -> int:
+        return 0 if self._log is None else int(self._log[0].shape[0])
+
+    def _append_log(self, X: torch.Tensor, uid: torch.Tensor, cand: torch.Tensor) -> None:
+        ring, ru, ri, cur = self._log
+        n, nf = X.shape
+        if nf != ring.shape[1]:
+            raise RuntimeError(f"feature log holds {ring.shape[1]} features, the ranker builds {nf}: reset_feature_log()")
+        L.check(L.lib().rihip_feature_log_append(X.data_ptr(), n, nf, uid.data_ptr(), cand.data_ptr(), cand.shape[1],
+                                                 ring.data_ptr(), ru.data_ptr(), ri.data_ptr(), ring.shape[0],
+                                                 cur.data_ptr(), L.stream_ptr()), "feature_log_append")
+
+    def _log_order(self) -> torch.Tensor:
+        """ring slots oldest -> newest (one synchronisation: the cursor)"""
+        R = self._log[0].shape[0]
+        c = int(self._log[3][0].item())
+        dev = self._log[0].device
+        if c <= R:
+            return torch.arange(c, device=dev)
+        return (torch.arange(R, device=dev) + c) % R
+
+    def serving_features(self):
+        """DataFrame [user_id, item_id, *ranker.feature_names] of the logged rows, oldest to newest, padded candidates
+        dropped: the serving side of metrics.detect_training_serving_skew"""
+        import pandas as pd
+        if self._log is None:
+            raise RuntimeError("the feature log is off (feature_log_rows=0)")
+        ring, ru, ri, _ = self._log
+        o = self._log_order()
+        keep = o[ri[o] >= 0]
+        X = ring[keep].cpu().numpy()
+        cols = {"user_id": ru[keep].cpu().numpy(), "item_id": ri[keep].cpu().numpy()}
+        for j, name in enumerate(self.ranker.feature_names):
+            cols[name] = X[:, j]
+        return pd.DataFrame(cols)
+
+    def detect_skew(self, train_features, threshold: float = 0.1, numeric_cols: Optional[List[str]] = None,
+                    columns: Optional[Sequence[str]] = None) -> Dict[str, Any]:
+        """skew_device.detect_training_serving_skew_device of train_features against the logged rows, read in place on
+        the device (the ring is not copied to the host); the same result as the host detector on serving_features()"""
+        from . import skew_device as S
+        if self._log is None:
+            raise RuntimeError("the feature log is off (feature_log_rows=0)")
+        ring, ru, ri, _ = self._log
+        ids = torch.stack([ru, ri], dim=1).to(torch.float64)
+        serving = [S._Segment(ring, list(self.ranker.feature_names), ri), S._Segment(ids, ["user_id", "item_id"], ri)]
+        return S.detect_training_serving_skew_device(train_features, serving, threshold, numeric_cols, columns)
 
     def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False) -> List[Dict[str, Any]]:
         ids, sc, rs = self.recommend_batch([user_id], k, graph=graph)
