@@ -162,6 +162,18 @@ __device__ __forceinline__ void brow_schedule(int nrows) {
     __builtin_amdgcn_sched_group_barrier(0x8, RPI * CT, 0);    // MFMA
   }
 }
+// Scalar (kernel-argument) loads share lgkmcnt with the LDS reads and return out of order: one still pending at a
+// loop's entry makes the first LDS wait of every trip a full lgkmcnt(0).  Called in front of the tile loops.
+__device__ __forceinline__ void scalar_loads_done() { __builtin_amdgcn_s_waitcnt(0xc07f); }  // lgkmcnt(0) only
+// The steady tile loops address global memory as a uniform base (a buffer resource rebuilt from an advancing scalar
+// pointer once per trip, so there is no 4 GB window) plus a constant 32-bit lane offset plus a constant: no per-lane
+// 64-bit address arithmetic.  Reads past `bytes` return 0; the loops never make one.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const float* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);  // raw, 32-bit data
+}
+__device__ __forceinline__ f32x4 buffer_load_f32x4(__amdgpu_buffer_rsrc_t r, unsigned lane_off, int off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, off, 0));
+}
 // GOUT (user mode only): additionally write the G tile (diagonal and ragged entries = 0) to a.gmat, so that the item
 // gradients come from a plain G^T.U product (inbatch_gt_kernel) instead of a second score sweep.
 template <int D, bool MODE_USER, bool GOUT = false, int NW = 4>
@@ -179,7 +191,8 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
   __shared__ float rsum[NW][32];
   __shared__ double red_loss[NW];
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  // w through readfirstlane: the wave index is uniform, and the tile tests built on o_base then stay in SGPRs
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r31 = lane & 31, hh = lane >> 5;
   const int64_t o_base = (int64_t)blockIdx.x * (NW * 32) + w * 32;
   const int64_t o_loc = o_base + r31;  // this lane's owner (S^T accumulator column)
@@ -266,12 +279,63 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
     }
   }
 
-#pragma unroll 1
-  for (int64_t tile = t0; tile < t1; ++tile) {
-    const int it = (int)((tile - t0) % 3);
+  // S^T(next tile) chain from Yn into sb, interleaved with the branch-free element work on sa (full tile, off the
+  // diagonal).  Unconditional: on the last tile this multiplies a stale buffer and the result is dropped -- a branch
+  // here splits the block and the scheduler then parks all the VALU work behind the MFMA chain.
+  auto fast_block = [&](const float* Yn, int cur, const f32x16& sa, f32x16& sb, float (&g)[16]) {
+    float den_prod = 1.f;  // running product of (1 + e^-z): one log per eight elements
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(&Yn[r31 * LDY + kb * 8 + 4 * hh]);
+      sb = mfma32(av.x, xo[kb].x, sb);
+      sb = mfma32(av.y, xo[kb].y, sb);
+      sb = mfma32(av.z, xo[kb].z, sb);
+      sb = mfma32(av.w, xo[kb].w, sb);
+#pragma unroll
+      for (int e = 0; e < EPK; ++e) {
+        const int r = kb * EPK + e;
+        const float pos = MODE_USER ? pos_o : posS[cur][acc_row(r, lane)];
+        g[r] = sweep_elem<MODE_USER, true>(sa[r], pos, true, false, 0.f, loss_acc, den_prod, r_acc);
+        if constexpr (SWEEP_STEADY(D, MODE_USER, GOUT, NW)) {
+          // The SLP vectoriser pairs independent f32 adds (loss_acc with r_acc, 1 + e of two elements) into v_pk_*_f32,
+          // which cost far more than two scalar ops beside the MFMAs.  An empty asm makes each value opaque to it.
+          asm("" : "+v"(loss_acc));
+          asm("" : "+v"(r_acc));
+          asm("" : "+v"(g[r]));
+          asm("" : "+v"(den_prod));
+        }
+        if (MODE_USER && (r & 7) == 7) {
+          loss_acc += __builtin_amdgcn_logf(den_prod);
+          den_prod = 1.f;
+        }
+      }
+    }
+  };
+  // ---- dOwner[o][c] += sum_s G[s][o] * Y[s][c]   (A operand = g registers, k = acc_row(r))
+  // k-row of g[r] is acc_row(r) = (r & 3) + 8 (r >> 2) + 4 hh; its B operands are read LEAD k-rows ahead.
+  // gstore(k-row within the half, value): the GOUT store of one G element (2 full 128 B lines per wave store)
+  auto gy_block = [&](const float* Yc, const float (&g)[16], auto gstore) {
+    const float* Yb = Yc + 4 * hh * LDY + r31 * CT;
+    constexpr int LEAD = 8 / CT;
+    BRow<CT> yb[16];
+#pragma unroll
+    for (int r = 0; r < LEAD; ++r) yb[r] = lds_brow<CT>(Yb + ((r & 3) + 8 * (r >> 2)) * LDY);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rn = r + LEAD;
+      if (rn < 16) yb[rn] = lds_brow<CT>(Yb + ((rn & 3) + 8 * (rn >> 2)) * LDY);
+      if (GOUT) gstore((r & 3) + 8 * (r >> 2), g[r]);
+#pragma unroll
+      for (int t = 0; t < CT; ++t) out[t] = mfma32(g[r], yb[r].v[t], out[t]);
+    }
+    brow_schedule<CT, LEAD>(16);
+  };
+
+  int64_t tile = t0;
+  int it = 0;  // (tile - t0) % 3: the LDS ring position of the current tile
+  auto general_tile = [&]() {
     const int cur = it, nxt = (it + 1) % 3, pre = (it + 2) % 3;
     const int64_t s_base = tile * TSW;
-    const bool has_next = (tile + 1 < t1);
     const bool has_pre = (tile + 2 < t1);
     if (has_pre) load_tile(tile + 2);  // global loads stay in flight under the MFMA blocks below
 
@@ -287,34 +351,13 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
     const float* Yc = Ysh[cur];
     f32x16 sn = zero16();
     float g[16];
-    float den_prod = 1.f;  // running product of (1 + e^-z): one log per eight elements
     if (!slow) {
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) {
-        {  // unconditional: on the last tile this multiplies a stale buffer and the result is dropped -- a branch
-           // here splits the block and the scheduler then parks all the VALU work behind the MFMA chain
-          const f32x4 av = *reinterpret_cast<const f32x4*>(&Yn[r31 * LDY + kb * 8 + 4 * hh]);
-          sn = mfma32(av.x, xo[kb].x, sn);
-          sn = mfma32(av.y, xo[kb].y, sn);
-          sn = mfma32(av.z, xo[kb].z, sn);
-          sn = mfma32(av.w, xo[kb].w, sn);
-        }
-#pragma unroll
-        for (int e = 0; e < EPK; ++e) {
-          const int r = kb * EPK + e;
-          const float pos = MODE_USER ? pos_o : posS[cur][acc_row(r, lane)];
-          g[r] = sweep_elem<MODE_USER, true>(st[r], pos, true, false, 0.f, loss_acc, den_prod, r_acc);
-          if (MODE_USER && (r & 7) == 7) {
-            loss_acc += __builtin_amdgcn_logf(den_prod);
-            den_prod = 1.f;
-          }
-        }
-      }
+      fast_block(Yn, cur, st, sn, g);
     } else {
+      float den_prod = 1.f;
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
-        {  // unconditional: on the last tile this multiplies a stale buffer and the result is dropped -- a branch
-           // here splits the block and the scheduler then parks all the VALU work behind the MFMA chain
+        {  // unconditional, as in fast_block
           const f32x4 av = *reinterpret_cast<const f32x4*>(&Yn[r31 * LDY + kb * 8 + 4 * hh]);
           sn = mfma32(av.x, xo[kb].x, sn);
           sn = mfma32(av.y, xo[kb].y, sn);
@@ -337,27 +380,91 @@ __global__ __launch_bounds__(NW * 64, 2) void inbatch_sweep_kernel(SweepArgs a) 
         }
       }
     }
-    // ---- dOwner[o][c] += sum_s G[s][o] * Y[s][c]   (A operand = g registers, k = acc_row(r))
     float* gp = nullptr;
     if (GOUT) gp = a.gmat + ((size_t)tile * a.g_ub + (size_t)blockIdx.x * NW + w) * 1024 + (4 * hh) * 32 + r31;
-    // k-row of g[r] is acc_row(r) = (r & 3) + 8 (r >> 2) + 4 hh; its B operands are read LEAD k-rows ahead
-    const float* Yb = Yc + 4 * hh * LDY + r31 * CT;
-    constexpr int LEAD = 8 / CT;
-    BRow<CT> yb[16];
-#pragma unroll
-    for (int r = 0; r < LEAD; ++r) yb[r] = lds_brow<CT>(Yb + ((r & 3) + 8 * (r >> 2)) * LDY);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rn = r + LEAD;
-      if (rn < 16) yb[rn] = lds_brow<CT>(Yb + ((rn & 3) + 8 * (rn >> 2)) * LDY);
-      if (GOUT) gp[((r & 3) + 8 * (r >> 2)) * 32] = g[r];  // 2 full 128 B lines per wave store
-#pragma unroll
-      for (int t = 0; t < CT; ++t) out[t] = mfma32(g[r], yb[r].v[t], out[t]);
-    }
-    brow_schedule<CT, LEAD>(16);
+    gy_block(Yc, g, [&](int krow, float v) { gp[krow * 32] = v; });
     if (has_pre) store_tile(pre);
     st = sn;
     __syncthreads();
+    ++tile;
+    it = (it == 2 ? 0 : it + 1);
+  };
+
+  // Which instantiations take the steady loop: SWEEP_STEADY (loss_sweep_args.h).  The one-tile loop runs every tile
+  // of the others, and the first three tiles (one turn of the LDS ring) otherwise.
+  constexpr bool STEADY = SWEEP_STEADY(D, MODE_USER, GOUT, NW);
+  const int64_t lead_end = (STEADY && t0 + 3 < t1) ? t0 + 3 : t1;
+  scalar_loads_done();
+#pragma unroll 1
+  while (tile < lead_end) general_tile();
+
+  // Steady tiles: full, off the diagonal band of the workgroup's owners, tile + 2 a full tile of this split -- so no
+  // bounds test, no conditional load and no `slow` evaluation.  They run six per trip (the LDS ring has period 3, the
+  // st / sn pair period 2), so ring positions and accumulator names are static and nothing is copied.  Two ranges:
+  // before the band and after it.  Everything else (the band, the last two tiles, the up to five tiles left before a
+  // range can start at ring position 0) goes through the one-tile code, one tile at a time.
+  if constexpr (STEADY) {
+    static_assert(!STEADY || (MODE_USER && GOUT && (TSW * (D / 4)) % NT == 0), "user pass with stored G, whole rows");
+    const int ntl = (int)(t1 - t0);
+    auto rel = [&](int64_t t) { t -= t0; return (int)(t < 0 ? 0 : (t > ntl ? ntl : t)); };  // tile -> [0, ntl]
+    const int64_t nfull = a.Ns / TSW;
+    const bool wg_full = (int64_t)(blockIdx.x + 1) * (NW * 32) <= a.No;
+    const int s_lim = wg_full ? rel((t1 < nfull ? t1 : nfull) - 2) : 0;
+    // tiles [band_lo, band_hi) hold a diagonal element of one of the workgroup's NW * 32 owners
+    const int64_t ddw = a.o_goff + (int64_t)blockIdx.x * (NW * 32) - a.s_goff;
+    const int band_lo = rel(ddw >> 5), band_hi = rel((ddw + NW * 32 + 31) >> 5);
+    const unsigned soff = (unsigned)((tid / (D / 4)) * LDY + (tid % (D / 4)) * 4) * 4u;  // store_tile's address, i = 0
+    const unsigned yoff = (unsigned)tid * 16u, goff = (unsigned)((4 * hh) * 32 + r31) * 4u;
+    constexpr int YB = TSW * D * 4;  // bytes per swept tile
+    int rt = (int)(tile - t0);
+    auto steady_tile = [&](int p, __amdgpu_buffer_rsrc_t ry, const float* gblk, const f32x16& sa, f32x16& sb) {
+      const int cur = p % 3, nxt = (p + 1) % 3, pre = (p + 2) % 3;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) stage[i] = buffer_load_f32x4(ry, yoff, p * YB + i * NT * 16);
+      float g[16];
+      sb = zero16();
+      fast_block(Ysh[nxt], cur, sa, sb, g);
+      const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(gblk, 4096);
+      gy_block(Ysh[cur], g, [&](int krow, float v) {
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rg, (int)goff, krow * 128, 0);
+      });
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(Ysh[pre]) + (soff + i * (NT / (D / 4)) * LDY * 4)) = stage[i];
+      __syncthreads();
+    };
+#pragma unroll 1
+    for (;;) {
+      int n = 0;  // steady tiles from here (a multiple of 6)
+      if (it == 0) {
+        const int end = rt < band_lo ? (band_lo < s_lim ? band_lo : s_lim) : (rt >= band_hi ? s_lim : rt);
+        n = end > rt ? (end - rt) / 6 * 6 : 0;
+      }
+      if (n > 0) {
+        const float* yt = a.Ys + (tile + 2) * (TSW * D);  // tile + 2 of the trip's first tile
+        const size_t gstep = (size_t)a.g_ub * 1024;
+        const float* gt = a.gmat + ((size_t)tile * a.g_ub + (size_t)blockIdx.x * NW + w) * 1024;
+        scalar_loads_done();
+#pragma unroll 1
+        for (int k = n; k > 0; k -= 6) {
+          const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(yt, 6 * YB);
+          f32x16 sn;
+          steady_tile(0, ry, gt, st, sn);
+          steady_tile(1, ry, gt + gstep, sn, st);
+          steady_tile(2, ry, gt + 2 * gstep, st, sn);
+          steady_tile(3, ry, gt + 3 * gstep, sn, st);
+          steady_tile(4, ry, gt + 4 * gstep, st, sn);
+          steady_tile(5, ry, gt + 5 * gstep, sn, st);
+          yt += 6 * TSW * D;
+          gt += 6 * gstep;
+        }
+        tile += n;
+        rt += n;
+      }
+      if (rt >= ntl) break;
+      general_tile();
+      ++rt;
+    }
   }
 
   // ---- epilogue
@@ -504,17 +611,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void inbatch_gt_kernel(Sw
     if (t0 + 1 < t1) load_tile(t0 + 1);  // stays in registers until the top of the first iteration
     __syncthreads();
   }
-  int it = 0;
-#pragma unroll 1
-  for (int64_t tile = t0; tile < t1; ++tile, it = (it == 2 ? 0 : it + 1)) {
-    const int cur = it, nxt = (it + 1) % 3;
-    if (tile + 1 < t1) store_tile(nxt);  // buffer nxt was last read two iterations ago
-    if (tile + 2 < t1) load_tile(tile + 2);
-    if (tile + GA < t1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) gs[GA][q] = gp[(size_t)(tile + GA) * 256 + q];
-    }
-    // lane (r31, hh) consumes k-rows 16 hh .. 16 hh + 15 in order; row j + LEAD is requested before row j's MFMAs
+  // out += G(tile)^T . Y(tile): lane (r31, hh) consumes k-rows 16 hh .. 16 hh + 15 in order; row j + LEAD is requested
+  // before row j's MFMAs
+  // early_barrier: the tile's barrier goes in front of the last k-row's MFMAs (they read registers only), where the
+  // wait for that row's operands -- the last read in flight, so a full lgkmcnt(0) -- is the barrier's own
+  auto gy_tile = [&](int cur, const f32x4 (&g)[4], bool early_barrier) {
     const float* Yb = Ysh[cur] + 16 * hh * LDY + r31 * CT;
     // k-rows read ahead: 16 MFMAs (about 1000 cycles) of lead, 8 under the 168-VGPR cap of the 3-wave form and at
     // d = 32 (where a lead of the whole tile leaves the scheduler no room and it falls back to a wait per read)
@@ -525,15 +626,80 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void inbatch_gt_kernel(Sw
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       if (j + LEAD < 16) yb[j + LEAD] = lds_brow<CT>(Yb + (j + LEAD) * LDY);
+      if (early_barrier && j == 15) __syncthreads();
 #pragma unroll
-      for (int t = 0; t < CT; ++t) out[t] = mfma32(gs[0][j >> 2][j & 3], yb[j].v[t], out[t]);
+      for (int t = 0; t < CT; ++t) out[t] = mfma32(g[j >> 2][j & 3], yb[j].v[t], out[t]);
     }
     brow_schedule<CT, LEAD>(16);
+  };
+  // Steady tiles (GT_STEADY instantiations): tile + 2 is a full tile of this split, so every load of the iteration
+  // is unconditional.  They run in a loop of three tiles per trip (the period of the LDS ring and, with GA = 2, of
+  // the G ring), so buffer indices and the gs[] names are static and nothing is copied; the swept rows and the G
+  // blocks are addressed as a uniform base that advances by one tile plus a constant 32-bit lane offset.  The
+  // one-tile code runs whatever is left: the last tiles of the split and ragged swept ranges.
+  constexpr bool STEADY = GT_STEADY(D, NW);
+  int64_t tile = t0;
+  int it = 0;
+  auto general_tile = [&]() {
+    const int cur = it, nxt = (it + 1) % 3;
+    if (tile + 1 < t1) store_tile(nxt);  // buffer nxt was last read two iterations ago
+    if (tile + 2 < t1) load_tile(tile + 2);
+    if (tile + GA < t1) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gs[GA][q] = gp[(size_t)(tile + GA) * 256 + q];
+    }
+    gy_tile(cur, gs[0], false);
 #pragma unroll
     for (int j = 0; j < GA; ++j)
 #pragma unroll
       for (int q = 0; q < 4; ++q) gs[j][q] = gs[j + 1][q];
     __syncthreads();
+    ++tile;
+    it = (it == 2 ? 0 : it + 1);
+  };
+  // The one-tile loop: every tile of the instantiations without a steady loop, the first three otherwise (one turn
+  // of the ring, so that the steady loop starts at phase 0 like t0 does).
+  const int64_t lead_end = (STEADY && t0 + 3 < t1) ? t0 + 3 : t1;
+  scalar_loads_done();
+#pragma unroll 1
+  while (tile < lead_end) general_tile();
+  if constexpr (STEADY) {
+    static_assert(!STEADY || (GA == 2 && (TSW * (D / 4)) % NT == 0), "three-tile period, whole float4 rows");
+    const int64_t nfull = a.Ns / TSW;
+    const int64_t s_lim = (t1 < nfull ? t1 : nfull) - 2;
+    const int64_t s_end = s_lim > tile ? tile + (s_lim - tile) / 3 * 3 : tile;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const float* yt = a.Ys + (tile + 2) * (TSW * D);  // tile + 2 of the trip's first tile
+    const float* gt = a.gmat + ((size_t)(blockIdx.x * NW + wu) * a.g_ub + (tile + 2)) * 1024;
+    const unsigned soff = (unsigned)((tid / (D / 4)) * LDY + (tid % (D / 4)) * 4) * 4u;  // store_tile's address, i = 0
+    const unsigned yoff = (unsigned)tid * 16u, goff = (unsigned)(r31 * 32 + 16 * hh) * 4u;
+    constexpr int YB = TSW * D * 4, GB = 4096;  // bytes per swept tile, per G block
+    auto steady_tile = [&](int p, __amdgpu_buffer_rsrc_t ry, __amdgpu_buffer_rsrc_t rg) {  // p = tile % 3, static
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(Ysh[(p + 1) % 3]) + (soff + i * (NT / (D / 4)) * LDY * 4)) = stage[i];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) stage[i] = buffer_load_f32x4(ry, yoff, p * YB + i * NT * 16);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gs[(p + 2) % 3][q] = buffer_load_f32x4(rg, goff, p * GB + 16 * q);
+      __builtin_amdgcn_sched_group_barrier(0x200, NV, 0);      // DS write, then the VMEM reads: a full tile (and
+      __builtin_amdgcn_sched_group_barrier(0x020, NV + 4, 0);  // for G two) ahead of their use, as in the one-tile loop
+      gy_tile(p, gs[p], true);
+    };
+    scalar_loads_done();
+#pragma unroll 1
+    for (int n = (int)(s_end - tile); n > 0; n -= 3) {
+      const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(yt, 3 * YB), rg = buffer_rsrc(gt, 3 * GB);
+      steady_tile(0, ry, rg);
+      steady_tile(1, ry, rg);
+      steady_tile(2, ry, rg);
+      yt += 3 * TSW * D;
+      gt += 3 * 1024;
+    }
+    tile = s_end;
+    scalar_loads_done();
+#pragma unroll 1
+    while (tile < t1) general_tile();  // the last tiles of the split and ragged swept ranges
   }
 
   const bool final_pass = (a.nsplit == 1);

@@ -24,6 +24,10 @@ struct SweepArgs {
 
 constexpr int OW = 128;  // owners per workgroup (32 per wave)
 constexpr int TSW = 32;  // swept rows per LDS tile (shared by the 4 waves)
+// Instantiations of inbatch_gt_kernel and inbatch_sweep_kernel whose full interior tiles run in the unrolled steady-state loop (loss.hip); the
+// others keep the one-tile loop for every tile.  tests/test_loss_isa_steady.py mirrors this table.
+constexpr bool GT_STEADY(int d, int nw) { return d == 128 && nw == 8; }
+constexpr bool SWEEP_STEADY(int d, bool mode_user, bool gout, int nw) { return d == 128 && mode_user && gout && nw == 8; }
 
 // Workgroup = 4 waves x 32 register-stationary owners; every wave multiplies the SAME 32-row swept tile,
 // so one 16 KB (d=128) tile feeds 4 x 128 MFMAs.  Software pipeline (3 LDS tile buffers, one barrier per tile):
