@@ -475,6 +475,64 @@ int rihip_sample_negatives(const int64_t* users, int64_t n, const int64_t* catal
                            const int64_t* rated_keys, int64_t n_rated, int64_t key_stride, uint64_t seed,
                            int max_attempts, int64_t* neg_out, int* gave_up, void* stream);
 
+/* ---- LambdaMART training set from raw ratings ---------------------------------------------------
+ * Replaces the pandas stages of FeatureEngineer (src/features/feature_engineering.py): build_user_features :91-166,
+ * build_item_features :172-219, build_training_pairs :225-300 and build_interaction_features :306-370, i.e. what
+ * RankerTrainer.run (src/training/train_ranker.py:45-137) does before LightGBMRanker.train.  All arrays are device
+ * arrays.  Ratings: rating_user / rating_item i64 [R] (ids 1..n_users / 1..n_items), rating_value i32 [R] (1..5),
+ * rating_ts i64 [R] (seconds), in any order, R < 2^31.  Metadata: user_meta f64 [n_users+1, 3] (gender_encoded,
+ * age_normalized, occupation_normalized), item_meta f64 [n_items+1, 19] (year_normalized, 18 genre flags),
+ * item_in_catalog u8 [n_items+1].  *err (device int, zeroed by stats and by join): bit 0 = a rating with an id out
+ * of range, bit 1 = a rating outside 1..5 (such ratings are left out everywhere), bit 2 = a join pair with an id
+ * outside its table (that row of X is zero).  grid_blocks: 0 = the library's launch geometry, > 0 = that many
+ * workgroups (results never depend on it; for tests).
+ *
+ * rihip_ltr_widths: row widths of user_acc (24) / item_acc (3) and the length of totals (8).
+ * rihip_ltr_stats (:104-108, :130-139, :183-187): integer accumulators, zeroed here.  user_acc i64 [n_users+1, 24] =
+ *   count, rating sum, last timestamp (sign bit flipped), ratings >= 4, of those with a catalogue item, unused, 18
+ *   sums of (rating-3)*genre; item_acc i64 [n_items+1, 3] = count, sum, sum of squares.
+ * rihip_ltr_finalize (:110-121, :139-143, :188-193): the two tables in the layout of rihip_rank_features_build (user
+ *   [n_users+1, 24], item [n_items+1, 23], f64; entities without ratings hold the serving defaults, whose
+ *   log_rating_count is 0.0).  scratch: i64 [3] workspace.
+ * rihip_ltr_plan (:248-262, :283-293): per-user buckets of rating positions (bucket_off i64 [n_users+2], bucket i32
+ *   [R]: a user's ratings >= 4 first; cursor i32 [2, n_users+1] workspace), the candidate items (cand_index i32
+ *   [n_items+1], cand_items i64 [n_items+1]: items with a rating, ascending), and per user: user_rows i32 = P_u + m_u with P_u = ratings >= 4,
+ *   m_u = min(P_u * n_negatives, U_u), U_u = candidates the user never rated; 0 when P_u = 0 or U_u < n_negatives;
+ *   query_id i32 (rank among kept users, -1 = dropped); row_start i64 (first row in [train rows | test rows], -1 =
+ *   dropped); groups i32 [n_users+1]: rows per query in that same order.  n_test = max(1, int(n_queries *
+ *   test_ratio)) whole queries are held out by a permutation keyed by seed.  totals i64 [8] = n_rows, n_queries,
+ *   n_train_rows, n_train_queries, largest query, n_candidates, n_test_queries, 0.  At most 2^20 - 1 items.
+ * rihip_ltr_emit (:264-280): a kept user's rows = its positives in (timestamp, input position) order (label 1, its
+ *   rating) then m_u negatives (label 0, rating 0) drawn without replacement, uniformly, from the candidates the user
+ *   never rated, by a permutation keyed by (seed, user id).  Outputs [n_rows]: out_user, out_item, out_query i64,
+ *   out_label f32, out_rating i32.  n_rows must be totals[0] of the plan.
+ * rihip_ltr_join (:306-370): X f32 [n_rows, nf] (nf <= 64) for flat (user, item) rows in TRAINING semantics:
+ *   col_map as in rihip_rank_features_build; user_item_popularity_ratio in float32; a user / item without ratings
+ *   (its row's log_rating_count is 0.0: the left merge finds nothing) gives 0.0 in its columns and in the
+ *   interaction columns, as does NaN metadata. */
+int rihip_ltr_widths(int* user_acc_width, int* item_acc_width, int* n_totals);
+int rihip_ltr_stats(const int64_t* rating_user, const int64_t* rating_item, const int* rating_value,
+                    const int64_t* rating_ts, int64_t n_ratings, int64_t n_users, int64_t n_items,
+                    const double* item_meta, const uint8_t* item_in_catalog, int64_t* user_acc, int64_t* item_acc,
+                    int* err, int grid_blocks, void* stream);
+int rihip_ltr_finalize(const int64_t* user_acc, const int64_t* item_acc, const double* user_meta,
+                       const double* item_meta, int64_t n_users, int64_t n_items, int64_t* scratch, double* user_tab,
+                       double* item_tab, void* stream);
+int rihip_ltr_plan(const int64_t* rating_user, const int64_t* rating_item, const int* rating_value, int64_t n_ratings,
+                   const int64_t* user_acc, const int64_t* item_acc, int64_t n_users, int64_t n_items, int n_negatives,
+                   double test_ratio, uint64_t seed, int64_t* bucket_off, int* bucket, int* cursor, int* cand_index,
+                   int64_t* cand_items, int* user_rows, int* query_id, int64_t* row_start, int* groups, int64_t* totals,
+                   int grid_blocks, void* stream);
+int rihip_ltr_emit(const int64_t* rating_item, const int* rating_value, const int64_t* rating_ts,
+                   const int64_t* user_acc, const int64_t* bucket_off, const int* bucket, const int* cand_index,
+                   const int64_t* cand_items, const int* user_rows, const int* query_id, const int64_t* row_start,
+                   const int64_t* totals, int64_t n_users, int64_t n_items, int64_t n_rows, uint64_t seed,
+                   int64_t* out_user, int64_t* out_item, float* out_label, int* out_rating, int64_t* out_query,
+                   int grid_blocks, void* stream);
+int rihip_ltr_join(const double* user_tab, int64_t n_user_rows, const double* item_tab, int64_t n_item_rows,
+                   const int64_t* user_ids, const int64_t* item_ids, int64_t n_rows, const int* col_map, int nf,
+                   float* X, int* err, int grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,14 @@ SIGNATURES = {
     "rihip_feature_log_append": (C.c_int, [vp, c_i64, C.c_int, vp, vp, C.c_int, vp, vp, vp, c_i64, vp, vp]),
     "rihip_feature_log_rewind": (C.c_int, [vp, vp]),
     "rihip_rank_features_build": (C.c_int, [vp, c_i64, vp, c_i64, vp, vp, c_i64, C.c_int, vp, C.c_int, vp, vp]),
+    "rihip_ltr_widths": (C.c_int, [vp, vp, vp]),
+    "rihip_ltr_stats": (C.c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "rihip_ltr_finalize": (C.c_int, [vp, vp, vp, vp, c_i64, c_i64, vp, vp, vp, vp]),
+    "rihip_ltr_plan": (C.c_int, [vp, vp, vp, c_i64, vp, vp, c_i64, c_i64, C.c_int, C.c_double, C.c_uint64, vp, vp, vp, vp,
+                                 vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "rihip_ltr_emit": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, C.c_uint64, vp, vp,
+                                 vp, vp, vp, C.c_int, vp]),
+    "rihip_ltr_join": (C.c_int, [vp, c_i64, vp, c_i64, vp, vp, c_i64, vp, C.c_int, vp, vp, C.c_int, vp]),
 }
 
 

@@ -30,6 +30,8 @@ except ImportError:
     lgb = None
     LGB_AVAILABLE = False
 
+MAX_DOCS_PER_QUERY = 16384   # csrc/gbdt_train.hip: a query's sorted scores and labels live in LDS
+
 
 class _Forest:
     """Owns one rihip gbdt handle; method names follow lgb.Booster where callers use them."""
@@ -169,6 +171,50 @@ class LightGBMRanker:
         Xv = yv = gv = None
         if valid_df is not None:
             Xv, yv, gv = pack(valid_df)
+        return self._train_packed(X, y, g, Xv, yv, gv, feature_cols, seed, hist_bits, use_missing, split_order)
+
+    def train_device(self, train, valid=None, feature_cols: Optional[List[str]] = None, verbose_eval: int = 50,
+                     seed: int = 2, hist_dtype: str = "int20", use_missing: bool = False, split_order: str = "low"):
+        """``train`` of the hip backend for a training set that already lives on the device (not in the reference):
+        ``train`` / ``valid`` are objects with ``X`` f32 [n, nf] and ``y`` f32 [n] device tensors and ``groups``
+        (int32 rows per query, in row order) -- e.g. the two parts of feature_engineering.LtrDataset.  Same trainer,
+        same parameters and same return value as ``train(..., backend="hip")``; no DataFrame, no upload."""
+        if hist_dtype not in ("int20", "float", "int40") or split_order not in ("low", "lightgbm"):
+            raise ValueError("hist_dtype in {'int20', 'float'}, split_order in {'low', 'lightgbm'}")
+        dev = L.device()
+
+        def pack(part):
+            X, y = part.X, part.y
+            if not (isinstance(X, torch.Tensor) and isinstance(y, torch.Tensor)) or X.dim() != 2 or y.dim() != 1:
+                raise ValueError("train_device: X must be a [n, nf] tensor and y a [n] tensor")
+            if X.device.type != "cuda" or y.device.type != "cuda":
+                raise RuntimeError("train_device: X and y must be tensors on the HIP device")
+            X = X.to(device=dev, dtype=torch.float32).contiguous()
+            y = y.to(device=dev, dtype=torch.float32).contiguous()
+            g = np.ascontiguousarray(torch.as_tensor(part.groups).cpu().numpy().astype(np.int32))
+            if X.shape[0] != y.shape[0] or int(g.sum()) != X.shape[0] or (g.size and int(g.min()) <= 0):
+                raise ValueError(f"train_device: {X.shape[0]} rows, {y.shape[0]} labels, groups sum to {int(g.sum())}")
+            if g.size and int(g.max()) > MAX_DOCS_PER_QUERY:
+                raise ValueError(f"train_device: a query has {int(g.max())} documents; the device trainer takes at "
+                                 f"most {MAX_DOCS_PER_QUERY} per query")
+            return X, y, g
+
+        feature_cols = list(feature_cols if feature_cols is not None else getattr(train, "feature_names", None) or [])
+        X, y, g = pack(train)
+        if len(feature_cols) != X.shape[1]:
+            raise ValueError(f"train_device: {len(feature_cols)} feature names for {X.shape[1]} columns")
+        self.feature_names = feature_cols
+        Xv = yv = gv = None
+        if valid is not None:
+            Xv, yv, gv = pack(valid)
+            if Xv.shape[1] != X.shape[1]:
+                raise ValueError("train_device: train and valid differ in width")
+        return self._train_packed(X, y, g, Xv, yv, gv, feature_cols, seed,
+                                  40 if hist_dtype in ("float", "int40") else 20, bool(use_missing),
+                                  1 if split_order == "lightgbm" else 0)
+
+    def _train_packed(self, X, y, g, Xv, yv, gv, feature_cols, seed, hist_bits, use_missing, split_order):
+        lib = L.lib()
         prm = L.LambdamartParams()
         prm.num_leaves, prm.n_estimators, prm.learning_rate = self.num_leaves, self.n_estimators, self.learning_rate
         prm.min_child_samples, prm.max_bin, prm.truncation_level, prm.early_stopping_rounds = 20, 255, 30, 30
@@ -186,7 +232,7 @@ class LightGBMRanker:
         nk = len(self.eval_at)
         hist = np.full((self.n_estimators, 2, nk), np.nan, dtype=np.float64)
         text_p, best_it, rounds = C.c_void_p(), C.c_int(0), C.c_int(0)
-        logger.info("Training LambdaMART ranker: %d samples, %d features, %d queries", len(train_df), len(feature_cols), len(g))
+        logger.info("Training LambdaMART ranker: %d samples, %d features, %d queries", X.shape[0], len(feature_cols), len(g))
         L.check(lib.rihip_lambdamart_train(X.data_ptr(), y.data_ptr(), g.ctypes.data, X.shape[0], X.shape[1], len(g),
                                            None if Xv is None else Xv.data_ptr(), None if yv is None else yv.data_ptr(),
                                            None if gv is None else gv.ctypes.data, 0 if Xv is None else Xv.shape[0],
@@ -202,7 +248,7 @@ class LightGBMRanker:
         self._trained = True
         r = int(rounds.value)
         res: Dict = {"train": {f"ndcg@{k}": hist[:r, 0, t].tolist() for t, k in enumerate(self.eval_at)}}
-        if valid_df is not None:
+        if Xv is not None:
             res["valid"] = {f"ndcg@{k}": hist[:r, 1, t].tolist() for t, k in enumerate(self.eval_at)}
         logger.info("Training complete. Best iteration: %d", self.model.best_iteration)
         return res
