@@ -404,6 +404,22 @@ int rihip_rank_features_build(const double* user_tab, int64_t n_user_rows, const
 int rihip_rank_topk(const double* scores, const int64_t* cand, const float* retrieval_scores, int64_t nq, int kc, int k,
                     int64_t* out_ids, double* out_scores, float* out_retrieval_scores, void* stream);
 
+/* ---- seen-item exclusion ----------------------------------------------------------------------
+ * Not in the reference, which serves and evaluates every retrieved candidate whether the user has rated it or not
+ * (src/serving/recommender.py:269-387, src/pipelines/run_pipeline.py:166-220; SURVEY.md section 3.4, hazard ii).  Replaces the
+ * host-side `[i for i in ids if i not in seen][:k]` after FAISSIndex.batch_search with a device stage.
+ * scores f32 / ids i64 [nq, kc]: an over-fetched search result (item ids in descending score order, -1 / -inf only as a
+ * tail).  The excluded ids are a CSR: seen_offsets i64 [n_seen_rows + 1] into seen_items i32, row u = the ids of user
+ * u, ascending and unique.  Query q uses row user_ids[q] (device i64 [nq]; outside [0, n_seen_rows): nothing excluded);
+ * user_ids NULL: row q (n_seen_rows >= nq).  Output row out_slot[q] (device int [nq]; NULL: row q) of out_scores f32 /
+ * out_ids i64 [.., k] = the first k entries of the input row whose id is >= 0 and not in the list, in order, then
+ * -1 / -inf.  deficit (device int, nullable; added to, never reset here) counts queries that produced fewer than k
+ * entries although their input row had no -1 tail: kc was too small for them.  No host synchronisation, no allocation;
+ * capturable in a hipGraph; deterministic. */
+int rihip_exclude_topk(const float* scores, const int64_t* ids, int64_t nq, int kc, const int64_t* user_ids,
+                       const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items, int k,
+                       float* out_scores, int64_t* out_ids, const int* out_slot, int* deficit, void* stream);
+
 /* ---- evaluation report ------------------------------------------------------------------------
  * Replaces the per-user loop of evaluate_model (src/evaluation/metrics.py:301-384) and the component functions it
  * calls: ndcg_at_k (:20-69, binary relevance), recall_at_k (:72-87), precision_at_k (:90-99), mrr (:104-118),

@@ -23,9 +23,11 @@ from .recommender import GpuRecommendationPipeline
 
 def run_evaluate(pipe: GpuRecommendationPipeline, ratings_df, movies_df=None, n_eval_users: Optional[int] = 200,
                  top_k: int = 20, batch_size: int = 256, k_values: Optional[List[int]] = None, on_device: bool = False,
-                 item_genre_vectors: Optional[Dict[int, Any]] = None) -> Dict[str, Any]:
+                 item_genre_vectors: Optional[Dict[int, Any]] = None, exclude_train: bool = False) -> Dict[str, Any]:
     """on_device=True: the top-k ids stay on the device and eval_device scores them (same report).
-    item_genre_vectors: the reference's optional diversity input (evaluate_model's avg_diversity)."""
+    item_genre_vectors: the reference's optional diversity input (evaluate_model's avg_diversity).
+    exclude_train=True (not in the reference: SURVEY.md §3.4 hazard ii): the standard protocol that never recommends
+    a training item -- every rating outside the test split is excluded from its user's retrieval."""
     ratings = ratings_df.sort_values("timestamp")
     n_test = max(1, int(len(ratings) * 0.1 / ratings["user_id"].nunique()))
     test = ratings.groupby("user_id").tail(n_test)
@@ -36,9 +38,22 @@ def run_evaluate(pipe: GpuRecommendationPipeline, ratings_df, movies_df=None, n_
     truth = {int(u): g[g["rating"] >= 4]["item_id"].tolist() for u, g in sub.groupby("user_id")}
     users = [int(u) for u in eval_users if truth.get(int(u))]
     catalog = int(movies_df["item_id"].nunique()) if movies_df is not None else None
+    if exclude_train:
+        from .seen import SeenItems
+        attached = pipe.seen
+        pipe.set_seen(SeenItems.from_frame(ratings.drop(test.index)))
+        try:
+            return _evaluate(pipe, users, truth, catalog, top_k, batch_size, k_values, on_device, item_genre_vectors, True)
+        finally:
+            pipe.set_seen(attached)
+    return _evaluate(pipe, users, truth, catalog, top_k, batch_size, k_values, on_device, item_genre_vectors, False)
+
+
+def _evaluate(pipe, users, truth, catalog, top_k, batch_size, k_values, on_device, item_genre_vectors, exclude):
     if on_device:
         from .eval_device import GroundTruth, evaluate_topk_device, vectors_from_dict
-        parts = [pipe.recommend_batch(users[s:s + batch_size], k=top_k)[0] for s in range(0, len(users), batch_size)]
+        parts = [pipe.recommend_batch(users[s:s + batch_size], k=top_k, exclude_seen=exclude)[0]
+                 for s in range(0, len(users), batch_size)]
         if not parts:
             res = evaluate_model({}, truth, k_values or [5, 10, 20])
         else:
@@ -53,7 +68,7 @@ def run_evaluate(pipe: GpuRecommendationPipeline, ratings_df, movies_df=None, n_
         recs: Dict[int, List[int]] = {}
         for s in range(0, len(users), batch_size):
             chunk = users[s:s + batch_size]
-            ids, _, _ = pipe.recommend_batch(chunk, k=top_k)
+            ids, _, _ = pipe.recommend_batch(chunk, k=top_k, exclude_seen=exclude)
             ids = ids.cpu().numpy()
             for u, row in zip(chunk, ids):
                 recs[u] = [int(x) for x in row if x >= 0]

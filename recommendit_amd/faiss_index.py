@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import math
 import pickle
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
@@ -74,6 +75,8 @@ class FAISSIndex:
         self.item_ids: Optional[np.ndarray] = None
         self._item_id_to_faiss_idx: Dict[int, int] = {}
         self._item_ids_dev: Optional[torch.Tensor] = None
+        self._deferred = False
+        self._deficit: Optional[torch.Tensor] = None
 
     # -- build (faiss_index.py:45-82) ---------------------------------------------------------
     def build_ivf_index(self, embeddings: np.ndarray, item_ids: List[int], kmeans_iters: int = 20,
@@ -174,6 +177,7 @@ class FAISSIndex:
         """Serving chains (not in the reference): a thresholded IVF search then returns without its host
         synchronisation; call `finish_search()` after enqueueing the consumers of the result."""
         L.check(L.lib().rihip_ip_index_set_deferred_check(self.index._h, 1 if enable else 0), "ip_index_set_deferred_check")
+        self._deferred = bool(enable)
 
     def finish_search(self) -> int:
         """-> number of queries of the last deferred search that had to be re-done exactly (their output rows were
@@ -191,7 +195,66 @@ class FAISSIndex:
         L.check(L.lib().rihip_ip_index_last_fail_count(self.index._h, C.byref(n), L.stream_ptr()), "ip_index_last_fail_count")
         return int(n.value)
 
-    def search(self, query_vector: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+    # -- seen-item exclusion (not in the reference: SURVEY.md §3.4 hazard ii; seen.py, csrc/exclude.hip) ---------
+    def filter_excluded(self, scores: torch.Tensor, ids: torch.Tensor, k: int, seen, user_ids: Optional[torch.Tensor],
+                        out_scores: torch.Tensor, out_ids: torch.Tensor, out_slot: Optional[torch.Tensor] = None) -> None:
+        """rows of an over-fetched result [nq, k_eff] -> their first k allowed entries, written to row out_slot[q]
+        (int32 device tensor; None: row q) of out_scores / out_ids [.., k]; user_ids None: list q of `seen` belongs to
+        query q.  A result that already holds the whole corpus cannot have been fetched short: not counted."""
+        if self._deficit is None:
+            self._deficit = torch.zeros(1, dtype=torch.int32, device=scores.device)
+        nq, kc = ids.shape
+        whole = kc >= self.index.ntotal
+        L.check(L.lib().rihip_exclude_topk(scores.data_ptr(), ids.data_ptr(), nq, kc, L.ptr(user_ids),
+                                           seen.offsets.data_ptr(), seen.n_users, seen.items.data_ptr(), k,
+                                           out_scores.data_ptr(), out_ids.data_ptr(), L.ptr(out_slot),
+                                           None if whole else self._deficit.data_ptr(), L.stream_ptr()), "exclude_topk")
+
+    def exclusion_deficit(self) -> int:
+        """queries so far whose over-fetch was too small to fill k allowed entries (one synchronisation); 0 whenever
+        the plan of seen.py chose k_eff"""
+        return 0 if self._deficit is None else int(self._deficit.item())
+
+    def _search_excluding(self, q: torch.Tensor, k: int, seen, user_ids) -> Tuple[torch.Tensor, torch.Tensor]:
+        """q normalised f32 [nq,d] on device -> (scores, item ids) [nq,k] without each query's excluded items.
+        user_ids: host sequence (queries are grouped by how far they have to over-fetch, one search per group), a
+        device tensor (one group at the store's longest list) or None (list q of `seen` belongs to query q)."""
+        from .seen import overfetch_k, plan_overfetch
+        nq, ntotal = q.shape[0], self.index.ntotal
+        k_max = int(L.lib().rihip_ip_index_max_k())
+        if isinstance(user_ids, torch.Tensor) and user_ids.is_cuda:
+            uid = user_ids.to(dtype=torch.long).contiguous()
+            plan = [(overfetch_k(k, seen.max_count, ntotal, k_max), None)]
+            nothing = seen.max_count == 0
+        else:
+            host = np.arange(nq) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
+            if host.shape[0] != nq:
+                raise ValueError(f"{host.shape[0]} user ids for {nq} queries")
+            # a deferred exactness check belongs to ONE search of the handle: no groups under it
+            extra = seen.counts_of(host)
+            plan = plan_overfetch(extra, k, ntotal, k_max, math.inf if self._deferred else None)
+            uid = None if user_ids is None else torch.from_numpy(host).to(q.device)
+            nothing = not extra.any()
+        if len(plan) == 1:
+            k_eff = plan[0][0]
+            s, c = self._search_device(q, k_eff, item_ids=True)
+            if nothing:
+                return s, c
+            scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            self.filter_excluded(s, c, k, seen, uid, scores, ids)
+            return scores, ids
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        for k_eff, pos in plan:
+            slot = torch.from_numpy(pos.astype(np.int32)).to(q.device)
+            sel = slot.to(torch.long)
+            s, c = self._search_device(q[sel].contiguous(), k_eff, item_ids=True)
+            self.filter_excluded(s, c, k, seen, sel if uid is None else uid[sel], scores, ids, slot)
+        return scores, ids
+
+    def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None) -> Tuple[np.ndarray, np.ndarray]:
+        """exclude_items (not in the reference): item ids that must not be returned"""
         if self.index is None:
             raise RuntimeError("Index not built. Call build_ivf_index() first.")
         query = np.atleast_2d(query_vector).astype(np.float32)
@@ -199,6 +262,13 @@ class FAISSIndex:
         query = query / np.maximum(norm, 1e-8)
         k = min(k, self.index.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(query[:1])).to(L.device())
+        if exclude_items is not None:
+            from .seen import SeenItems
+            ex = np.asarray(exclude_items, dtype=np.int64).reshape(-1)
+            scores, ids = self._search_excluding(q_dev, k, SeenItems.from_pairs(np.zeros(ex.shape[0], np.int64), ex, 1),
+                                                 None)
+            distances, ids = scores[0].cpu().numpy(), ids[0].cpu().numpy()
+            return distances[ids >= 0], ids[ids >= 0]
         scores, rows = self._search_device(q_dev, k)
         distances = scores[0].cpu().numpy()
         faiss_indices = rows[0].cpu().numpy()
@@ -207,7 +277,9 @@ class FAISSIndex:
         faiss_indices = faiss_indices[valid_mask]
         return distances, self.item_ids[faiss_indices]
 
-    def batch_search(self, query_vectors: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500, exclude=None, user_ids=None
+                     ) -> Tuple[np.ndarray, np.ndarray]:
+        """exclude / user_ids (not in the reference): as in batch_search_device"""
         if self.index is None:
             raise RuntimeError("Index not built.")
         queries = query_vectors.astype(np.float32)
@@ -215,19 +287,38 @@ class FAISSIndex:
         queries = queries / np.maximum(norms, 1e-8)
         k = min(k, self.index.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
-        scores, rows = self._search_device(q_dev, k, item_ids=True)
+        if exclude is not None:
+            scores, rows = self._search_excluding(q_dev, k, exclude, self._require_user_ids(user_ids))
+        else:
+            scores, rows = self._search_device(q_dev, k, item_ids=True)
         return scores.cpu().numpy(), rows.cpu().numpy()
 
-    def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False
-                            ) -> Tuple[torch.Tensor, torch.Tensor]:
+    @staticmethod
+    def _require_user_ids(user_ids):
+        if user_ids is None:
+            raise ValueError("exclude needs user_ids: the row of the seen store every query reads")
+        return user_ids
+
+    def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, exclude=None,
+                            user_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-resident batch_search (not in the reference): queries f32 [nq,d] on the HIP device;
-        returns (scores, item_ids) on device, -1 padded.  This is the QPS benchmark entry."""
+        returns (scores, item_ids) on device, -1 padded.  This is the QPS benchmark entry.
+
+        exclude (a seen.SeenItems) with user_ids [nq]: query q never returns an item of row user_ids[q] of the store;
+        the result is the top k of the corpus (IVF: of the probed lists) minus that row, -1 padded when fewer remain.
+        user_ids as a host sequence: the batch is searched in groups by how far each query has to over-fetch
+        (seen.plan_overfetch); as a device tensor: one search at the store's longest list.  ValueError when k plus a
+        user's list exceeds the 16384-candidate limit of the search on a corpus larger than that.
+        Under set_deferred_check(True) the filtered result is a consumer of the search like any other: when
+        finish_search() returns > 0, call this again (it then runs as one group: one search, one finish)."""
         if self.index is None:
             raise RuntimeError("Index not built.")
         q = queries.to(dtype=torch.float32).contiguous()
         if not normalized:
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
         k = min(k, self.index.ntotal)
+        if exclude is not None:
+            return self._search_excluding(q, k, exclude, self._require_user_ids(user_ids))
         return self._search_device(q, k, item_ids=True)
 
     # -- persistence (faiss_index.py:159-205) -------------------------------------------------

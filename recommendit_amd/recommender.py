@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from .faiss_index import FAISSIndex
 from .ranker import LightGBMRanker
+from .seen import SeenItems, overfetch_k, plan_overfetch
 from .two_tower import N_GENRES, TwoTowerModel
 
 USER_SCALARS = [("avg_rating", 3.5), ("log_rating_count", 0.0), ("recency_score", 0.5), ("gender_encoded", 0.0),
@@ -165,23 +166,73 @@ def build_ranking_features_device(store: GpuFeatureStore, user_ids: torch.Tensor
 
 class GpuRecommendationPipeline:
     def __init__(self, model: TwoTowerModel, index: FAISSIndex, ranker: LightGBMRanker, store: GpuFeatureStore,
-                 top_k_candidates: int = 500, top_k_results: int = 20, feature_log_rows: int = 0):
+                 top_k_candidates: int = 500, top_k_results: int = 20, feature_log_rows: int = 0,
+                 seen: Optional[SeenItems] = None):
         """defaults = settings.TOP_K_CANDIDATES / TOP_K_RESULTS (src/config.py:11-12).
+
+        seen (not in the reference, which recommends what the user has already rated: SURVEY.md §3.4 hazard ii): a
+        store of excluded item ids per user id; with one attached, retrieval over-fetches and a device filter drops
+        each user's items, so features, the feature log, the ranker and the top-k still see top_k_candidates columns.
 
         feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
         device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
         serving_features(), detect_skew(), reset_feature_log().  0 leaves the chain as it is."""
         self.model, self.index, self.ranker, self.store = model, index, ranker, store
         self.top_k_candidates, self.top_k_results = top_k_candidates, top_k_results
-        self._graphs: Dict[Tuple[int, int], Any] = {}
+        self._graphs: Dict[Tuple[int, int, Optional[int]], Any] = {}
+        self.seen = seen
         self._pin: Dict[int, Any] = {}
         self._defer = os.environ.get("RIHIP_SERVE_DEFER", "1") != "0"   # 0: exactness check inside the search (experiments)
         self._log: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None
         self.reset_feature_log(feature_log_rows)
 
+    def set_seen(self, seen: Optional[SeenItems]) -> None:
+        """attach / replace / detach (None) the store of excluded items; captured graphs are re-captured"""
+        self.seen = seen
+
+    def exclusion_deficit(self) -> int:
+        """requests so far whose over-fetch could not fill top_k_candidates allowed candidates (one synchronisation);
+        0 whenever the over-fetch was planned from the attached store"""
+        return self.index.exclusion_deficit()
+
     @torch.no_grad()
-    def recommend_batch(self, user_ids, k: Optional[int] = None, graph: bool = False
-                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def recommend_batch(self, user_ids, k: Optional[int] = None, graph: bool = False,
+                        exclude_seen: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """recommendations of a batch of users (outputs: _recommend).  exclude_seen: drop each user's items of the
+        attached seen store from retrieval; None = yes iff a store is attached.  With host ids the batch is served in
+        groups by how far each user has to over-fetch (seen.plan_overfetch: one heavy user does not slow the rest), one
+        run of the chain per group; graph=True and device ids run as one group at the store's longest list."""
+        k = k or self.top_k_results
+        if exclude_seen and self.seen is None:
+            raise ValueError("exclude_seen=True without a seen store (set_seen)")
+        if self.seen is None or exclude_seen is False:
+            return self._recommend(user_ids, k, graph, None)
+        ntotal = self.index.index.ntotal
+        kc = min(self.top_k_candidates, ntotal)
+        k_max = int(L.lib().rihip_ip_index_max_k())
+        if graph or (isinstance(user_ids, torch.Tensor) and user_ids.is_cuda):
+            return self._recommend(user_ids, k, graph, overfetch_k(kc, self.seen.max_count, ntotal, k_max)
+                                   if self.seen.max_count else None)
+        host = np.asarray(user_ids.tolist() if isinstance(user_ids, torch.Tensor) else user_ids, dtype=np.int64)
+        extra = self.seen.counts_of(host)
+        if not extra.any():
+            return self._recommend(user_ids, k, False, None)
+        plan = plan_overfetch(extra, kc, ntotal, k_max)
+        if len(plan) == 1:
+            return self._recommend(user_ids, k, False, plan[0][0])
+        outs = None
+        for k_eff, pos in plan:
+            part = self._recommend(host[pos].tolist(), k, False, k_eff if extra[pos].any() else None)
+            if outs is None:
+                outs = tuple(torch.empty((host.shape[0],) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device)
+                             for p in part)
+            sel = torch.from_numpy(pos).to(part[0].device)
+            for o, p in zip(outs, part):
+                o.index_copy_(0, sel, p)
+        return outs
+
+    def _recommend(self, user_ids, k: int, graph: bool, k_eff: Optional[int]
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """-> (item_ids i64 [nq,k], ranker scores f64 [nq,k], retrieval scores f32 [nq,k]) on device; -1 padded
         where retrieval returned fewer than k candidates.  Ties in the ranker score keep retrieval order
         (DataFrame.nlargest(keep='first'), recommender.py:346).
@@ -189,26 +240,29 @@ class GpuRecommendationPipeline:
         graph=True (small request batches): the ~20 launches of the chain are captured once per (batch size, k) into a
         hipGraph and replayed -- a single request is launch-bound otherwise.  The returned tensors are the graph's static
         outputs: valid until the next replay of the same shape.  Falls back to the eager chain when the shape takes a
-        path with a host synchronisation inside the chain."""
-        k = k or self.top_k_results
+        path with a host synchronisation inside the chain.
+
+        k_eff: None = retrieval as it is; else retrieval fetches k_eff candidates and the seen filter keeps the
+        first top_k_candidates allowed ones (a consumer of the search like the stages behind it: it runs again with
+        the chain after an exactness re-do)."""
         # The retrieval stage's exactness check is deferred to the END of the chain (FAISSIndex.set_deferred_check): the
         # thresholded IVF pass of a large batch used to stop for a host round trip in the middle of the chain (a 54 us
         # hole at 256 requests, and the reason such batches could not be captured as a hipGraph).  In the rare case that
         # queries had to be re-done exactly, the chain runs again on the corrected candidates (not deferred).
         if not self._defer:
-            out = self._replay(user_ids, k) if graph else None
+            out = self._replay(user_ids, k, k_eff) if graph else None
             if out is not None:
                 return out[0]
-            return self._chain(self._ids_to_device(user_ids), k)
+            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff)
         self.index.set_deferred_check(True)
         try:
-            out = self._replay(user_ids, k) if graph else None
+            out = self._replay(user_ids, k, k_eff) if graph else None
             uid = None
             if out is not None:
                 out, redone = out
             else:
                 uid = self._ids_to_device(user_ids)
-                out = self._chain(uid, k)
+                out = self._chain(uid, k, k_eff=k_eff)
                 redone = self.index.finish_search()
         finally:
             self.index.set_deferred_check(False)
@@ -217,7 +271,7 @@ class GpuRecommendationPipeline:
                 uid = self._ids_to_device(user_ids)
             if self._log is not None:       # the batch is logged again with its final candidates: drop the first rows
                 L.check(L.lib().rihip_feature_log_rewind(self._log[3].data_ptr(), L.stream_ptr()), "feature_log_rewind")
-            out = self._chain(uid, k)
+            out = self._chain(uid, k, k_eff=k_eff)
         return out
 
     def _ids_to_device(self, user_ids) -> torch.Tensor:
@@ -247,11 +301,13 @@ class GpuRecommendationPipeline:
         ut, it = self.store.device_tables()
         return (int(L.lib().rihip_scratch_generation()), ut.data_ptr(), it.data_ptr(), id(self.index), id(self.ranker),
                 id(self.model), self.top_k_candidates, tuple(self.ranker.feature_names),
-                None if self._log is None else (self._log[0].data_ptr(), self._log[0].shape[0]))
+                None if self._log is None else (self._log[0].data_ptr(), self._log[0].shape[0]),
+                None if self.seen is None else (self.seen.offsets.data_ptr(), self.seen.items.data_ptr(),
+                                                self.seen.n_users))
 
-    def _replay(self, user_ids, k: int):
+    def _replay(self, user_ids, k: int, k_eff: Optional[int] = None):
         nq = len(user_ids)
-        key = (nq, k)
+        key = (nq, k, k_eff)
         ent = self._graphs.get(key)
         if ent is not None and ent is not False and ent[3] != self._graph_state():
             # an eager call (or a capture of a larger shape) grew a scratch buffer, nprobe changed, the feature tables
@@ -267,13 +323,13 @@ class GpuRecommendationPipeline:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):      # warm-up: scratch buffers, LDS grants, lazy module loads
                     for _ in range(2):
-                        self._chain(su, k, log=False)
+                        self._chain(su, k, log=False, k_eff=k_eff)
                         self.index.finish_search()
                 cur.wait_stream(side)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    out = self._chain(su, k)
+                    out = self._chain(su, k, k_eff=k_eff)
                 deferred = self.index.search_pending()      # the captured search left its exactness check to the caller
                 self.index.set_deferred_check(True)         # (capture ran nothing: drop the pending state)
                 ent = (g, su, out, self._graph_state(), deferred)   # state recorded AFTER capture: the warm-up may have grown scratch
@@ -289,12 +345,19 @@ class GpuRecommendationPipeline:
         # a replay runs no host code: the failure count of its deferred search is read here (one synchronisation)
         return out, (self.index.last_fail_count() if deferred else 0)
 
-    def _chain(self, uid: torch.Tensor, k: int, log: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
-        rs, cand = self.index.batch_search_device(q, k=self.top_k_candidates, normalized=True)
+        rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True)
         nq, kc = cand.shape
+        if k_eff is not None:       # over-fetched: keep each user's first top_k_candidates unseen candidates
+            kc = min(self.top_k_candidates, self.index.index.ntotal)
+            fs = torch.empty((nq, kc), dtype=torch.float32, device=cand.device)
+            fc = torch.empty((nq, kc), dtype=torch.int64, device=cand.device)
+            self.index.filter_excluded(rs, cand, kc, self.seen, uid, fs, fc)
+            rs, cand = fs, fc
         X = build_ranking_features_device(self.store, uid, cand, self.ranker.feature_names)
         if log and self._log is not None:
             self._append_log(X, uid, cand)
@@ -377,8 +440,9 @@ class GpuRecommendationPipeline:
         serving = [S._Segment(ring, list(self.ranker.feature_names), ri), S._Segment(ids, ["user_id", "item_id"], ri)]
         return S.detect_training_serving_skew_device(train_features, serving, threshold, numeric_cols, columns)
 
-    def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False) -> List[Dict[str, Any]]:
-        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph)
+    def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False,
+                            exclude_seen: Optional[bool] = None) -> List[Dict[str, Any]]:
+        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen)
         out = []
         for rank, (i, s, r) in enumerate(zip(ids[0].tolist(), sc[0].tolist(), rs[0].tolist()), start=1):
             if i >= 0:

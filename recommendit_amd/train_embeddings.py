@@ -246,12 +246,13 @@ def retrieval_ndcg(model: TwoTowerModel, ratings_df: pd.DataFrame, movies_df: pd
 def evaluate_retrieval_all_users(model: TwoTowerModel, index, test_pairs, k_candidates: int = 500, top: int = 20,
                                  batch: int = 65536, k_values=(5, 10, 20), catalog_size: Optional[int] = None,
                                  item_vectors: Optional[torch.Tensor] = None,
-                                 item_present: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+                                 item_present: Optional[torch.Tensor] = None, exclude=None) -> Dict[str, Any]:
     """Whole-population retrieval evaluation (not in the reference, which scores 200 users): every user of
     ``test_pairs`` (a frame with user_id / item_id columns, or a (users, items) pair of arrays: the relevant items)
     is retrieved in batches of ``batch`` users (top ``k_candidates`` by inner product, the first ``top`` kept) into
     one device tensor, which eval_device scores; only the report comes back to the host.  Users in order of first
-    appearance in ``test_pairs``."""
+    appearance in ``test_pairs``.  exclude (a seen.SeenItems, e.g. of the training pairs): no user is recommended an
+    item of its own row; every batch is searched in groups planned from the host ids (seen.plan_overfetch)."""
     from .eval_device import GroundTruth, evaluate_topk_device
     if isinstance(test_pairs, tuple):
         pu, pi = (np.asarray(x, dtype=np.int64) for x in test_pairs)
@@ -268,7 +269,8 @@ def evaluate_retrieval_all_users(model: TwoTowerModel, index, test_pairs, k_cand
     uid = torch.from_numpy(users).to(dev)
     for s in range(0, users.shape[0], batch):
         U = model.get_user_embeddings(uid[s:s + batch], as_tensor=True)
-        _, ids = index.batch_search_device(U, k=k_candidates)
+        _, ids = index.batch_search_device(U, k=k_candidates, exclude=exclude,
+                                           user_ids=None if exclude is None else users[s:s + batch])
         recs[s:s + ids.shape[0], :min(top, ids.shape[1])] = ids[:, :top]
     n_id = int(np.max(index.item_ids)) + 1 if catalog_size else None
     return evaluate_topk_device(recs, truth, list(k_values), catalog_size=catalog_size, item_vectors=item_vectors,
