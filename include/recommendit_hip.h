@@ -251,7 +251,10 @@ int rihip_clip_coef_step(const double* part, int64_t n_part, float max_norm, flo
  * group (id,sample) pairs by id (radix sort), sum each row's contributions in sorted order
  * (bitwise reproducible), then Adam on touched rows only.  workspace bytes from
  * rihip_rows_workspace_bytes(B, d); uniq int64[B]; Gc float[B,d]; part double[rihip_rows_nparts()].
- * n_rows: number of table rows (ids < n_rows) -- only the significant key bits are sorted; 0 = unknown (all 63). */
+ * n_rows: number of table rows (ids < n_rows) -- only the significant key bits are sorted; 0 = unknown (all 63).
+ * An id that is negative, or >= n_rows when n_rows is given, counts as the padding row 0: its gradient is dropped.
+ * uniq[0 .. n_unique) is strictly ascending; row 0, when present, comes first with Gc = 0.  With n_rows = 0 the caller
+ * vouches that every non-negative id is a row of the table rihip_adam_rows is given. */
 int64_t rihip_rows_workspace_bytes(int64_t B, int d);
 int rihip_rows_nparts(void);
 int rihip_rows_group(const int64_t* ids, int64_t B, int d, int64_t n_rows, int64_t* uniq, void* workspace,

@@ -146,17 +146,26 @@ __global__ __launch_bounds__(256) void adam_dense_kernel(float* __restrict__ p, 
 }
 
 // ---------------------------------- row-sparse path ---------------------------------------
-__global__ void iota_kernel(int* v, int64_t n) {
+// sort values 0..n-1 and the keys that are sorted: an id outside the table (negative, or >= n_rows when n_rows is
+// known) becomes the padding row 0 BEFORE the sort, so that the sorted keys hold every row in one run even when only
+// the low key bits are sorted (a stray id whose low bits equal a valid row's would otherwise land inside that row's
+// run and split it)
+__global__ void iota_keys_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t n_rows, int* v, int64_t* keys) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = (int)i;
+  if (i < n) {
+    v[i] = (int)i;
+    const int64_t id = ids[i];
+    keys[i] = (id >= 0 && (n_rows <= 0 || id < n_rows)) ? id : 0;
+  }
 }
 __global__ void head_flags_kernel(const int64_t* __restrict__ sorted, int64_t n, int* flags) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) flags[i] = (i == 0 || sorted[i] != sorted[i - 1]) ? 1 : 0;
 }
 // seg[i] = inclusive scan of head flags (1-based segment number); write segment starts + unique ids
-// an id outside [0, n_rows) (already flagged by the tower forward's err word) becomes the padding row 0: its gradient is
-// dropped and the row-sparse Adam never touches memory outside the table
+// an id outside [0, n_rows) (already flagged by the tower forward's err word) became the padding row 0 before the sort
+// (iota_keys_kernel): its gradient is dropped; the clamp here only keeps the row-sparse Adam inside the table whatever
+// the keys hold
 __global__ void seg_starts_kernel(const int64_t* __restrict__ sorted, const int* __restrict__ seg, int64_t n,
                                   int64_t n_rows, int* seg_start, int64_t* uniq, int* n_unique) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -530,13 +539,13 @@ extern "C" int rihip_adam_hyper_step(int64_t* step_dev, const float* lr_dev, flo
 
 // ---- row-sparse path ------------------------------------------------------------------------
 // workspace layout (bytes), all 256-B aligned:
-//   keys_out int64[B] | vals_in int32[B] | perm int32[B] | flags int32[B] | seg int32[B] |
-//   seg_start int32[B+1] | n_unique int32 | rocprim temp | P float[B,d] (block partials)
+//   keys_out int64[B] | keys_in int64[B] (ids with strays mapped to row 0) | vals_in int32[B] | perm int32[B] |
+//   flags int32[B] | seg int32[B] | seg_start int32[B+1] | n_unique int32 | rocprim temp | P float[B,d] (block partials)
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RowsWs {
-  int64_t* keys_out; int* vals_in; int* perm; int* flags; int* seg; int* seg_start; int* n_unique; void* temp;
-  float* P; size_t temp_bytes; size_t total;
+  int64_t* keys_out; int64_t* keys_in; int* vals_in; int* perm; int* flags; int* seg; int* seg_start; int* n_unique;
+  void* temp; float* P; size_t temp_bytes; size_t total;
 };
 
 static int rows_ws_layout(int64_t B, int d, void* base, RowsWs* ws) {
@@ -549,6 +558,7 @@ static int rows_ws_layout(int64_t B, int d, void* base, RowsWs* ws) {
   size_t off = 0;
   char* b = (char*)base;
   ws->keys_out = (int64_t*)(b + off); off += align256(sizeof(int64_t) * B);
+  ws->keys_in = (int64_t*)(b + off); off += align256(sizeof(int64_t) * B);
   ws->vals_in = (int*)(b + off); off += align256(sizeof(int) * B);
   ws->perm = (int*)(b + off); off += align256(sizeof(int) * B);
   ws->flags = (int*)(b + off); off += align256(sizeof(int) * B);
@@ -569,7 +579,7 @@ extern "C" int64_t rihip_rows_workspace_bytes(int64_t B, int d) {
   return (int64_t)ws.total;
 }
 
-// Groups the B (id, sample) pairs by id.  Outputs (device): uniq[<=B] unique ids ascending,
+// Groups the B (id, sample) pairs by id.  Outputs (device): uniq[<=B] unique ids ascending (strays as one row 0),
 // and inside the workspace perm / seg_start / n_unique used by rihip_rows_reduce / rihip_adam_rows.
 extern "C" int rihip_rows_group(const int64_t* ids, int64_t B, int d, int64_t n_rows, int64_t* uniq, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
@@ -580,15 +590,15 @@ extern "C" int rihip_rows_group(const int64_t* ids, int64_t B, int d, int64_t n_
                 ws.total, (long long)workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = (unsigned)((B + 255) / 256);
-  hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, st, ws.vals_in, B);
+  hipLaunchKernelGGL(iota_keys_kernel, dim3(nb), dim3(256), 0, st, ids, B, n_rows, ws.vals_in, ws.keys_in);
   RIHIP_CHECK_LAUNCH();
   size_t tb = ws.temp_bytes;
-  unsigned end_bit = 64;  // ids are non-negative row numbers < n_rows: sort only the bits that can differ
+  unsigned end_bit = 64;  // keys_in holds non-negative row numbers < n_rows: sort only the bits that can differ
   if (n_rows > 0) {
     end_bit = 1;
     while (end_bit < 63 && (1ll << end_bit) < n_rows) ++end_bit;
   }
-  RIHIP_CHECK_HIP(rocprim::radix_sort_pairs(ws.temp, tb, ids, ws.keys_out, ws.vals_in, ws.perm, (size_t)B, 0, end_bit, st));
+  RIHIP_CHECK_HIP(rocprim::radix_sort_pairs(ws.temp, tb, ws.keys_in, ws.keys_out, ws.vals_in, ws.perm, (size_t)B, 0, end_bit, st));
   hipLaunchKernelGGL(head_flags_kernel, dim3(nb), dim3(256), 0, st, ws.keys_out, B, ws.flags);
   RIHIP_CHECK_LAUNCH();
   tb = ws.temp_bytes;

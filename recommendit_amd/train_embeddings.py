@@ -119,11 +119,13 @@ class UserItemDataset:
             if 0 <= iid < self.M:
                 gm[iid] = vec
         self.d_genres = torch.from_numpy(gm).to(dev)
+        self.d_gave_up = torch.zeros(1, dtype=torch.int32, device=dev)   # samples whose attempts ran out (never read per call)
         self._dev_ready = True
 
     def sample_negatives(self, users: torch.Tensor, gen: torch.Generator, max_attempts: int = 1000) -> torch.Tensor:
         """One HIP launch for the whole batch (rihip_sample_negatives): uniform catalogue draws, re-drawn while the
-        item is in the user's rated set -- the reference's rejection loop (:58-63), bounded at `max_attempts`."""
+        item is in the user's rated set -- the reference's rejection loop (:58-63), bounded at `max_attempts`.  A sample
+        that exhausts them keeps its last draw, a RATED item, and is counted on the device (negatives_given_up)."""
         self._prepare_device()
         u = users.contiguous()
         neg = torch.empty_like(u)
@@ -131,9 +133,19 @@ class UserItemDataset:
         seed = (gen.initial_seed() * 0x9E3779B97F4A7C15 + self._neg_calls) & ((1 << 63) - 1)
         L.check(L.lib().rihip_sample_negatives(u.data_ptr(), u.numel(), self.d_catalog.data_ptr(),
                                                self.d_catalog.numel(), self.d_rated.data_ptr(), self.d_rated.numel(),
-                                               self.M, seed, max_attempts, neg.data_ptr(), None, L.stream_ptr()),
+                                               self.M, seed, max_attempts, neg.data_ptr(), self.d_gave_up.data_ptr(),
+                                               L.stream_ptr()),
                 "sample_negatives")
         return neg
+
+    def negatives_given_up(self, reset: bool = False) -> int:
+        """Samples since the last reset whose negative is a rated item because max_attempts ran out (one device read)."""
+        if not self._dev_ready:
+            return 0
+        n = int(self.d_gave_up.item())
+        if reset:
+            self.d_gave_up.zero_()
+        return n
 
     def epoch_batches(self, batch_size: int, gen: torch.Generator, with_negatives: bool = True
                       ) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
@@ -150,6 +162,11 @@ class UserItemDataset:
             else:
                 items = p
             yield u, items, self.d_genres[items]
+        if with_negatives:
+            n_bad = self.negatives_given_up(reset=True)      # the epoch's only read of the counter
+            if n_bad:
+                logger.warning("negative sampler: %d samples of this epoch exhausted their attempts and kept a RATED "
+                               "item as the negative (a user rated almost the whole catalogue)", n_bad)
 
 
 class EmbeddingTrainer:
