@@ -375,6 +375,24 @@ int rihip_map_rows_to_ids(int64_t* rows, int64_t n, const int64_t* item_ids, voi
  * >= ntotal item ids, out_rows receives item_ids[row] (-1 padding unchanged).  The array is not copied and must stay
  * valid while searches run; NULL restores row numbers. */
 int rihip_ip_index_set_id_map(void* handle, const int64_t* item_ids_dev);
+/* Add / remove / replace items of a built index without retraining (faiss add_with_ids / remove_ids): ONE repack of the
+ * corpus on the device under the existing centroids.  item_ids: device [N], the id of every stored row; drop_ids: device
+ * [n_drop], any order, ids that are not stored are ignored; X_add: device [n_add,d] normalised rows, appended in call order
+ * as rows N_keep .. N_keep+n_add-1 with the ids add_ids (device [n_add]); surviving rows keep their relative order and are
+ * renumbered densely.  item_ids_out: device [N + n_add], receives the id of every row of the result (first *n_total
+ * entries).  Host outputs: *n_total rows of the result, *n_dropped stored rows removed.  The handle is left bit for bit in
+ * the state rihip_ip_index_set_vectors + rihip_ip_index_set_ivf of the final corpus (same centroids, kept rows in their
+ * lists, new rows in their arg-max list) would leave it in; centroids are not retrained.  Refused with RIHIP_ERR_ARG and
+ * *bad_kind = 1: an id is repeated inside drop_ids or add_ids, 2: an id to add is stored and not dropped by this call
+ * (*bad_id names one such id), 3: the result would be empty; RIHIP_ERR_STATE while a deferred search is pending.  A
+ * refused or failed call leaves the index as it was.  A call that drops and adds nothing changes nothing.  Synchronises the
+ * stream.  Peak device memory: the old plus the new corpus.  Captured serve graphs are stale afterwards
+ * (rihip_scratch_generation advances). */
+int rihip_ip_index_update(void* handle, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                          const float* X_add, const int64_t* add_ids, int64_t n_add, int64_t* item_ids_out,
+                          int64_t* n_total, int64_t* n_dropped, int64_t* bad_id, int* bad_kind, void* stream);
+/* real rows of every IVF list (host int64 [nlist]) */
+int rihip_ip_index_list_sizes(void* handle, int64_t* out);
 
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict

@@ -81,6 +81,17 @@ int pad_rows(const float* src, int64_t n, int du, int d, float* dst, hipStream_t
 int prepare_flat(IpIndex* h, hipStream_t st);
 // upload the per-list offsets/lengths the list-major scan reads (from the host copy list_len; ivf.hip)
 int derive_ivf_aux(IpIndex* h, hipStream_t st);
+// arg-max-IP list (lowest list id wins ties) of each of N device rows of width d under C [nlist,d] (ivf.hip)
+int launch_assign(int d, const float* X, int64_t N, const float* C, int nlist, int* assign, hipStream_t st);
+// (list,row) pairs sorted by list; rows ascending inside a list (the sort is stable); off: [nlist+1] list bounds (ivf.hip)
+struct Grouper {
+  int* keys = nullptr; int* rows_in = nullptr; int* rows = nullptr; int* off = nullptr; void* temp = nullptr;
+  size_t temp_bytes = 0;
+  int64_t N = 0; int nlist = 0; int end_bit = 1;
+  int init(int64_t N_, int nlist_, hipStream_t st);
+  int group(const int* assign, hipStream_t st);
+  void release();
+};
 
 }  // namespace rihip_index
 

@@ -172,6 +172,9 @@ __global__ void ivf_unpermute_kernel(const float* __restrict__ Xn, int d, const 
   reinterpret_cast<f32x4*>(X + (size_t)rid * d)[idx % d4] = reinterpret_cast<const f32x4*>(Xn + (size_t)p * d)[idx % d4];
 }
 
+}  // namespace
+
+namespace rihip_index {
 int launch_assign(int d, const float* X, int64_t N, const float* C, int nlist, int* assign, hipStream_t st) {
   const int64_t nblk = (N + 127) / 128;
   const dim3 mg((unsigned)(nblk < 2048 ? nblk : 2048));
@@ -183,34 +186,35 @@ int launch_assign(int d, const float* X, int64_t N, const float* C, int nlist, i
   return RIHIP_OK;
 }
 
-struct Grouper {  // (list,row) pairs sorted by list; rows ascending inside a list (the sort is stable)
-  int* keys = nullptr; int* rows_in = nullptr; int* rows = nullptr; int* off = nullptr; void* temp = nullptr;
-  size_t temp_bytes = 0;
-  int64_t N = 0; int nlist = 0; int end_bit = 1;
-  int init(int64_t N_, int nlist_, hipStream_t st) {
-    N = N_; nlist = nlist_;
-    end_bit = 1;
-    while ((1 << end_bit) < nlist) ++end_bit;
-    HIPCHK(hipMalloc((void**)&keys, sizeof(int) * N));
-    HIPCHK(hipMalloc((void**)&rows_in, sizeof(int) * N));
-    HIPCHK(hipMalloc((void**)&rows, sizeof(int) * N));
-    HIPCHK(hipMalloc((void**)&off, sizeof(int) * (nlist + 1)));
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, temp_bytes, (const int*)nullptr, (int*)nullptr, (const int*)nullptr,
-                                     (int*)nullptr, (size_t)N, 0, end_bit, st));
-    HIPCHK(hipMalloc(&temp, temp_bytes ? temp_bytes : 16));
-    hipLaunchKernelGGL(iota_int_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rows_in, N);
-    RIHIP_CHECK_LAUNCH();
-    return RIHIP_OK;
-  }
-  int group(const int* assign, hipStream_t st) {
-    size_t tb = temp_bytes;
-    HIPCHK(rocprim::radix_sort_pairs(temp, tb, assign, keys, (const int*)rows_in, rows, (size_t)N, 0, end_bit, st));
-    hipLaunchKernelGGL(list_bounds_kernel, dim3((unsigned)((nlist + 1 + 255) / 256)), dim3(256), 0, st, keys, N, nlist, off);
-    RIHIP_CHECK_LAUNCH();
-    return RIHIP_OK;
-  }
-  void release() { hipFree(keys); hipFree(rows_in); hipFree(rows); hipFree(off); hipFree(temp); keys = rows_in = rows = off = nullptr; temp = nullptr; }
-};
+int Grouper::init(int64_t N_, int nlist_, hipStream_t st) {
+  N = N_; nlist = nlist_;
+  end_bit = 1;
+  while ((1 << end_bit) < nlist) ++end_bit;
+  HIPCHK(hipMalloc((void**)&keys, sizeof(int) * N));
+  HIPCHK(hipMalloc((void**)&rows_in, sizeof(int) * N));
+  HIPCHK(hipMalloc((void**)&rows, sizeof(int) * N));
+  HIPCHK(hipMalloc((void**)&off, sizeof(int) * (nlist + 1)));
+  HIPCHK(rocprim::radix_sort_pairs(nullptr, temp_bytes, (const int*)nullptr, (int*)nullptr, (const int*)nullptr,
+                                   (int*)nullptr, (size_t)N, 0, end_bit, st));
+  HIPCHK(hipMalloc(&temp, temp_bytes ? temp_bytes : 16));
+  hipLaunchKernelGGL(iota_int_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rows_in, N);
+  RIHIP_CHECK_LAUNCH();
+  return RIHIP_OK;
+}
+int Grouper::group(const int* assign, hipStream_t st) {
+  size_t tb = temp_bytes;
+  HIPCHK(rocprim::radix_sort_pairs(temp, tb, assign, keys, (const int*)rows_in, rows, (size_t)N, 0, end_bit, st));
+  hipLaunchKernelGGL(list_bounds_kernel, dim3((unsigned)((nlist + 1 + 255) / 256)), dim3(256), 0, st, keys, N, nlist, off);
+  RIHIP_CHECK_LAUNCH();
+  return RIHIP_OK;
+}
+void Grouper::release() {
+  hipFree(keys); hipFree(rows_in); hipFree(rows); hipFree(off); hipFree(temp);
+  keys = rows_in = rows = off = nullptr; temp = nullptr;
+}
+}  // namespace rihip_index
+
+namespace {
 
 // Lloyd iterations on device.  C: [nlist,d] device, initial centroids in, final centroids out; assign: [N] device, the
 // assignment to the FINAL centroids; g holds that assignment grouped.

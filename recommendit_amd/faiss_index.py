@@ -64,6 +64,15 @@ class _IndexHandle:
             pass
 
 
+def _list_stats(sizes: np.ndarray) -> Dict:
+    sizes = np.asarray(sizes, dtype=np.int64)
+    n, tot = int(sizes.shape[0]), int(sizes.sum())
+    sq = int((sizes.astype(object) ** 2).sum()) if n else 0
+    return {"n_lists": n, "min": int(sizes.min()) if n else 0, "max": int(sizes.max()) if n else 0,
+            "mean": tot / n if n else 0.0, "empty": int((sizes == 0).sum()),
+            "imbalance": n * sq / (tot * tot) if tot else 0.0}
+
+
 class FAISSIndex:
     def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
         """exact=True skips the IVF partition (brute-force inner product; not in the reference)."""
@@ -73,10 +82,25 @@ class FAISSIndex:
         self.exact = exact
         self.index: Optional[_IndexHandle] = None
         self.item_ids: Optional[np.ndarray] = None
-        self._item_id_to_faiss_idx: Dict[int, int] = {}
+        self._id_map: Dict[int, int] = {}
+        self._id_map_stale = False
         self._item_ids_dev: Optional[torch.Tensor] = None
         self._deferred = False
         self._deficit: Optional[torch.Tensor] = None
+
+    @property
+    def _item_id_to_faiss_idx(self) -> Dict[int, int]:
+        """{item id: row}: the plain dict after a build or load; after add_items / remove_items / update_items it is
+        rebuilt from item_ids on the first read (save() reads it), not inside the update"""
+        if self._id_map_stale:
+            self._id_map = {int(iid): row for row, iid in enumerate(self.item_ids.tolist())}
+            self._id_map_stale = False
+        return self._id_map
+
+    @_item_id_to_faiss_idx.setter
+    def _item_id_to_faiss_idx(self, value: Dict[int, int]) -> None:
+        self._id_map = value
+        self._id_map_stale = False
 
     # -- build (faiss_index.py:45-82) ---------------------------------------------------------
     def build_ivf_index(self, embeddings: np.ndarray, item_ids: List[int], kmeans_iters: int = 20,
@@ -127,6 +151,99 @@ class FAISSIndex:
         self.item_ids = np.asarray(item_ids, dtype=np.int64)
         self._item_ids_dev = torch.from_numpy(self.item_ids).to(x_dev.device)
         logger.info("Index built: %d vectors, %d lists, probe=%d", self.index.ntotal, self.n_lists, self.n_probe)
+
+    # -- live catalogue (faiss add_with_ids / remove_ids; not in the reference, which rebuilds offline) ----------
+    # Every call is ONE repack of the corpus on the device under the existing centroids (csrc/index_update.hip): O(N),
+    # so batch the changes.  Centroids are not retrained: watch list_stats()["imbalance"].  The handle ends bit for bit
+    # in the state a from-scratch build of the final corpus with the same centroids would give.  Serving: an item id
+    # outside the feature store's item table (a new item the store has not seen) is not an error in
+    # rihip_rank_features_build -- it reads row 0 of the table, the reference's cold-start defaults.
+    def _apply_update(self, drop_ids, x_add: Optional[torch.Tensor], add_ids) -> Tuple[int, int]:
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        if self.search_pending():
+            raise RuntimeError("a deferred search is pending: call finish_search() before changing the index")
+        dev = self._item_ids_dev.device
+
+        def ids_dev(ids):
+            if ids is None:
+                return None, 0
+            if isinstance(ids, torch.Tensor):
+                t = ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+            else:
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))).to(dev)
+            return t, int(t.shape[0])
+
+        drop, n_drop = ids_dev(drop_ids)
+        add, n_add = ids_dev(add_ids)
+        x = None
+        if n_add or x_add is not None:
+            if x_add.dim() != 2 or x_add.shape[1] != self.embed_dim:
+                raise ValueError(f"Expected embeddings [n, {self.embed_dim}], got {tuple(x_add.shape)}")
+            if x_add.shape[0] != n_add:
+                raise ValueError(f"{x_add.shape[0]} embeddings for {n_add} item ids")
+            x = x_add.to(device=dev, dtype=torch.float32).contiguous()
+        n_old = self.index.ntotal
+        out = torch.empty(n_old + n_add, dtype=torch.int64, device=dev)
+        n_total, n_dropped, bad_id, bad_kind = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        rc = L.lib().rihip_ip_index_update(self.index._h, self._item_ids_dev.data_ptr(), L.ptr(drop) if n_drop else None,
+                                           n_drop, L.ptr(x) if n_add else None, L.ptr(add) if n_add else None, n_add,
+                                           out.data_ptr(), C.byref(n_total), C.byref(n_dropped), C.byref(bad_id),
+                                           C.byref(bad_kind), L.stream_ptr())
+        if rc != 0 and bad_kind.value != 0:
+            raise ValueError(L.lib().rihip_last_error().decode("utf-8", "replace"))
+        L.check(rc, "ip_index_update")
+        if n_dropped.value == 0 and n_add == 0:
+            return 0, 0
+        self._item_ids_dev = out[:n_total.value]
+        self.item_ids = self._item_ids_dev.cpu().numpy()
+        self._id_map_stale = True
+        return int(n_dropped.value), n_add
+
+    def _normalised(self, embeddings: np.ndarray) -> torch.Tensor:
+        embeddings = np.asarray(embeddings)
+        if embeddings.dtype != np.float32:
+            raise ValueError("Embeddings must be float32")
+        if embeddings.ndim != 2 or embeddings.shape[1] != self.embed_dim:
+            raise ValueError(f"Expected embeddings [n, {self.embed_dim}], got {embeddings.shape}")
+        norms = np.linalg.norm(embeddings, axis=1, keepdims=True)
+        return torch.from_numpy(np.ascontiguousarray(embeddings / np.maximum(norms, 1e-8), dtype=np.float32)).to(L.device())
+
+    def add_items(self, embeddings: np.ndarray, item_ids) -> int:
+        """Append f32 [n, embed_dim] rows (normalised as build_ivf_index does) as rows N .. N+n-1 with these ids; -> n.
+        ValueError for an id that is already stored or repeated."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        return self.add_items_device(self._normalised(embeddings), item_ids)
+
+    def add_items_device(self, x_dev: torch.Tensor, item_ids) -> int:
+        """add_items for rows that are already normalised and on the device (as build_from_device)"""
+        return self._apply_update(None, x_dev, item_ids)[1]
+
+    def remove_items(self, item_ids) -> int:
+        """Remove the stored items with these ids (ids that are not stored are ignored, as faiss remove_ids does);
+        surviving rows keep their relative order and are renumbered densely.  -> number of items removed"""
+        return self._apply_update(item_ids, None, None)[0]
+
+    def update_items(self, embeddings: np.ndarray, item_ids) -> Tuple[int, int]:
+        """Upsert in one repack: a stored id is dropped and its new vector appended, an unknown id is appended; the
+        result is that of remove_items(ids) followed by add_items(embeddings, ids).  -> (replaced, added)"""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        replaced, n = self._apply_update(item_ids, self._normalised(embeddings), item_ids)
+        return replaced, n - replaced
+
+    def list_stats(self) -> Dict:
+        """IVF list sizes: n_lists, min, max, mean, empty, imbalance = n_lists * sum(len^2) / sum(len)^2 (faiss
+        imbalance_factor: 1.0 = even lists); it grows as updates drift away from the trained partition -- the signal
+        to rebuild.  Flat index: {"n_lists": 0}."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        if not self.index.is_ivf:
+            return {"n_lists": 0}
+        sizes = np.empty(int(L.lib().rihip_ip_index_nlist(self.index._h)), dtype=np.int64)
+        L.check(L.lib().rihip_ip_index_list_sizes(self.index._h, sizes.ctypes.data), "ip_index_list_sizes")
+        return _list_stats(sizes)
 
     # -- trained state (what faiss exposes as index.quantizer / index.invlists) ------------------
     def centroids(self) -> np.ndarray:
