@@ -393,6 +393,24 @@ int rihip_ip_index_update(void* handle, const int64_t* item_ids, const int64_t* 
                           int64_t* n_total, int64_t* n_dropped, int64_t* bad_id, int* bad_kind, void* stream);
 /* real rows of every IVF list (host int64 [nlist]) */
 int rihip_ip_index_list_sizes(void* handle, int64_t* out);
+/* Filtered search (faiss SearchParameters.sel / IDSelector on IndexFlat and IndexIVFFlat; the reference's FAISSIndex has
+ * none): every stored row carries one 32-bit tag word, a query carries (any_of, all_of, none_of), and row r passes iff
+ * (any_of == 0 || (tag[r] & any_of) != 0) && (tag[r] & all_of) == all_of && (tag[r] & none_of) == 0.  The result is the
+ * exact top k of the passing rows (IVF: of the passing rows of the probed lists; probing does not look at tags) in the
+ * plain search's order, padded with -inf / -1; (0,0,0) equals rihip_ip_index_search bit for bit.
+ * set_tags: device uint32 [ntotal] in insertion-row order, copied into the order the scan reads (NULL clears);
+ * synchronises the stream.  set_vectors, train_ivf*, set_ivf and rihip_ip_index_update drop the tags (has_tags = 0): set
+ * them again in the new row order.  save / load do not carry tags.
+ * search_filtered: pred_dev device uint32, query q's three words at pred_dev[q * pred_stride]; pred_stride = 3 (one
+ * predicate per query) or 0 (one shared by the batch).  Honours set_id_map.  Its exactness check is always synchronous
+ * (set_deferred_check is ignored); RIHIP_ERR_STATE without tags or while a deferred search is pending.  A large flat
+ * index takes the all-f32 scan whatever set_two_precision says.
+ * filtered_stats: cumulative {queries searched filtered, of those re-done by the exact fallback}. */
+int rihip_ip_index_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream);
+int rihip_ip_index_has_tags(void* handle);
+int rihip_ip_index_search_filtered(void* handle, const float* Q, int64_t nq, int k, const uint32_t* pred_dev,
+                                   int64_t pred_stride, float* out_scores, int64_t* out_rows, void* stream);
+int rihip_ip_index_filtered_stats(void* handle, int64_t* out);
 
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict

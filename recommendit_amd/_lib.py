@@ -113,6 +113,10 @@ SIGNATURES = {
     "rihip_ip_index_update": (C.c_int, [vp, vp, vp, c_i64, vp, vp, c_i64, vp, C.POINTER(c_i64), C.POINTER(c_i64),
                                         C.POINTER(c_i64), C.POINTER(C.c_int), vp]),
     "rihip_ip_index_list_sizes": (C.c_int, [vp, vp]),
+    "rihip_ip_index_set_tags": (C.c_int, [vp, vp, vp]),
+    "rihip_ip_index_has_tags": (C.c_int, [vp]),
+    "rihip_ip_index_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, vp, c_i64, vp, vp, vp]),
+    "rihip_ip_index_filtered_stats": (C.c_int, [vp, vp]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

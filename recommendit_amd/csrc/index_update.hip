@@ -308,6 +308,7 @@ extern "C" int rihip_ip_index_update(void* handle, const int64_t* item_ids, cons
     RIHIP_CHECK_LAUNCH();
     HIPCHK(hipStreamSynchronize(st));
     hipFree(h->X); hipFree(h->Xb);
+    drop_tags(h);
     h->X = o.Xn; o.Xn = nullptr; h->Xb = nullptr; h->max_norm = 0.f; h->N = n_new; h->id_map = nullptr;
     rihip_bump_generation();
     *n_total = n_new;

@@ -49,11 +49,17 @@ struct IpIndex {
   int64_t* list_poff = nullptr; // [nlist+1] first physical row of each list (device)
   int* list_len_dev = nullptr;  // [nlist] real rows of each list (device)
   int64_t* row_ids = nullptr;  // [Np] original row per physical row, -1 for padding
+  // filtered search (rihip_ip_index_set_tags): one 32-bit tag word per scanned row, in the order the scan reads them
+  // (flat: [N] row order; IVF: [Np] physical order, padding slots 0); null = untagged
+  uint32_t* tags = nullptr;
+  int64_t filt_stats[2] = {0, 0};   // queries searched filtered, of those re-done by the exact fallback
   std::vector<int64_t> list_len;  // host copy
   // scratch (grown on demand, owned by the handle)
   DevBuf<uint64_t> cand, scand, fcand, seg;   // seg: per (query, corpus split) survivor segments of the bf16 filter
   DevBuf<int> seg_cnt;
   DevBuf<int> count, fail_flags, fail_list, n_fail, fcount;
+  DevBuf<int> n_pass;             // filtered search: rows that pass each query's predicate (IVF: of its probed lists)
+  DevBuf<uint32_t> fpred;         // filtered search: predicates of the queries being re-done
   DevBuf<float> thr, thr2, fQ, qpad;    // qpad: queries / rows zero-padded from du to d columns
   DevBuf<float> coarse;                                    // IVF: coarse scores [nq,nlist]
   DevBuf<int> probe_list, list_q, list_cnt, list_qoff, list_cur, work_off, plan;
@@ -68,8 +74,14 @@ struct IpIndex {
   bool ev_recorded = false;
 };
 
+// a new row order or layout invalidates the tag copy: the index reports untagged until the caller sets tags again
+inline void drop_tags(IpIndex* h) {
+  if (h->tags) { hipFree(h->tags); h->tags = nullptr; }
+}
+
 inline void free_index_arrays(IpIndex* h) {
   rihip_bump_generation();
+  drop_tags(h);
   hipFree(h->X); hipFree(h->C); hipFree(h->tile_list); hipFree(h->list_poff); hipFree(h->list_len_dev); hipFree(h->row_ids); hipFree(h->Xb);
   h->X = nullptr; h->C = nullptr; h->tile_list = nullptr; h->list_poff = nullptr; h->list_len_dev = nullptr; h->row_ids = nullptr; h->Xb = nullptr;
   h->N = 0; h->Np = 0; h->ivf = false; h->nlist = 0; h->list_len.clear();

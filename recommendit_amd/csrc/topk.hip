@@ -15,6 +15,11 @@
 // IVF-Flat (IP): k-means lists built on device, corpus re-ordered list-contiguous and padded
 // to the 64-row tile so a tile belongs to one list; the scan skips tiles whose list no query
 // of the block probes and masks per query.
+//
+// Filtered search (rihip_ip_index_search_filtered; faiss SearchParameters.sel): one 32-bit tag word per row, one
+// (any_of, all_of, none_of) predicate per query, tested in the scans' emit (the FILT instantiations of scan_kernel and
+// ivf_scan_lm_kernel).  The thresholded paths count each query's passing rows first: few passing rows mean "keep them
+// all", not "re-do the query".
 #include "common.h"
 #include "recommendit_hip.h"
 
@@ -67,13 +72,47 @@ struct ScanArgs {
   int* seg_cnt;               // [nq, nsplit] survivors found (may exceed seg_cap: the query is then re-done exactly)
   int seg_cap;
   int cs;                     // ints between two queries' candidate counters (0/1 = dense; CSTRIDE = a 128-B line each)
+  // filtered search (scan_kernel<D, true> only)
+  const uint32_t* tags;       // [N] tag word of every corpus row
+  const uint32_t* pred;       // query q's predicate (any_of, all_of, none_of) at pred[q * pred_stride]
+  int pred_stride;            // 3 = one per query, 0 = one shared by the batch
 };
+
+// Filtered search: row r passes query q's predicate iff (any_of == 0 or tag[r] & any_of) and (tag[r] & all_of) == all_of
+// and (tag[r] & none_of) == 0.  (0,0,0) passes every row.
+struct Pred {
+  uint32_t any_of, all_of, none_of;
+  __device__ __forceinline__ bool pass(uint32_t t) const {
+    return (any_of == 0u || (t & any_of) != 0u) && (t & all_of) == all_of && (t & none_of) == 0u;
+  }
+};
+__device__ __forceinline__ Pred load_pred(const uint32_t* pred, int64_t q, int stride) {
+  const uint32_t* p = pred + q * stride;
+  return Pred{p[0], p[1], p[2]};
+}
+// the tag words of a lane's 16 accumulator rows: four runs of four rows (acc_row)
+__device__ __forceinline__ uint32_t tag_of(const uint4* tw, int r) {
+  const uint4 t = tw[r >> 2];
+  return (r & 3) == 0 ? t.x : (r & 3) == 1 ? t.y : (r & 3) == 2 ? t.z : t.w;
+}
+template <bool FILT>
+__device__ __forceinline__ uint32_t* tag_tiles() {   // LDS only in the filtered instantiation
+  if constexpr (FILT) {
+    __shared__ __attribute__((aligned(16))) uint32_t Ts[3 * TRS];
+    return Ts;
+  } else {
+    return nullptr;
+  }
+}
 
 
 // 4 waves x 32 register-stationary queries share each 32-row corpus tile.  Same software pipeline as the
 // in-batch sweep: 3 LDS buffers, tile t+2 prefetched through registers, the S chain of tile t+1 interleaved with
 // the threshold test / candidate emission of tile t, one barrier per tile.
-template <int D>
+// FILT: every tile brings its 32 tag words along through the same prefetch (one coalesced 128-byte load by 32 threads, a
+// slot of LDS per stage); emit tests the lane's query predicate against them.  A failing row is key 0 (below every score)
+// in a dense slot and simply no hit in append mode.  FILT = false compiles to the unfiltered kernel as it was.
+template <int D, bool FILT = false>
 __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
   constexpr int LDX = D + 4, KB = D / 8;
   constexpr int EPK = 16 / KB > 0 ? 16 / KB : 1;
@@ -90,6 +129,10 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
   for (int kb = 0; kb < KB; ++kb) qf[kb] = *reinterpret_cast<const f32x4*>(&a.Q[qrow * D + kb * 8 + 4 * hh]);
   const float thr = (a.thr && q_ok) ? a.thr[q] : -INFINITY;
   uint64_t* my_cand = a.cand + (size_t)qrow * a.cap;
+  uint32_t* Ts = tag_tiles<FILT>();
+  Pred pr{0u, 0u, 0u};
+  if constexpr (FILT) pr = load_pred(a.pred, qrow, a.pred_stride);
+  uint32_t tg = 0u;   // FILT: staged tag word (threads 0..31)
 
   const int64_t n_seq = (a.n_virtual + TRS - 1) / TRS;
   const int64_t per = (n_seq + a.nsplit - 1) / a.nsplit;
@@ -111,6 +154,10 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
         val = reinterpret_cast<const f32x4*>(a.X + (size_t)(v * a.row_stride) * D)[c4];
       stage[i] = val;
     }
+    if constexpr (FILT) {
+      tg = 0u;
+      if (tid < TRS && v_base + tid < a.n_virtual) tg = a.tags[(size_t)((v_base + tid) * a.row_stride)];
+    }
   };
   auto store_tile = [&](int buf) {
 #pragma unroll
@@ -119,23 +166,40 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
       const int r = idx / (D / 4), c4 = idx % (D / 4);
       if (idx < TRS * (D / 4)) *reinterpret_cast<f32x4*>(&Xs[buf][r * LDX + c4 * 4]) = stage[i];
     }
+    if constexpr (FILT) {
+      if (tid < TRS) Ts[buf * TRS + tid] = tg;
+    }
   };
-  auto emit = [&](const f32x16& acc, int64_t tile) {
+  auto emit = [&](const f32x16& acc, int64_t tile, int buf) {
     const int64_t v_base = tile * TRS;
     if (!q_ok) return;
+    uint4 tw[4];
+    if constexpr (FILT) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) tw[g] = *reinterpret_cast<const uint4*>(&Ts[buf * TRS + 8 * g + 4 * hh]);
+    }
     if (a.dense) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t v = v_base + acc_row(r, lane);
-        if (v < a.n_virtual) my_cand[v] = make_key(acc[r], (uint32_t)v);
+        if constexpr (FILT) {
+          if (v < a.n_virtual) my_cand[v] = pr.pass(tag_of(tw, r)) ? make_key(acc[r], (uint32_t)v) : 0ull;
+        } else {
+          if (v < a.n_virtual) my_cand[v] = make_key(acc[r], (uint32_t)v);
+        }
       }
       return;
     }
     const int n_ok = (a.n_virtual - v_base) < TRS ? (int)(a.n_virtual - v_base) : TRS;
     unsigned hits = 0;  // per-lane aggregation: one atomic per (query, tile) that has survivors
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (acc_row(r, lane) < n_ok && acc[r] >= thr) hits |= (1u << r);
+    for (int r = 0; r < 16; ++r) {
+      if constexpr (FILT) {
+        if (acc_row(r, lane) < n_ok && acc[r] >= thr && pr.pass(tag_of(tw, r))) hits |= (1u << r);
+      } else {
+        if (acc_row(r, lane) < n_ok && acc[r] >= thr) hits |= (1u << r);
+      }
+    }
     if (hits) {
       int pos = atomicAdd(&a.count[q * (a.cs > 1 ? a.cs : 1)], __popc(hits));
 #pragma unroll
@@ -177,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
     if (has_pre) load_tile(tile_at(i + 2));
     f32x16 sn = zero16();
     if (has_next) s_chain(Xs[nxt], sn);  // the compiler interleaves the (independent) emit below into this chain
-    emit(st, tile_at(i));
+    emit(st, tile_at(i), it);
     if (has_pre) store_tile(pre);
     st = sn;
     __syncthreads();
@@ -1018,6 +1082,10 @@ struct FinArgs {
   int* fail_list; int* n_fail;   // optional (mode 0): a failed query appends itself here (n_fail reset by an earlier launch's zero_me)
   int lds_keys;           // > 0: key slots in dynamic LDS behind the sort buffer (set by launch_finalize for small launches)
   int sort_slots;         // uint64 slots of the sort buffer in front of them
+  // filtered search (finalize_kernel<true>): rows that pass query q's predicate at n_pass[q * n_pass_stride]; a query
+  // fails when it holds fewer than min(k, n_pass) candidates -- fewer than k passing rows is an ordinary answer
+  const int* n_pass;
+  int n_pass_stride;
 };
 
 #ifdef RIHIP_FIN_PROBE
@@ -1112,6 +1180,7 @@ __device__ __forceinline__ uint64_t finalize_select(const FinArgs& a, const uint
   return T;
 }
 
+template <bool FILT = false>
 __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
   __shared__ unsigned hist[256];
   extern __shared__ __attribute__((aligned(16))) uint64_t sbuf[];  // [pow2 >= k] (mode 0 only), then [lds_keys] key copy
@@ -1126,7 +1195,12 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
   const int64_t oslot = a.out_slot ? a.out_slot[qi] : qi;
 
   bool fail = (cnt_raw > a.cap) || (a.need_min > 0 && cnt_raw < a.need_min);
-  if (a.ivf_thr && cnt_raw < a.k && a.ivf_thr[q] > -INFINITY) fail = true;
+  if constexpr (FILT) {
+    const int np = a.n_pass[q * a.n_pass_stride];
+    fail = (cnt_raw > a.cap) || cnt_raw < (np < a.k ? np : a.k);
+  } else {
+    if (a.ivf_thr && cnt_raw < a.k && a.ivf_thr[q] > -INFINITY) fail = true;
+  }
   int k_sel = (a.mode == 0) ? a.k : a.rank;
   if (k_sel > n) k_sel = (int)n;
   int P = 64;
@@ -1506,6 +1580,10 @@ struct LmArgs {
                              // atomics serialise in L2)
   int64_t dense_cap;         // > 0: dense slots, cand = [nq*nprobe, dense_cap] pre-zeroed keys (no atomics)
   int dense_ids;             // dense slots carry the original row id (unfiltered search) instead of 0 (threshold sample)
+  // filtered search (ivf_scan_lm_kernel<D, true> only)
+  const uint32_t* tags;      // [Np] tag word of every physical row (padding slots 0)
+  const uint32_t* pred;      // query q's predicate at pred[q * pred_stride]
+  int pred_stride;
 };
 
 // coarse scores cs[q, c] = <Q[q], C[c]> on exact-f32 MFMA (4 waves x 32 register-stationary queries, centroid tiles
@@ -1709,7 +1787,9 @@ __global__ __launch_bounds__(256, 2) void ivf_prepare_small_kernel(PrepSmallArgs
   }
 }
 
-template <int D>
+// FILT: the tile's 32 tag words are contiguous in the physical order the handle keeps them in; every lane loads the four
+// 16-byte runs of its accumulator rows before the MFMA chain (two addresses per wave and load, in flight under the chain).
+template <int D, bool FILT = false>
 __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
   constexpr int KB = D / 8, LDX = D + 4;
   constexpr int NL = (TRS * (D / 4)) / 64;  // 16-byte pieces per lane per tile (fully coalesced 1-KiB wave loads)
@@ -1746,6 +1826,9 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
   for (int kb = 0; kb < KB; ++kb) qf[kb] = *reinterpret_cast<const f32x4*>(&a.Q[q * D + kb * 8 + 4 * hh]);
   const float thr = a.thr ? a.thr[q] : -INFINITY;
   uint64_t* my_cand = a.cand + (size_t)q * a.cap;
+  Pred pr{0u, 0u, 0u};
+  if constexpr (FILT) pr = load_pred(a.pred, q, a.pred_stride);
+  uint4 tw[4];
   // dense mode (threshold sample): slot = (pair, sampled tile, row): no atomics, no row-id gather
   uint64_t* my_dense = a.dense_cap > 0 ? a.cand + (size_t)pair * a.dense_cap : nullptr;
   const int64_t per = tpi;
@@ -1790,14 +1873,15 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
         const int rr = acc_row(r, lane);
         const int64_t sl = i * TRS + rr;
         if (sl < a.dense_cap)
-          my_dense[sl] = rr < n_ok ? make_key(acc[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
+          my_dense[sl] = (rr < n_ok && (!FILT || pr.pass(tag_of(tw, r))))
+                             ? make_key(acc[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
       }
       return;
     }
     unsigned hits = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (acc_row(r, lane) < n_ok && acc[r] >= thr) hits |= (1u << r);
+      if (acc_row(r, lane) < n_ok && acc[r] >= thr && (!FILT || pr.pass(tag_of(tw, r)))) hits |= (1u << r);
     if (hits) {
       int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
 #pragma unroll
@@ -1816,10 +1900,97 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
   for (int64_t i = i0; i < i1; ++i) {
     const bool more = i + 1 < i1;
     if (more) load_tile(i + 1);          // in flight during this tile's MFMA chain
+    if constexpr (FILT) {
+      const uint4* tp = reinterpret_cast<const uint4*>(a.tags + p0 + i * tstep * TRS + 4 * hh);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) tw[g] = tp[2 * g];
+    }
     const f32x16 acc = chain();
     if (more) store_tile();              // after the chain's LDS reads (same wave: in order)
     emit(acc, i);
   }
+}
+
+// ------------------------------- filtered search: helpers ---------------------------------------
+// The thresholded searches assume that about k*S/N of the sample beats the threshold and that at least min(k, N)
+// candidates exist.  Under a predicate both depend on how many rows PASS, so the filtered search counts them first.
+struct FiltCtx {
+  const uint32_t* pred;   // device: query q's (any_of, all_of, none_of) at pred[q * stride]
+  int stride;             // 3, or 0 = one predicate shared by the batch
+};
+constexpr int CNT_TAGS = 4096;   // tag words staged in LDS per workgroup of the flat count
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// flat index, per-query predicates: n_pass[q] = #{r < N : row r passes query q}.  A workgroup stages CNT_TAGS tag words in
+// LDS and every thread tests all of them against its own query's predicate (broadcast LDS reads, 16 bytes at a time).
+__global__ __launch_bounds__(256) void count_pass_kernel(const uint32_t* __restrict__ tags, int64_t N,
+                                                         const uint32_t* __restrict__ pred, int64_t nq, int* n_pass) {
+  __shared__ __attribute__((aligned(16))) uint32_t Tg[CNT_TAGS];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * CNT_TAGS;
+  const int n = (int)((N - r0) < CNT_TAGS ? (N - r0) : CNT_TAGS);
+  for (int i = tid; i < CNT_TAGS; i += 256) Tg[i] = i < n ? tags[r0 + i] : 0u;
+  __syncthreads();
+  const int64_t q = (int64_t)blockIdx.y * 256 + tid;
+  if (q >= nq) return;
+  const Pred pr = load_pred(pred, q, 3);
+  int cnt = 0;
+  const int n4 = n & ~3;
+  for (int i = 0; i < n4; i += 4) {
+    const uint4 t = *reinterpret_cast<const uint4*>(&Tg[i]);
+    cnt += (int)pr.pass(t.x) + (int)pr.pass(t.y) + (int)pr.pass(t.z) + (int)pr.pass(t.w);
+  }
+  for (int i = n4; i < n; ++i) cnt += (int)pr.pass(Tg[i]);
+  if (cnt) atomicAdd(&n_pass[q], cnt);
+}
+// flat index, one shared predicate: n_pass[0] = #{r < N : row r passes}; a thread per row, one atomic per wave
+__global__ __launch_bounds__(256) void count_pass_shared_kernel(const uint32_t* __restrict__ tags, int64_t N,
+                                                                const uint32_t* __restrict__ pred, int* n_pass) {
+  const Pred pr = load_pred(pred, 0, 0);
+  int cnt = 0;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < N; r += (int64_t)gridDim.x * 256) cnt += (int)pr.pass(tags[r]);
+  cnt = wave_sum_i(cnt);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_pass, cnt);
+}
+// IVF: n_pass[q] = passing rows of query q's probed lists; one workgroup per (query, probe) pair over the list's tag run
+__global__ __launch_bounds__(256) void count_pass_ivf_kernel(const uint32_t* __restrict__ tags, const int64_t* __restrict__ list_poff,
+                                                             const int* __restrict__ list_len, const int* __restrict__ probe_list,
+                                                             int nprobe, const uint32_t* __restrict__ pred, int pred_stride,
+                                                             int* n_pass) {
+  const int64_t pair = blockIdx.x;
+  const int c = probe_list[pair];
+  if (c < 0) return;
+  const int64_t q = pair / nprobe;
+  const Pred pr = load_pred(pred, q, pred_stride);
+  const uint32_t* t = tags + list_poff[c];
+  const int len = list_len[c];
+  int cnt = 0;
+  for (int i = threadIdx.x; i < len; i += 256) cnt += (int)pr.pass(t[i]);
+  cnt = wave_sum_i(cnt);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&n_pass[q], cnt);
+}
+// The sample's rank-th best is key 0 when fewer than `rank` sampled rows pass, and ord2f(0) is a NaN that `score >= thr`
+// rejects for every row: such a query keeps EVERY passing row (thr = -inf), and so does one whose passing rows all fit
+// the candidate list.
+__global__ void filt_thr_kernel(float* thr, const int* __restrict__ n_pass, int n_pass_stride, int64_t cap, int64_t nq) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const float t = thr[q];
+  if (t != t || (int64_t)n_pass[q * n_pass_stride] <= cap) thr[q] = -INFINITY;
+}
+__global__ void gather_pred_kernel(const uint32_t* __restrict__ pred, const int* __restrict__ idx, int n, uint32_t* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n * 3) out[i] = pred[(size_t)idx[i / 3] * 3 + (i % 3)];
+}
+// tags in insertion-row order -> the order the IVF scan reads them (padding slots 0)
+__global__ void tags_to_scan_order_kernel(const uint32_t* __restrict__ by_row, const int64_t* __restrict__ row_ids, int64_t Np,
+                                          uint32_t* out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < Np) { const int64_t r = row_ids[p]; out[p] = r >= 0 ? by_row[r] : 0u; }
 }
 
 // ------------------------------------------ handle ---------------------------------------------
@@ -1831,7 +2002,8 @@ __global__ void fill_int_kernel(int* p, int64_t n, int v) {
 
 template <int D>
 void launch_scan(const ScanArgs& a, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL((scan_kernel<D>), grid, dim3(256), 0, st, a);
+  if (a.tags) hipLaunchKernelGGL((scan_kernel<D, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((scan_kernel<D, false>), grid, dim3(256), 0, st, a);
 }
 int dispatch_scan(int d, const ScanArgs& a, dim3 grid, hipStream_t st) {
   if (d == 32) launch_scan<32>(a, grid, st);
@@ -1854,7 +2026,9 @@ int launch_finalize(const FinArgs& f0, unsigned n, hipStream_t st) {
   size_t lds = 0;
   static bool granted = false;
   if (!granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(sizeof(uint64_t) * K_MAX));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(sizeof(uint64_t) * K_MAX));
     granted = true;
   }
@@ -1871,7 +2045,8 @@ int launch_finalize(const FinArgs& f0, unsigned n, hipStream_t st) {
     f.lds_keys = (int)f.cap;
     lds = sizeof(uint64_t) * (size_t)(P + f.cap);
   }
-  hipLaunchKernelGGL(finalize_kernel, dim3(n), dim3(256), lds, st, f);
+  if (f.n_pass) hipLaunchKernelGGL(finalize_kernel<true>, dim3(n), dim3(256), lds, st, f);
+  else hipLaunchKernelGGL(finalize_kernel<false>, dim3(n), dim3(256), lds, st, f);
   return check_launch("finalize");
 }
 
@@ -1884,7 +2059,10 @@ int pick_nsplit(int64_t nq, int64_t n_tiles) {
   return (int)ns;
 }
 
-int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, int64_t* out_r, hipStream_t st) {
+// F != null: the filtered search (rihip_ip_index_search_filtered).  Same four paths; the scans test F's predicates against
+// h->tags, the thresholded paths count the passing rows first and never defer their exactness check.
+int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, int64_t* out_r, hipStream_t st,
+                 const FiltCtx* F = nullptr) {
   const int d = h->d;
   const int64_t Nphys = h->ivf ? h->Np : h->N;
   const int64_t n_tiles = (Nphys + TRS - 1) / TRS;
@@ -1903,6 +2081,20 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
   FinArgs fa;
   memset(&fa, 0, sizeof(fa));
   fa.nq = nq; fa.k = k; fa.count = h->count.p; fa.out_scores = out_s; fa.out_rows = out_r; fa.id_map = h->id_map;
+  // predicates the scans read: the batch's, or the gathered ones of the queries being re-done
+  const uint32_t* f_pred = F ? F->pred : nullptr;
+  int f_stride = F ? F->stride : 0;
+  if (F) {
+    sa.tags = h->tags; sa.pred = f_pred; sa.pred_stride = f_stride;
+    RCCHK(h->n_pass.reserve(nq));
+    RCCHK(h->fpred.reserve(64 * 3));
+    h->filt_stats[0] += nq;
+  }
+  auto gather_pred = [&](const int* idx, int n) {   // re-do of failed queries: their predicates, in fail-list order
+    if (!F || F->stride == 0) return;
+    hipLaunchKernelGGL(gather_pred_kernel, dim3((unsigned)((n * 3 + 255) / 256)), dim3(256), 0, st, F->pred, idx, n, h->fpred.p);
+    f_pred = h->fpred.p;
+  };
 
   if (h->ivf) {
     // population upper bound of one query = the nprobe longest lists (padded to the 64-row granule)
@@ -1930,6 +2122,13 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
       // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
       const int64_t bound = (int64_t)target + nlist + (n * nprobe + 31) / 32 + 4;
       const dim3 grid((unsigned)((bound + 3) / 4));
+      if (F) {
+        x.tags = h->tags; x.pred = f_pred; x.pred_stride = f_stride;
+        if (d == 32) hipLaunchKernelGGL((ivf_scan_lm_kernel<32, true>), grid, dim3(256), 0, st, x);
+        else if (d == 64) hipLaunchKernelGGL((ivf_scan_lm_kernel<64, true>), grid, dim3(256), 0, st, x);
+        else hipLaunchKernelGGL((ivf_scan_lm_kernel<128, true>), grid, dim3(256), 0, st, x);
+        return check_launch("filtered ivf scan");
+      }
       if (d == 32) hipLaunchKernelGGL((ivf_scan_lm_kernel<32>), grid, dim3(256), 0, st, x);
       else if (d == 64) hipLaunchKernelGGL((ivf_scan_lm_kernel<64>), grid, dim3(256), 0, st, x);
       else hipLaunchKernelGGL((ivf_scan_lm_kernel<128>), grid, dim3(256), 0, st, x);
@@ -2015,12 +2214,21 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
     RCCHK(h->scand.reserve(nq * cap_s));
     RCCHK(h->cand.reserve(nq * cap));
     RCCHK(ivf_prepare(Q, nq, SS, h->scand.p, nq * cap_s));      // (also zeroes the sample's dense slots: key 0 = below every score)
+    if (F) {   // passing rows of every query's probed lists
+      HIPCHK(hipMemsetAsync(h->n_pass.p, 0, sizeof(int) * nq, st));
+      hipLaunchKernelGGL(count_pass_ivf_kernel, dim3((unsigned)(nq * nprobe)), dim3(256), 0, st, h->tags, h->list_poff,
+                         h->list_len_dev, h->probe_list.p, nprobe, f_pred, f_stride, h->n_pass.p);
+    }
     RCCHK(ivf_scan(Q, nq, nullptr, h->scand.p, cap_s, SS, cap_l, true, 0));
     // (the sample's lists are dense: count = null means cap_s keys each; this launch also resets the failed-query counter
     // that the final select appends to -- no fill / collect launches of their own)
     fa.cand = h->scand.p; fa.cap = cap_s; fa.mode = 1; fa.rank = rank; fa.thr_out = h->thr.p; fa.count = nullptr;
     fa.zero_me = h->n_fail.p;
     RCCHK(launch_finalize(fa, (unsigned)nq, st));
+    if (F) {   // (the sampled share of the passing rows beats the threshold like the sampled share of all rows did: same rank)
+      hipLaunchKernelGGL(filt_thr_kernel, dim3(nqb), dim3(256), 0, st, h->thr.p, h->n_pass.p, 1, cap, nq);
+      fa.n_pass = h->n_pass.p; fa.n_pass_stride = 1;
+    }
     RCCHK(ivf_scan(Q, nq, h->thr.p, h->cand.p, cap, 1, 0, false, 0));                         // pass B: all probed tiles, filtered
     fa.cand = h->cand.p; fa.cap = cap; fa.mode = 0; fa.thr_out = nullptr; fa.fail_flags = h->fail_flags.p;
     fa.count = h->count.p; fa.zero_me = nullptr; fa.fail_list = h->fail_list.p; fa.n_fail = h->n_fail.p;
@@ -2028,7 +2236,7 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
     RCCHK(launch_finalize(fa, (unsigned)nq, st));
     RCCHK(check_launch("finalize"));
     HIPCHK(hipMemcpyAsync(h->h_nfail, h->n_fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (h->defer_check && h->defer_ok) {   // the caller checks later (rihip_ip_index_search_finish): no host sync here
+    if (h->defer_check && h->defer_ok && !F) {   // the caller checks later (rihip_ip_index_search_finish): no host sync here
       // finish then waits for THIS point of the stream only: whatever the caller enqueues behind the search keeps the GPU
       // busy while the host is already back (a capturing stream records no event: replays use _last_fail_count)
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2044,6 +2252,7 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
     }
     HIPCHK(hipStreamSynchronize(st));
     const int nf = *h->h_nfail;
+    if (F) h->filt_stats[1] += nf;
     if (nf > 0) {  // threshold too aggressive (or candidate overflow) for these queries: unfiltered re-do
       const int FCH = 64;
       RCCHK(h->fQ.reserve((int64_t)FCH * d));
@@ -2051,6 +2260,7 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
         const int nfc = (nf - f0 < FCH) ? nf - f0 : FCH;
         hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((nfc * d + 255) / 256)), dim3(256), 0, st, Q,
                            h->fail_list.p + f0, nfc, d, h->fQ.p);
+        gather_pred(h->fail_list.p + f0, nfc);
         RCCHK(ivf_full(h->fQ.p, nfc, h->fail_list.p + f0));
       }
     }
@@ -2070,7 +2280,8 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
   }
 
   // ---- pass 0: threshold from a strided sample
-  const bool two_prec = h->two_precision && h->Xb != nullptr;
+  // (a filtered search takes the all-f32 scan: the bf16 filter pass does not read tags)
+  const bool two_prec = h->two_precision && h->Xb != nullptr && !F;
   // the two-precision path samples twice as many rows: the threshold estimate tightens (expected survivors per query
   // 2 200 -> 1 700 at k = 500, N = 1 M), which saves more in the filter's emission and in the re-score than the longer
   // sample pass costs (measured 2.33 -> 2.16 ms per 4 096 queries; 3x, 4x the same, 6x slower again)
@@ -2171,6 +2382,15 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
   fa.zero_me = h->n_fail.p;            // (reset here: refine_kernel appends the failed queries itself)
   RCCHK(launch_finalize(fa, (unsigned)nq, st));
   fa.count = h->count.p; fa.zero_me = nullptr;
+  if (F) {   // exact passing-row counts; queries whose passing rows all fit the candidate list skip the threshold
+    const int np_stride = f_stride == 0 ? 0 : 1;
+    HIPCHK(hipMemsetAsync(h->n_pass.p, 0, sizeof(int) * (np_stride ? nq : 1), st));
+    if (np_stride) hipLaunchKernelGGL(count_pass_kernel, dim3((unsigned)((h->N + CNT_TAGS - 1) / CNT_TAGS), nqb), dim3(256), 0, st,
+                                      h->tags, h->N, f_pred, nq, h->n_pass.p);
+    else hipLaunchKernelGGL(count_pass_shared_kernel, dim3(2 * RIHIP_NCU), dim3(256), 0, st, h->tags, h->N, f_pred, h->n_pass.p);
+    hipLaunchKernelGGL(filt_thr_kernel, dim3(nqb), dim3(256), 0, st, h->thr.p, h->n_pass.p, np_stride, cap, nq);
+    fa.n_pass = h->n_pass.p; fa.n_pass_stride = np_stride;
+  }
   // ---- pass 1: thresholded scan (survivors into per-(query, split) segments; the f32 scan appends through `count`)
   if (!two_prec)
     hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)((nq * CSTRIDE + 255) / 256)), dim3(256), 0, st, h->count.p, nq * CSTRIDE, 0);
@@ -2237,6 +2457,7 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
   HIPCHK(hipMemcpyAsync(h->h_nfail, h->n_fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const int nf = *h->h_nfail;
+  if (F) h->filt_stats[1] += nf;
   if (nf > 0) {  // exact re-do of under/overflowed queries (heavy ties, adversarial data)
     const int FCH = 8;
     RCCHK(h->fcand.reserve((int64_t)FCH * h->N));
@@ -2251,6 +2472,7 @@ int search_chunk(IpIndex* h, const float* Q, int64_t nq, int k, float* out_s, in
       memset(&fs, 0, sizeof(fs));
       fs.X = h->X; fs.n_virtual = h->N; fs.row_stride = 1; fs.Q = h->fQ.p; fs.nq = nfc; fs.thr = nullptr;
       fs.cand = h->fcand.p; fs.cap = h->N; fs.count = h->fcount.p; fs.dense = 1; fs.nsplit = pick_nsplit(nfc, n_tiles);
+      if (F) { gather_pred(h->fail_list.p + f0, nfc); fs.tags = h->tags; fs.pred = f_pred; fs.pred_stride = f_stride; }
       RCCHK(dispatch_scan(d, fs, dim3(1, fs.nsplit), st));
       FinArgs ff;
       memset(&ff, 0, sizeof(ff));
@@ -2322,6 +2544,7 @@ extern "C" int rihip_ip_index_destroy(void* handle) {
   IpIndex* h = (IpIndex*)handle;
   if (!h) return RIHIP_OK;
   free_index_arrays(h);
+  h->n_pass.release(); h->fpred.release();
   h->cand.release(); h->scand.release(); h->fcand.release(); h->count.release(); h->fail_flags.release();
   h->fail_list.release(); h->n_fail.release(); h->fcount.release(); h->thr.release(); h->thr2.release(); h->fQ.release();
   h->coarse.release(); h->probe_list.release(); h->list_q.release(); h->list_cnt.release(); h->list_qoff.release();
@@ -2402,6 +2625,65 @@ extern "C" int rihip_ip_index_search(void* handle, const float* Q, int64_t nq, i
   for (int64_t q0 = 0; q0 < nq; q0 += CH) {
     const int64_t n = (nq - q0 < CH) ? nq - q0 : CH;
     int rc = search_chunk(h, Q + q0 * h->d, n, k, out_scores + q0 * k, out_rows + q0 * k, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return RIHIP_OK;
+}
+
+// ---- filtered search: per-query tag predicates inside the scan ----------------------------------------------------
+extern "C" int rihip_ip_index_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && h->X && h->N > 0, RIHIP_ERR_STATE, "ip_index_set_tags: index is empty");
+  RIHIP_REQUIRE(!h->pending.active, RIHIP_ERR_STATE, "ip_index_set_tags: a deferred search is pending");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipStreamSynchronize(st));   // (searches in flight still read the old copy)
+  drop_tags(h);
+  if (!tags_by_row_dev) return RIHIP_OK;
+  const int64_t n = h->ivf ? h->Np : h->N;
+  uint32_t* t = nullptr;
+  HIPCHK(hipMalloc((void**)&t, sizeof(uint32_t) * (size_t)n));
+  hipError_t e;
+  if (h->ivf) {
+    hipLaunchKernelGGL(tags_to_scan_order_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tags_by_row_dev, h->row_ids, n, t);
+    e = hipGetLastError();
+  } else {
+    e = hipMemcpyAsync(t, tags_by_row_dev, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // the caller's array may go away after the call
+  if (e != hipSuccess) { hipFree(t); rihip_set_error("ip_index_set_tags: %s", hipGetErrorString(e)); return RIHIP_ERR_HIP; }
+  h->tags = t;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_has_tags(void* handle) { return handle && ((IpIndex*)handle)->tags ? 1 : 0; }
+
+extern "C" int rihip_ip_index_filtered_stats(void* handle, int64_t* out) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "ip_index_filtered_stats: bad arguments");
+  out[0] = h->filt_stats[0]; out[1] = h->filt_stats[1];
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_search_filtered(void* handle, const float* Q, int64_t nq, int k, const uint32_t* pred_dev,
+                                              int64_t pred_stride, float* out_scores, int64_t* out_rows, void* stream) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && h->X && h->N > 0, RIHIP_ERR_STATE, "ip_index_search_filtered: index is empty");
+  RIHIP_REQUIRE(h->tags, RIHIP_ERR_STATE, "ip_index_search_filtered: the index has no tags (rihip_ip_index_set_tags)");
+  RIHIP_REQUIRE(!h->pending.active, RIHIP_ERR_STATE, "ip_index_search_filtered: a deferred search is pending (rihip_ip_index_search_finish)");
+  RIHIP_REQUIRE(Q && pred_dev && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "ip_index_search_filtered: bad arguments");
+  RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "ip_index_search_filtered: pred_stride=%lld (0 or 3)", (long long)pred_stride);
+  RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "ip_index_search_filtered: k=%d outside [1,%d]", k, K_MAX);
+  if (h->du != h->d) {
+    RCCHK(h->qpad.reserve(nq * h->d));
+    RCCHK(pad_rows(Q, nq, h->du, h->d, h->qpad.p, (hipStream_t)stream));
+    Q = h->qpad.p;
+  }
+  RIHIP_REQUIRE((reinterpret_cast<uintptr_t>(Q) & 15) == 0, RIHIP_ERR_ARG, "ip_index_search_filtered: Q must be 16-byte aligned");
+  const int64_t CH = 4096;
+  for (int64_t q0 = 0; q0 < nq; q0 += CH) {
+    const int64_t n = (nq - q0 < CH) ? nq - q0 : CH;
+    const FiltCtx F{pred_dev + q0 * pred_stride, (int)pred_stride};
+    int rc = search_chunk(h, Q + q0 * h->d, n, k, out_scores + q0 * k, out_rows + q0 * k, (hipStream_t)stream, &F);
     if (rc) return rc;
   }
   return RIHIP_OK;

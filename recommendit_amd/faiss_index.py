@@ -11,6 +11,10 @@ layout is restated from faiss 1.7.x and unverifiable offline: parity unpinned, S
 the library's own, so the IVF list membership of an index TRAINED here differs from one trained by faiss; an index
 LOADED from a faiss file keeps faiss's centroids and lists.  Limits the reference (faiss) does not have: embed_dim <= 128
 (any width: rows are zero-padded to the 32/64/128 kernel width inside the handle), n_lists <= 2048, k <= 16384.
+
+Filtered retrieval (not in the reference; faiss has it as ``SearchParameters.sel``): ``set_item_tags`` gives every item a
+32-bit tag word and ``item_filter=(any_of, all_of, none_of)`` restricts a search to the items whose word passes, tested
+inside the index scan.
 """
 from __future__ import annotations
 
@@ -64,6 +68,64 @@ class _IndexHandle:
             pass
 
 
+def genre_tags(genre_matrix) -> np.ndarray:
+    """uint32 [n]: bit g of word i is set iff genre_matrix[i, g] > 0 (at most 32 columns; the reference's 18 genres take
+    bits 0-17 and leave bits 18-31 to the caller)"""
+    g = genre_matrix.detach().cpu().numpy() if isinstance(genre_matrix, torch.Tensor) else np.asarray(genre_matrix)
+    if g.ndim != 2 or g.shape[1] > 32:
+        raise ValueError(f"genre matrix must be [n, <=32], got {g.shape}")
+    bits = np.uint32(1) << np.arange(g.shape[1], dtype=np.uint32)
+    return ((g > 0).astype(np.uint32) * bits[None, :]).sum(axis=1, dtype=np.uint64).astype(np.uint32)
+
+
+def _word(v) -> int:
+    v = int(v)
+    if not -(1 << 31) <= v < (1 << 32):
+        raise ValueError(f"item_filter word {v} does not fit 32 bits")
+    return v & 0xFFFFFFFF
+
+
+def item_filter_words(item_filter, nq: int) -> np.ndarray:
+    """item_filter as uint32 [nq, 3] words (any_of, all_of, none_of): a 3-tuple of ints is shared by the batch, an
+    integer array or tensor [nq, 3] (or [3]) holds one predicate per query and is read as a bit pattern"""
+    if isinstance(item_filter, torch.Tensor):
+        item_filter = item_filter.detach().cpu().numpy()
+    if isinstance(item_filter, (tuple, list)) and len(item_filter) == 3 and all(np.ndim(v) == 0 for v in item_filter):
+        return np.tile(np.array([_word(v) for v in item_filter], dtype=np.uint32), (nq, 1))
+    a = np.asarray(item_filter)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"item_filter must hold integers, got {a.dtype}")
+    if a.shape == (3,):
+        a = np.tile(a, (nq, 1))
+    if a.shape != (nq, 3):
+        raise ValueError(f"item_filter must be a 3-tuple or [{nq}, 3], got {a.shape}")
+    if a.dtype.itemsize == 4:
+        return np.ascontiguousarray(a).view(np.uint32)
+    return np.array([[_word(v) for v in row] for row in a.tolist()], dtype=np.uint32).reshape(nq, 3)
+
+
+def _filter_device(item_filter, nq: int, device) -> Tuple[torch.Tensor, int]:
+    """-> (int32 device tensor of predicate words, stride between two queries' words: 3, or 0 = shared)"""
+    if isinstance(item_filter, torch.Tensor) and item_filter.is_cuda:
+        if item_filter.dtype != torch.int32 or tuple(item_filter.shape) != (nq, 3):
+            raise ValueError(f"a device item_filter must be int32 [{nq}, 3], got {item_filter.dtype} "
+                             f"{tuple(item_filter.shape)}")
+        return item_filter.contiguous(), 3
+    shared = isinstance(item_filter, (tuple, list)) and len(item_filter) == 3 and all(np.ndim(v) == 0 for v in item_filter)
+    w = item_filter_words(item_filter, 1 if shared else nq)
+    return torch.from_numpy(w.view(np.int32).copy()).to(device), 0 if shared else 3
+
+
+def _sub_filter(item_filter, sel: torch.Tensor):
+    """the predicates of the queries `sel` (a device index tensor) of a batch"""
+    if isinstance(item_filter, (tuple, list)):
+        return item_filter
+    if isinstance(item_filter, torch.Tensor):
+        return item_filter[sel.to(item_filter.device)]
+    a = np.asarray(item_filter)
+    return a if a.ndim == 1 else a[sel.cpu().numpy()]
+
+
 def _list_stats(sizes: np.ndarray) -> Dict:
     sizes = np.asarray(sizes, dtype=np.int64)
     n, tot = int(sizes.shape[0]), int(sizes.sum())
@@ -87,6 +149,8 @@ class FAISSIndex:
         self._item_ids_dev: Optional[torch.Tensor] = None
         self._deferred = False
         self._deficit: Optional[torch.Tensor] = None
+        self._tags: Optional[torch.Tensor] = None      # int32 bit patterns [ntotal] on the device, row order
+        self._pred_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}   # shared predicates already on the device
 
     @property
     def _item_id_to_faiss_idx(self) -> Dict[int, int]:
@@ -150,6 +214,7 @@ class FAISSIndex:
         L.check(lib.rihip_ip_index_set_nprobe(self.index._h, int(self.n_probe)), "ip_index_set_nprobe")
         self.item_ids = np.asarray(item_ids, dtype=np.int64)
         self._item_ids_dev = torch.from_numpy(self.item_ids).to(x_dev.device)
+        self._tags = None
         logger.info("Index built: %d vectors, %d lists, probe=%d", self.index.ntotal, self.n_lists, self.n_probe)
 
     # -- live catalogue (faiss add_with_ids / remove_ids; not in the reference, which rebuilds offline) ----------
@@ -158,7 +223,7 @@ class FAISSIndex:
     # in the state a from-scratch build of the final corpus with the same centroids would give.  Serving: an item id
     # outside the feature store's item table (a new item the store has not seen) is not an error in
     # rihip_rank_features_build -- it reads row 0 of the table, the reference's cold-start defaults.
-    def _apply_update(self, drop_ids, x_add: Optional[torch.Tensor], add_ids) -> Tuple[int, int]:
+    def _apply_update(self, drop_ids, x_add: Optional[torch.Tensor], add_ids, tags=None) -> Tuple[int, int]:
         if self.index is None:
             raise RuntimeError("Index not built.")
         if self.search_pending():
@@ -183,7 +248,12 @@ class FAISSIndex:
             if x_add.shape[0] != n_add:
                 raise ValueError(f"{x_add.shape[0]} embeddings for {n_add} item ids")
             x = x_add.to(device=dev, dtype=torch.float32).contiguous()
+        if tags is not None:
+            if self._tags is None:
+                raise ValueError("tags= on an index without tags: call set_item_tags() first")
+            tags = self._tags_dev(tags, n_add)
         n_old = self.index.ntotal
+        old_ids, old_tags = self._item_ids_dev, self._tags
         out = torch.empty(n_old + n_add, dtype=torch.int64, device=dev)
         n_total, n_dropped, bad_id, bad_kind = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
         rc = L.lib().rihip_ip_index_update(self.index._h, self._item_ids_dev.data_ptr(), L.ptr(drop) if n_drop else None,
@@ -198,6 +268,18 @@ class FAISSIndex:
         self._item_ids_dev = out[:n_total.value]
         self.item_ids = self._item_ids_dev.cpu().numpy()
         self._id_map_stale = True
+        if old_tags is not None:
+            # the update dropped the handle's tags (a new row order): surviving rows keep theirs in their new places, the
+            # appended rows take `tags`, else the word their id carried before the call, else 0
+            keep = torch.ones(n_old, dtype=torch.bool, device=dev) if n_drop == 0 else ~torch.isin(old_ids, drop)
+            if tags is None and n_add:
+                srt, order = torch.sort(old_ids)
+                pos = torch.searchsorted(srt, add).clamp(max=n_old - 1)
+                tags = torch.where(srt[pos] == add, old_tags[order[pos]], torch.zeros_like(old_tags[:1]))
+            parts = [old_tags[keep]] + ([tags] if n_add else [])
+            self._tags = torch.cat(parts).contiguous()
+            assert self._tags.shape[0] == n_total.value
+            self._push_tags()
         return int(n_dropped.value), n_add
 
     def _normalised(self, embeddings: np.ndarray) -> torch.Tensor:
@@ -209,29 +291,98 @@ class FAISSIndex:
         norms = np.linalg.norm(embeddings, axis=1, keepdims=True)
         return torch.from_numpy(np.ascontiguousarray(embeddings / np.maximum(norms, 1e-8), dtype=np.float32)).to(L.device())
 
-    def add_items(self, embeddings: np.ndarray, item_ids) -> int:
+    def add_items(self, embeddings: np.ndarray, item_ids, tags=None) -> int:
         """Append f32 [n, embed_dim] rows (normalised as build_ivf_index does) as rows N .. N+n-1 with these ids; -> n.
-        ValueError for an id that is already stored or repeated."""
+        ValueError for an id that is already stored or repeated.  tags: uint32 [n] tag words of the new rows of a tagged
+        index (0 when omitted)."""
         if self.index is None:
             raise RuntimeError("Index not built.")
-        return self.add_items_device(self._normalised(embeddings), item_ids)
+        return self.add_items_device(self._normalised(embeddings), item_ids, tags=tags)
 
-    def add_items_device(self, x_dev: torch.Tensor, item_ids) -> int:
+    def add_items_device(self, x_dev: torch.Tensor, item_ids, tags=None) -> int:
         """add_items for rows that are already normalised and on the device (as build_from_device)"""
-        return self._apply_update(None, x_dev, item_ids)[1]
+        return self._apply_update(None, x_dev, item_ids, tags)[1]
 
     def remove_items(self, item_ids) -> int:
         """Remove the stored items with these ids (ids that are not stored are ignored, as faiss remove_ids does);
         surviving rows keep their relative order and are renumbered densely.  -> number of items removed"""
         return self._apply_update(item_ids, None, None)[0]
 
-    def update_items(self, embeddings: np.ndarray, item_ids) -> Tuple[int, int]:
+    def update_items(self, embeddings: np.ndarray, item_ids, tags=None) -> Tuple[int, int]:
         """Upsert in one repack: a stored id is dropped and its new vector appended, an unknown id is appended; the
-        result is that of remove_items(ids) followed by add_items(embeddings, ids).  -> (replaced, added)"""
+        result is that of remove_items(ids) followed by add_items(embeddings, ids).  -> (replaced, added).  tags: uint32
+        [n] tag words of these ids on a tagged index; omitted, a replaced id keeps its word and a new id gets 0."""
         if self.index is None:
             raise RuntimeError("Index not built.")
-        replaced, n = self._apply_update(item_ids, self._normalised(embeddings), item_ids)
+        replaced, n = self._apply_update(item_ids, self._normalised(embeddings), item_ids, tags)
         return replaced, n - replaced
+
+    # -- item tags (filtered retrieval; not in the reference) ------------------------------------------------------
+    def _tags_dev(self, tags, n: int) -> torch.Tensor:
+        """uint32 / int32 words [n] (host array or tensor) -> int32 bit patterns on the index's device"""
+        if isinstance(tags, torch.Tensor):
+            if tags.dtype != torch.int32:
+                tags = torch.from_numpy(tags.detach().cpu().numpy().astype(np.uint32).view(np.int32))
+        else:
+            a = np.asarray(tags)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"tags must be uint32 words, got {a.dtype}")
+            if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 32)):
+                raise ValueError("tags must fit 32 bits")
+            tags = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
+        tags = tags.reshape(-1)
+        if tags.shape[0] != n:
+            raise ValueError(f"{tags.shape[0]} tag words for {n} items")
+        return tags.to(self._item_ids_dev.device).contiguous()
+
+    def _push_tags(self) -> None:
+        L.check(L.lib().rihip_ip_index_set_tags(self.index._h, None if self._tags is None else self._tags.data_ptr(),
+                                                L.stream_ptr()), "ip_index_set_tags")
+
+    def set_item_tags(self, tags, item_ids=None) -> None:
+        """Give every stored item a 32-bit tag word (bits 0-17: the reference's 18 genres by convention, see
+        genre_tags; bits 18-31: the caller's).  tags uint32 [ntotal] in row order; with item_ids, tags[i] belongs to
+        item_ids[i] and items that are not named keep their word (0 on an index that had none).  ValueError for an id
+        that is not stored."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        if self.search_pending():
+            raise RuntimeError("a deferred search is pending: call finish_search() before changing the tags")
+        n = self.index.ntotal
+        if item_ids is None:
+            self._tags = self._tags_dev(tags, n)
+        else:
+            ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+            t = self._tags_dev(tags, ids.shape[0])
+            order = np.argsort(self.item_ids, kind="stable")
+            pos = np.minimum(np.searchsorted(self.item_ids[order], ids), n - 1)
+            rows = order[pos]
+            missing = self.item_ids[rows] != ids
+            if missing.any():
+                raise ValueError(f"item id {int(ids[missing][0])} is not stored")
+            cur = self._tags.clone() if self._tags is not None else torch.zeros(n, dtype=torch.int32, device=t.device)
+            cur[torch.from_numpy(rows).to(t.device)] = t
+            self._tags = cur
+        self._push_tags()
+
+    def item_tags(self) -> Optional[np.ndarray]:
+        """uint32 [ntotal] tag words in row order (None without tags)"""
+        return None if self._tags is None else self._tags.cpu().numpy().view(np.uint32)
+
+    def clear_item_tags(self) -> None:
+        self._tags = None
+        if self.index is not None:
+            self._push_tags()
+
+    @property
+    def has_item_tags(self) -> bool:
+        return self.index is not None and bool(L.lib().rihip_ip_index_has_tags(self.index._h))
+
+    def filtered_stats(self) -> Tuple[int, int]:
+        """(queries searched with an item_filter, of those re-done by the exact fallback) since the handle was made"""
+        out = (C.c_int64 * 2)()
+        L.check(L.lib().rihip_ip_index_filtered_stats(self.index._h, out), "ip_index_filtered_stats")
+        return int(out[0]), int(out[1])
 
     def list_stats(self) -> Dict:
         """IVF list sizes: n_lists, min, max, mean, empty, imbalance = n_lists * sum(len^2) / sum(len)^2 (faiss
@@ -274,11 +425,25 @@ class FAISSIndex:
         return out
 
     # -- search (faiss_index.py:88-153) -------------------------------------------------------
-    def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool = False, item_filter=None
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
         """q_dev: normalised f32 [nq,d] on device -> (scores [nq,k], rows [nq,k]) on device; item_ids=True: the rows
-        come back as item ids (faiss_index.py:123,148-152), mapped inside the search's last kernel."""
+        come back as item ids (faiss_index.py:123,148-152), mapped inside the search's last kernel.  item_filter: only
+        rows whose tag word passes (batch_search_device)."""
         lib = L.lib()
         nq = q_dev.shape[0]
+        pred = None
+        if item_filter is not None:
+            if self._tags is None:
+                raise ValueError("item_filter needs item tags: call set_item_tags() first")
+            if isinstance(item_filter, tuple) and item_filter in self._pred_cache:
+                pred, stride = self._pred_cache[item_filter], 0      # (no host-to-device copy per request)
+            else:
+                pred, stride = _filter_device(item_filter, nq, q_dev.device)
+                if stride == 0 and isinstance(item_filter, tuple) and len(self._pred_cache) < 1024:
+                    self._pred_cache[item_filter] = pred
+            if self.search_pending():
+                raise RuntimeError("a deferred search is pending: call finish_search() before a filtered search")
         L.check(lib.rihip_ip_index_set_id_map(self.index._h, self._item_ids_dev.data_ptr() if item_ids else None),
                 "ip_index_set_id_map")
         if k > int(lib.rihip_ip_index_max_k()):
@@ -286,6 +451,11 @@ class FAISSIndex:
                              "the reference (faiss) has no such limit -- see INTEGRATION.md")
         scores = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=q_dev.device)
+        if pred is not None:
+            L.check(lib.rihip_ip_index_search_filtered(self.index._h, q_dev.data_ptr(), nq, k, pred.data_ptr(), stride,
+                                                       scores.data_ptr(), rows.data_ptr(), L.stream_ptr()),
+                    "ip_index_search_filtered")
+            return scores, rows
         L.check(lib.rihip_ip_index_search(self.index._h, q_dev.data_ptr(), nq, k, scores.data_ptr(), rows.data_ptr(),
                                           L.stream_ptr()), "ip_index_search")
         return scores, rows
@@ -332,7 +502,8 @@ class FAISSIndex:
         the plan of seen.py chose k_eff"""
         return 0 if self._deficit is None else int(self._deficit.item())
 
-    def _search_excluding(self, q: torch.Tensor, k: int, seen, user_ids) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _search_excluding(self, q: torch.Tensor, k: int, seen, user_ids, item_filter=None
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
         """q normalised f32 [nq,d] on device -> (scores, item ids) [nq,k] without each query's excluded items.
         user_ids: host sequence (queries are grouped by how far they have to over-fetch, one search per group), a
         device tensor (one group at the store's longest list) or None (list q of `seen` belongs to query q)."""
@@ -354,7 +525,7 @@ class FAISSIndex:
             nothing = not extra.any()
         if len(plan) == 1:
             k_eff = plan[0][0]
-            s, c = self._search_device(q, k_eff, item_ids=True)
+            s, c = self._search_device(q, k_eff, item_ids=True, item_filter=item_filter)
             if nothing:
                 return s, c
             scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
@@ -366,12 +537,15 @@ class FAISSIndex:
         for k_eff, pos in plan:
             slot = torch.from_numpy(pos.astype(np.int32)).to(q.device)
             sel = slot.to(torch.long)
-            s, c = self._search_device(q[sel].contiguous(), k_eff, item_ids=True)
+            s, c = self._search_device(q[sel].contiguous(), k_eff, item_ids=True,
+                                       item_filter=None if item_filter is None else _sub_filter(item_filter, sel))
             self.filter_excluded(s, c, k, seen, sel if uid is None else uid[sel], scores, ids, slot)
         return scores, ids
 
-    def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None) -> Tuple[np.ndarray, np.ndarray]:
-        """exclude_items (not in the reference): item ids that must not be returned"""
+    def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None, item_filter=None
+               ) -> Tuple[np.ndarray, np.ndarray]:
+        """exclude_items (not in the reference): item ids that must not be returned; item_filter (not in the reference):
+        (any_of, all_of, none_of) over the items' tag words, as in batch_search_device"""
         if self.index is None:
             raise RuntimeError("Index not built. Call build_ivf_index() first.")
         query = np.atleast_2d(query_vector).astype(np.float32)
@@ -383,10 +557,10 @@ class FAISSIndex:
             from .seen import SeenItems
             ex = np.asarray(exclude_items, dtype=np.int64).reshape(-1)
             scores, ids = self._search_excluding(q_dev, k, SeenItems.from_pairs(np.zeros(ex.shape[0], np.int64), ex, 1),
-                                                 None)
+                                                 None, item_filter)
             distances, ids = scores[0].cpu().numpy(), ids[0].cpu().numpy()
             return distances[ids >= 0], ids[ids >= 0]
-        scores, rows = self._search_device(q_dev, k)
+        scores, rows = self._search_device(q_dev, k, item_filter=item_filter)
         distances = scores[0].cpu().numpy()
         faiss_indices = rows[0].cpu().numpy()
         valid_mask = faiss_indices >= 0
@@ -394,9 +568,9 @@ class FAISSIndex:
         faiss_indices = faiss_indices[valid_mask]
         return distances, self.item_ids[faiss_indices]
 
-    def batch_search(self, query_vectors: np.ndarray, k: int = 500, exclude=None, user_ids=None
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500, exclude=None, user_ids=None, item_filter=None
                      ) -> Tuple[np.ndarray, np.ndarray]:
-        """exclude / user_ids (not in the reference): as in batch_search_device"""
+        """exclude / user_ids / item_filter (not in the reference): as in batch_search_device"""
         if self.index is None:
             raise RuntimeError("Index not built.")
         queries = query_vectors.astype(np.float32)
@@ -405,9 +579,9 @@ class FAISSIndex:
         k = min(k, self.index.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
         if exclude is not None:
-            scores, rows = self._search_excluding(q_dev, k, exclude, self._require_user_ids(user_ids))
+            scores, rows = self._search_excluding(q_dev, k, exclude, self._require_user_ids(user_ids), item_filter)
         else:
-            scores, rows = self._search_device(q_dev, k, item_ids=True)
+            scores, rows = self._search_device(q_dev, k, item_ids=True, item_filter=item_filter)
         return scores.cpu().numpy(), rows.cpu().numpy()
 
     @staticmethod
@@ -417,7 +591,7 @@ class FAISSIndex:
         return user_ids
 
     def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, exclude=None,
-                            user_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                            user_ids=None, item_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-resident batch_search (not in the reference): queries f32 [nq,d] on the HIP device;
         returns (scores, item_ids) on device, -1 padded.  This is the QPS benchmark entry.
 
@@ -427,7 +601,15 @@ class FAISSIndex:
         (seen.plan_overfetch); as a device tensor: one search at the store's longest list.  ValueError when k plus a
         user's list exceeds the 16384-candidate limit of the search on a corpus larger than that.
         Under set_deferred_check(True) the filtered result is a consumer of the search like any other: when
-        finish_search() returns > 0, call this again (it then runs as one group: one search, one finish)."""
+        finish_search() returns > 0, call this again (it then runs as one group: one search, one finish).
+
+        item_filter (needs set_item_tags): a 3-tuple of ints (any_of, all_of, none_of) shared by the batch, a uint32
+        array [nq,3], or an int32 device tensor [nq,3] read as a bit pattern.  Item i passes iff (any_of == 0 or
+        tag[i] & any_of) and tag[i] & all_of == all_of and tag[i] & none_of == 0; the result is the exact top k of the
+        passing items (IVF: of the probed lists), -1 padded when fewer pass; (0,0,0) equals the plain search.  The
+        predicate is tested inside the scan, so a filter that removes 99.9 % of the corpus needs no over-fetch.  With
+        exclude the result is filter AND not-seen.  A filtered search always synchronises (no deferred check), and on
+        a large flat index it takes the all-f32 scan.  ValueError without tags or on a bad shape."""
         if self.index is None:
             raise RuntimeError("Index not built.")
         q = queries.to(dtype=torch.float32).contiguous()
@@ -435,8 +617,8 @@ class FAISSIndex:
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
         k = min(k, self.index.ntotal)
         if exclude is not None:
-            return self._search_excluding(q, k, exclude, self._require_user_ids(user_ids))
-        return self._search_device(q, k, item_ids=True)
+            return self._search_excluding(q, k, exclude, self._require_user_ids(user_ids), item_filter)
+        return self._search_device(q, k, item_ids=True, item_filter=item_filter)
 
     # -- persistence (faiss_index.py:159-205) -------------------------------------------------
     def save(self, path: str, format: str = "rihip") -> None:
@@ -455,17 +637,17 @@ class FAISSIndex:
         else:
             raise ValueError(f"unknown index file format {format!r}")
         meta_path = save_path.with_suffix(".meta.pkl")
+        meta = {
+            "item_ids": self.item_ids,
+            "item_id_to_faiss_idx": self._item_id_to_faiss_idx,
+            "embed_dim": self.embed_dim,
+            "n_lists": self.n_lists,
+            "n_probe": self.n_probe,
+        }
+        if self._tags is not None:   # (only then: an untagged index writes the sidecar it always wrote)
+            meta["item_tags"] = self.item_tags()
         with open(meta_path, "wb") as f:
-            pickle.dump(
-                {
-                    "item_ids": self.item_ids,
-                    "item_id_to_faiss_idx": self._item_id_to_faiss_idx,
-                    "embed_dim": self.embed_dim,
-                    "n_lists": self.n_lists,
-                    "n_probe": self.n_probe,
-                },
-                f,
-            )
+            pickle.dump(meta, f)
         logger.info("Saved index to %s (meta: %s)", save_path, meta_path)
 
     @classmethod
@@ -508,6 +690,8 @@ class FAISSIndex:
                     if meta.get("n_probe") is None and f.get("nprobe"):
                         obj.set_n_probe(int(f["nprobe"]))
             obj._item_id_to_faiss_idx = meta["item_id_to_faiss_idx"]
+            if meta.get("item_tags") is not None:
+                obj.set_item_tags(meta["item_tags"])
             return obj
         h = C.c_void_p()
         L.check(L.lib().rihip_ip_index_load(str(load_path).encode(), C.byref(h)), "ip_index_load")
@@ -517,6 +701,8 @@ class FAISSIndex:
         obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())
         obj._item_id_to_faiss_idx = meta["item_id_to_faiss_idx"]
         obj.exact = not obj.index.is_ivf
+        if meta.get("item_tags") is not None:
+            obj.set_item_tags(meta["item_tags"])
         return obj
 
     # -- utilities (faiss_index.py:211-228) ---------------------------------------------------

@@ -134,6 +134,16 @@ class GpuFeatureStore:
         st.load_all_features(udf, idf)
         return st
 
+    def item_genre_tags(self, item_ids) -> np.ndarray:
+        """uint32 [n] tag words for FAISSIndex.set_item_tags: bit g is set iff item_ids[i]'s genre vector in the item
+        table has genre g (an id outside the table gets 0)"""
+        from .faiss_index import genre_tags
+        ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+        ok = (ids >= 0) & (ids < self.item.shape[0])
+        tags = np.zeros(ids.shape[0], dtype=np.uint32)
+        tags[ok] = genre_tags(self.item[ids[ok], 5:5 + N_GENRES])
+        return tags
+
     def device_tables(self) -> Tuple[torch.Tensor, torch.Tensor]:
         if self._dev is None:
             dev = L.device()
@@ -197,14 +207,36 @@ class GpuRecommendationPipeline:
 
     @torch.no_grad()
     def recommend_batch(self, user_ids, k: Optional[int] = None, graph: bool = False,
-                        exclude_seen: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                        exclude_seen: Optional[bool] = None, item_filter=None
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """recommendations of a batch of users (outputs: _recommend).  exclude_seen: drop each user's items of the
         attached seen store from retrieval; None = yes iff a store is attached.  With host ids the batch is served in
         groups by how far each user has to over-fetch (seen.plan_overfetch: one heavy user does not slow the rest), one
-        run of the chain per group; graph=True and device ids run as one group at the store's longest list."""
+        run of the chain per group; graph=True and device ids run as one group at the store's longest list.
+
+        item_filter (not in the reference; the index needs set_item_tags): (any_of, all_of, none_of) over the items' tag
+        words, shared by the batch or one row per user (FAISSIndex.batch_search_device).  Retrieval then returns only
+        passing items, -1 padded when fewer than top_k_candidates pass; features, ranker and top-k run as on any short
+        retrieval result, and with a seen store the candidates are filter AND not-seen (one group at the batch's
+        longest seen list).  The filtered search synchronises the stream for its exactness check, so it cannot be
+        captured: graph=True with a filter raises ValueError."""
         k = k or self.top_k_results
         if exclude_seen and self.seen is None:
             raise ValueError("exclude_seen=True without a seen store (set_seen)")
+        if item_filter is not None:
+            if graph:
+                raise ValueError("graph=True cannot serve an item_filter: the filtered search synchronises the stream")
+            k_eff = None
+            if self.seen is not None and exclude_seen is not False:
+                ntotal = self.index.index.ntotal
+                if isinstance(user_ids, torch.Tensor) and user_ids.is_cuda:
+                    most = self.seen.max_count
+                else:
+                    host = np.asarray(user_ids.tolist() if isinstance(user_ids, torch.Tensor) else user_ids, dtype=np.int64)
+                    most = int(self.seen.counts_of(host).max()) if host.size else 0
+                if most:
+                    k_eff = overfetch_k(min(self.top_k_candidates, ntotal), most, ntotal, int(L.lib().rihip_ip_index_max_k()))
+            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff, item_filter=item_filter)
         if self.seen is None or exclude_seen is False:
             return self._recommend(user_ids, k, graph, None)
         ntotal = self.index.index.ntotal
@@ -345,12 +377,16 @@ class GpuRecommendationPipeline:
         # a replay runs no host code: the failure count of its deferred search is read here (one synchronisation)
         return out, (self.index.last_fail_count() if deferred else 0)
 
-    def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None
+    def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None, item_filter=None
                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
-        rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True)
+        if item_filter is None:
+            rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True)
+        else:
+            rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True,
+                                                      item_filter=item_filter)
         nq, kc = cand.shape
         if k_eff is not None:       # over-fetched: keep each user's first top_k_candidates unseen candidates
             kc = min(self.top_k_candidates, self.index.index.ntotal)
@@ -441,8 +477,9 @@ class GpuRecommendationPipeline:
         return S.detect_training_serving_skew_device(train_features, serving, threshold, numeric_cols, columns)
 
     def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False,
-                            exclude_seen: Optional[bool] = None) -> List[Dict[str, Any]]:
-        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen)
+                            exclude_seen: Optional[bool] = None, item_filter=None) -> List[Dict[str, Any]]:
+        """item_filter: as in recommend_batch (graph=True with a filter raises ValueError)"""
+        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen, item_filter=item_filter)
         out = []
         for rank, (i, s, r) in enumerate(zip(ids[0].tolist(), sc[0].tolist(), rs[0].tolist()), start=1):
             if i >= 0:
