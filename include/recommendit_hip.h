@@ -415,12 +415,15 @@ int rihip_ip_index_filtered_stats(void* handle, int64_t* out);
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict
  * (ranker.py:174): raw score = sum over trees of the reached leaf value, float64.
- * X device f32 [n, ldx]; out device f64 [n]. */
+ * X device f32 [n, ldx]; out device f64 [n].
+ * predict_path names the kernel rihip_gbdt_predict launches for this handle (chosen when the model is parsed):
+ * 0 general (any forest), 1 compact nodes with missing types, 2 compact nodes without, 3 walk-ordered records. */
 int rihip_gbdt_load_text(const char* path, void** handle);
 int rihip_gbdt_create_from_text(const char* text, int64_t len, void** handle);
 int rihip_gbdt_destroy(void* handle);
 int rihip_gbdt_num_trees(void* handle);
 int rihip_gbdt_num_features(void* handle);
+int rihip_gbdt_predict_path(void* handle);
 int64_t rihip_gbdt_feature_names(void* handle, char* buf, int64_t buf_len); /* '\n'-joined, host */
 int rihip_gbdt_feature_importance(void* handle, int importance_type, double* out_host);
 int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int ldx, double* out, void* stream);
@@ -439,7 +442,9 @@ int rihip_rank_features_build(const double* user_tab, int64_t n_user_rows, const
                               int64_t n_item_rows, const int64_t* user_ids, const int64_t* cand_ids, int64_t nq,
                               int kc, const int* col_map, int nf, float* X, void* stream);
 /* nlargest(k, "score") of every request (src/serving/recommender.py:346): scores f64 [nq,kc] (ranker output), cand i64
- * [nq,kc] (-1 = padding, ranked last), retrieval_scores f32 [nq,kc]; outputs [nq,k], ties keep the retrieval order. */
+ * [nq,kc] (-1 = padding, ranked last), retrieval_scores f32 [nq,kc]; outputs [nq,k], ties keep the retrieval order
+ * (-0.0 ties with +0.0 and comes back with its sign; NaN scores rank after every number, before padding; outputs past
+ * the kc candidates are -1 / -inf). */
 int rihip_rank_topk(const double* scores, const int64_t* cand, const float* retrieval_scores, int64_t nq, int kc, int k,
                     int64_t* out_ids, double* out_scores, float* out_retrieval_scores, void* stream);
 

@@ -102,14 +102,18 @@ def _decide_left(fval: np.ndarray, t: Dict, node: int) -> np.ndarray:
     return np.where(is_missing, default_left, le)
 
 
-def predict_raw(model: Dict, X: np.ndarray) -> np.ndarray:
-    """Sum over trees of the reached leaf value -> float64[n] (Booster.predict raw)."""
+def predict_raw(model: Dict, X: np.ndarray, return_abs: bool = False):
+    """Sum over trees of the reached leaf value -> float64[n] (Booster.predict raw).  ``return_abs`` also returns the
+    sum of the |leaf values| reached by every row, before any averaging (the scale of a summation-order error bound)."""
     X = np.asarray(X, dtype=np.float32).astype(np.float64)  # ranker.py:173 casts to f32 first
     n = X.shape[0]
     out = np.zeros(n, dtype=np.float64)
+    out_abs = np.zeros(n, dtype=np.float64)
     for t in model["trees"]:
         if t["num_leaves"] <= 1:
-            out += t["leaf_value"][0] if t["leaf_value"].size else 0.0
+            v = t["leaf_value"][0] if t["leaf_value"].size else 0.0
+            out += v
+            out_abs += abs(v)
             continue
         node = np.zeros(n, dtype=np.int64)
         active = np.ones(n, dtype=bool)
@@ -120,16 +124,20 @@ def predict_raw(model: Dict, X: np.ndarray) -> np.ndarray:
                 node[sel] = np.where(left, t["left_child"][nd], t["right_child"][nd])
             active = node >= 0
         out += t["leaf_value"][~node]
+        out_abs += np.abs(t["leaf_value"][~node])
     if model.get("average_output") and model["trees"]:
         out /= len(model["trees"])
-    return out
+    return (out, out_abs) if return_abs else out
 
 
-def write_text_model(model: Dict) -> str:
-    """Emit a LightGBM-format text model (used to synthesise bench/test forests)."""
+def write_text_model(model: Dict, average_output=None) -> str:
+    """Emit a LightGBM-format text model (used to synthesise bench/test forests).  ``average_output`` (default: the
+    model's own flag) adds the bare header line GBDT::SaveModelToString writes for averaging boosters (rf)."""
     names = model["feature_names"]
+    if average_output is None:
+        average_output = bool(model.get("average_output", False))
     hdr = ["tree", "version=v4", "num_class=1", "num_tree_per_iteration=1", "label_index=0",
-           f"max_feature_idx={len(names) - 1}", "objective=lambdarank",
+           f"max_feature_idx={len(names) - 1}", "objective=lambdarank"] + (["average_output"] if average_output else []) + [
            "feature_names=" + " ".join(names),
            "feature_infos=" + " ".join(["[-1e30:1e30]"] * len(names)), "tree_sizes=0", ""]
     body = []
@@ -194,3 +202,51 @@ def random_forest_model(n_trees: int, n_leaves: int, n_features: int, seed: int 
                           leaf_value=rng.randn(nl) * 0.05, shrinkage=0.05))
     return dict(feature_names=names, max_feature_idx=n_features - 1, num_class=1,
                 num_tree_per_iteration=1, average_output=False, objective="lambdarank", trees=trees)
+
+
+# ---- which kernel serves a forest: host restatement of the chunk and record arithmetic of csrc/gbdt.hip ----
+N8_CAP, L8_CAP, T8_CAP, R_CAP = 2048, 2112, 32, 4096        # compact nodes / leaves / trees / walk records per chunk
+NODE_CAP, LEAF_CAP, T_CAP = 1280, 1536, 16                  # general kernel: nodes / leaves / trees per LDS chunk
+PATH_GENERAL, PATH_COMPACT_MISSING, PATH_COMPACT_SIMPLE, PATH_WALK = 0, 1, 2, 3
+
+
+def _tree_sizes(t: Dict):
+    nl = max(int(t["num_leaves"]), 1)
+    return (nl - 1 if nl > 1 else 0), nl
+
+
+def _chunks(model: Dict, node_cap: int, leaf_cap: int, tree_cap: int) -> List[int]:
+    starts, cn, cl, ct = [0], 0, 0, 0
+    for i, t in enumerate(model["trees"]):
+        tn, tl = _tree_sizes(t)
+        if ct > 0 and (cn + tn > node_cap or cl + tl > leaf_cap or ct >= tree_cap):
+            starts.append(i)
+            cn = cl = ct = 0
+        cn, cl, ct = cn + tn, cl + tl, ct + 1
+    return starts + [len(model["trees"])]
+
+
+def predict_plan(model: Dict) -> Dict:
+    """{"path", "chunks" (tree starts of the chunks that path uses), "records" (walk records per compact chunk)} as
+    rihip_gbdt_create_from_text decides them: the general kernel unless the forest is all-numerical with at most 127
+    internal nodes per tree and at least one split; then compact nodes, and -- if no split has a missing type -- walk
+    records when every chunk's breadth-first records (2 per tree root + 2 per internal node) fit R_CAP."""
+    trees = model["trees"]
+    general = dict(path=PATH_GENERAL, chunks=_chunks(model, NODE_CAP, LEAF_CAP, T_CAP), records=[])
+    n_nodes = sum(_tree_sizes(t)[0] for t in trees)
+    if not trees or n_nodes == 0 or len(model["feature_names"]) > 255:
+        return general
+    for t in trees:
+        tn, tl = _tree_sizes(t)
+        if t.get("num_cat", 0) > 0 or tn > 127 or tl > 128:
+            return general
+        if tn and (np.asarray(t["decision_type"])[:tn] & 1).any():
+            return general
+    chunks = _chunks(model, N8_CAP, L8_CAP, T8_CAP)
+    simple = all(not ((np.asarray(t["decision_type"])[:_tree_sizes(t)[0]] >> 2) & 3).any()
+                 for t in trees if _tree_sizes(t)[0])
+    records = [sum(2 + 2 * _tree_sizes(t)[0] for t in trees[a:b]) for a, b in zip(chunks[:-1], chunks[1:])]
+    path = PATH_COMPACT_MISSING
+    if simple:
+        path = PATH_WALK if all(r <= R_CAP for r in records) else PATH_COMPACT_SIMPLE
+    return dict(path=path, chunks=chunks, records=records)

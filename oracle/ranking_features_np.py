@@ -61,3 +61,53 @@ def feature_matrix(cols: Dict[str, np.ndarray], feature_names: List[str]) -> np.
         if name in cols:
             X[:, j] = cols[name]
     return X.astype(np.float32)
+
+
+# ---- the same glue over feature tables, vectorised (reference of the device kernels) ----
+USER_WIDTH, ITEM_WIDTH = len(USER_SCALARS) + N_GENRES, len(ITEM_SCALARS) + N_GENRES
+
+
+def canonical_matrix(user_rows: np.ndarray, item_rows: np.ndarray) -> np.ndarray:
+    """float64 [n, 50] in feature_columns() order from user rows [n, 24] (the 6 scalars of USER_SCALARS, then
+    genre_pref[18]) and item rows [n, 23] (the 5 scalars of ITEM_SCALARS, then genre_vector[18]).  The same float64
+    operations as build_ranking_features row by row; genre_affinity accumulates genre by genre, left to right, from
+    Python's sum() start value 0."""
+    u = np.asarray(user_rows, dtype=np.float64)
+    it = np.asarray(item_rows, dtype=np.float64)
+    n, nu, ni = u.shape[0], len(USER_SCALARS), len(ITEM_SCALARS)
+    out = np.empty((n, 14 + 2 * N_GENRES), dtype=np.float64)
+    out[:, :nu] = u[:, :nu]
+    out[:, nu:nu + ni] = it[:, :ni]
+    out[:, 11] = u[:, 0] - it[:, 0]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        out[:, 12] = u[:, 1] / (it[:, 1] + 1e-8)
+        aff = np.zeros(n, dtype=np.float64)
+        for g in range(N_GENRES):
+            aff = aff + u[:, nu + g] * it[:, ni + g]
+    out[:, 13] = aff
+    out[:, 14:14 + N_GENRES] = u[:, nu:]
+    out[:, 14 + N_GENRES:] = it[:, ni:]
+    return out
+
+
+def table_feature_matrix(user_tab: np.ndarray, item_tab: np.ndarray, user_ids: np.ndarray, cand_ids: np.ndarray,
+                         col_map: np.ndarray) -> np.ndarray:
+    """float32 [nq * kc, nf]: what the serving chain feeds the ranker for cand_ids [nq, kc] of users user_ids [nq].
+    Row 0 of either table holds the reference's defaults: a user id outside [0, n_user_rows) and an item id at or above
+    n_item_rows read it (an entity the feature store does not know); a negative candidate id is retrieval padding and
+    gives a row of zeros.  col_map[j] is the canonical column of ranker feature j, -1 for a column the pipeline does not
+    produce (0.0, recommender.py:334-336).  One cast to float32 at the end (ranker.py:173)."""
+    user_tab, item_tab = np.asarray(user_tab, np.float64), np.asarray(item_tab, np.float64)
+    cand = np.asarray(cand_ids, dtype=np.int64)
+    nq, kc = cand.shape
+    uid = np.repeat(np.asarray(user_ids, dtype=np.int64), kc)
+    iid = cand.reshape(-1)
+    pad = iid < 0
+    uid = np.where((uid < 0) | (uid >= user_tab.shape[0]), 0, uid)
+    iid = np.where(pad | (iid >= item_tab.shape[0]), 0, iid)
+    canon = canonical_matrix(user_tab[uid], item_tab[iid])
+    cm = np.asarray(col_map, dtype=np.int64)
+    X = np.where(cm[None, :] >= 0, canon[:, np.where(cm >= 0, cm, 0)], 0.0)
+    X[pad] = 0.0
+    with np.errstate(over="ignore"):
+        return X.astype(np.float32)

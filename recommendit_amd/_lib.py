@@ -122,6 +122,7 @@ SIGNATURES = {
     "rihip_gbdt_destroy": (C.c_int, [vp]),
     "rihip_gbdt_num_trees": (C.c_int, [vp]),
     "rihip_gbdt_num_features": (C.c_int, [vp]),
+    "rihip_gbdt_predict_path": (C.c_int, [vp]),
     "rihip_gbdt_feature_names": (c_i64, [vp, C.c_char_p, c_i64]),
     "rihip_gbdt_feature_importance": (C.c_int, [vp, C.c_int, vp]),
     "rihip_gbdt_predict": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp]),

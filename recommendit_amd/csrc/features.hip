@@ -22,6 +22,9 @@ __device__ __forceinline__ double canon_feature(const double* __restrict__ u, co
   if (c == 11) return u[0] - it[0];             // rating_diff
   if (c == 12) return u[1] / (it[1] + 1e-8);    // user_item_popularity_ratio
   if (c == 13) {                                // genre_affinity: left-to-right sum like Python's sum()
+    // every product rounds before it is added, as in Python: contracted into v_fma_f64 the sum differs from the wave
+    // kernel's (and the reference's) in the last bit, which the cast to float32 can carry into the result
+#pragma clang fp contract(off)
     double s = 0.0;
 #pragma unroll
     for (int g = 0; g < NG; ++g) s += u[6 + g] * it[5 + g];
@@ -120,6 +123,7 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const double* __restrict
       const bool real = cand[q * kc + i] >= 0;
       const double v = real ? scores[q * kc + i] : -INFINITY;
       unsigned long long u = (unsigned long long)__double_as_longlong(v);
+      if (v == 0.0) u = 0ull;   // -0.0 == +0.0 for nlargest: both zeros share a key and the retrieval position decides
       kk = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
       // padded candidates last (key 1), NaN scores just before them (key 2: DataFrame.nlargest never ranks a NaN above
       // a number; a positive NaN would otherwise order above +inf), every number above both (key(-inf) = 2^52 - 1)

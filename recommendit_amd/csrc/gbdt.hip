@@ -283,6 +283,13 @@ struct WalkArgs {
 // LDS bound it to 2 workgroups per CU, i.e. 8 waves per CU with 4-wave workgroups -- too few for a walk that waits on
 // LDS 60 % of the time)
 constexpr int WALK_NW = 16;
+// A leaf record's "feature offset" is 4 * leaf <= 508 and the lane adds 4 * lane <= 252, so every walk step reads inside
+// the first 3 feature rows (768 bytes) of the tile: the tile is never sized for fewer, whatever the model has.
+constexpr int WALK_F_MIN = 3;
+static size_t walk_lds_bytes(int n_features) {
+  const int f = n_features < WALK_F_MIN ? WALK_F_MIN : n_features;
+  return sizeof(uint2) * R_CAP + sizeof(double) * (L8_CAP + WALK_NW * 64) + sizeof(float) * 64 * (size_t)f;
+}
 __global__ __launch_bounds__(64 * WALK_NW, 2) void gbdt_walk_kernel(WalkArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smemw[];
   unsigned char* rS = smemw;                                             // [R_CAP] records
@@ -592,6 +599,15 @@ void destroy_forest(Forest* F) {
   delete F;
 }
 
+// which kernel rihip_gbdt_predict launches for this forest (the values of rihip_gbdt_predict_path)
+enum { PATH_GENERAL = 0, PATH_COMPACT_MISSING = 1, PATH_COMPACT_SIMPLE = 2, PATH_WALK = 3 };
+int predict_path(const Forest* F) {
+  const bool compact = F->compact && F->d_nodes8 != nullptr;
+  if (compact && F->bfs && F->d_rec) return PATH_WALK;
+  if (compact) return F->simple8 ? PATH_COMPACT_SIMPLE : PATH_COMPACT_MISSING;
+  return PATH_GENERAL;
+}
+
 }  // namespace
 
 extern "C" int rihip_gbdt_create_from_text(const char* text, int64_t len, void** handle) {
@@ -640,6 +656,7 @@ extern "C" int rihip_gbdt_load_text(const char* path, void** handle) {
 extern "C" int rihip_gbdt_destroy(void* handle) { destroy_forest((Forest*)handle); return RIHIP_OK; }
 extern "C" int rihip_gbdt_num_trees(void* handle) { return handle ? ((Forest*)handle)->n_trees : 0; }
 extern "C" int rihip_gbdt_num_features(void* handle) { return handle ? ((Forest*)handle)->n_features : 0; }
+extern "C" int rihip_gbdt_predict_path(void* handle) { return handle ? predict_path((Forest*)handle) : PATH_GENERAL; }
 
 // feature names joined by '\n' into buf (returns needed length incl. NUL)
 extern "C" int64_t rihip_gbdt_feature_names(void* handle, char* buf, int64_t buf_len) {
@@ -668,7 +685,8 @@ extern "C" int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int l
   if (n == 0) return RIHIP_OK;
   hipStream_t st = (hipStream_t)stream;
   if (F->n_trees == 0) { RIHIP_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(double) * n, st)); return RIHIP_OK; }
-  const bool compact = F->compact && F->d_nodes8 != nullptr;
+  const int path = predict_path(F);
+  const bool compact = path != PATH_GENERAL;
   const int n_chunks = compact ? (int)F->chunk8.size() - 1 : (int)F->chunk_tree_start.size() - 1;
   if (F->part_elems < (int64_t)n_chunks * n) {
     if (F->d_part) { hipFree(F->d_part); rihip_bump_generation(); }   // graphs that captured the old buffer are stale
@@ -676,16 +694,16 @@ extern "C" int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int l
     RIHIP_CHECK_HIP(hipMalloc((void**)&F->d_part, sizeof(double) * (size_t)n_chunks * n));
     F->part_elems = (int64_t)n_chunks * n;
   }
-  if (compact && F->bfs && F->d_rec) {
+  if (path == PATH_WALK) {
     WalkArgs c;
     c.rec = F->d_rec; c.leaves = F->d_leaves; c.tree_leaf_off = F->d_tree_leaf_off; c.chunk = F->d_chunk8;
     c.rec_chunk_off = F->d_rec_chunk_off; c.rec_root = F->d_rec_root; c.tree_depth = F->d_depth8;
     c.X = X; c.n = n; c.F = F->n_features; c.ldx = ldx; c.part = F->d_part;
-    const size_t lds = sizeof(uint2) * R_CAP + sizeof(double) * (L8_CAP + WALK_NW * 64) + sizeof(float) * 64 * (size_t)F->n_features;
+    const size_t lds = walk_lds_bytes(F->n_features);
     static bool granted_w = false;
     if (!granted_w) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gbdt_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(sizeof(uint2) * R_CAP + sizeof(double) * (L8_CAP + WALK_NW * 64) + sizeof(float) * 64 * 255));
+                                (int)walk_lds_bytes(255));
       granted_w = true;
     }
     const int64_t n_tiles8 = (n + 63) / 64;
@@ -716,7 +734,7 @@ extern "C" int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int l
     const int64_t n_tiles8 = (n + 63) / 64;
     int64_t per_chunk = (3 * RIHIP_NCU + n_chunks - 1) / n_chunks;     // 3 resident workgroups per CU over all chunks
     if (per_chunk > n_tiles8) per_chunk = n_tiles8;
-    if (F->simple8) hipLaunchKernelGGL(gbdt_predict8_kernel<true>, dim3((unsigned)per_chunk, n_chunks), dim3(256), lds, st, c);
+    if (path == PATH_COMPACT_SIMPLE) hipLaunchKernelGGL(gbdt_predict8_kernel<true>, dim3((unsigned)per_chunk, n_chunks), dim3(256), lds, st, c);
     else hipLaunchKernelGGL(gbdt_predict8_kernel<false>, dim3((unsigned)per_chunk, n_chunks), dim3(256), lds, st, c);
     RIHIP_CHECK_LAUNCH();
     const double scale8 = F->average_output ? 1.0 / (double)F->n_trees : 1.0;

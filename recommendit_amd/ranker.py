@@ -47,6 +47,11 @@ class _Forest:
     def num_feature(self) -> int:
         return int(L.lib().rihip_gbdt_num_features(self._h))
 
+    def predict_path(self) -> int:
+        """Which kernel predict() launches for this forest: 0 general, 1 compact nodes with missing types, 2 compact
+        nodes without, 3 walk-ordered records (rihip_gbdt_predict_path)."""
+        return int(L.lib().rihip_gbdt_predict_path(self._h))
+
     def feature_name(self) -> List[str]:
         n = int(L.lib().rihip_gbdt_feature_names(self._h, None, 0))
         buf = C.create_string_buffer(n)
