@@ -448,6 +448,31 @@ int rihip_rank_features_build(const double* user_tab, int64_t n_user_rows, const
 int rihip_rank_topk(const double* scores, const int64_t* cand, const float* retrieval_scores, int64_t nq, int kc, int k,
                     int64_t* out_ids, double* out_scores, float* out_retrieval_scores, void* stream);
 
+/* Diversified top-k (not in the reference, which stops at nlargest): greedy Maximal Marginal Relevance re-ranking.
+ * Replaces rihip_rank_topk as the last stage of the serving chain when a diversity weight is asked for; inputs and
+ * outputs are rihip_rank_topk's.  vec_tab: device f64 table, row index = item id, n_rows rows of stride ld; the vector
+ * of an item is columns col0 .. col0 + w - 1 of its row.  diversity = d in [0, 1].
+ *  - Eligible: cand >= 0 and a score that is not NaN.  Candidates with NaN scores, then padded ones, fill the slots
+ *    left once the eligible ones run out, each group in retrieval order (rihip_rank_topk's order; their output score is
+ *    the NaN / -inf); slots past kc are -1 / -inf / -inf.
+ *  - Relevance r = (s - smin) / (smax - smin) in f64, smin / smax over the finite eligible scores; r = 0 for every
+ *    candidate when smax == smin or no score is finite; +inf -> 1.0, -inf -> 0.0.
+ *  - sim(a, b) = dot(a, b) / (|a| * |b|): dot and the sums of squares in f64, sequentially over components 0..w-1,
+ *    multiply and add unfused (no FMA); |.| a correctly rounded sqrt; sim = 0 when either norm is 0 or either id is
+ *    outside [0, n_rows).  This is intra_list_diversity's cosine (src/evaluation/metrics.py:168-190).
+ *  - For t = 0..k-1 pick the eligible, unselected candidate of largest obj = (1 - d) * r - d * m, m = the largest sim
+ *    to anything selected so far (0 while nothing is); 1 - d is one f64 subtraction, obj two unfused multiplies and
+ *    one subtraction (a NaN obj, possible only with non-finite vectors, counts as -inf).  Ties in obj: the larger raw
+ *    score (==, so -0.0 ties +0.0), then the smaller retrieval position.
+ *  - Outputs [nq, k] in selection order: ids, raw ranker scores, retrieval scores.  d = 0 is rihip_rank_topk bit for
+ *    bit; at d = 1 the first pick is still the best score.
+ * Limits: 1 <= kc <= 4096, k >= 1, 1 <= w <= 256, col0 >= 0, ld >= col0 + w, 0 <= d <= 1 (NaN rejected): anything
+ * else is RIHIP_ERR_ARG and nothing is launched.  One workgroup per request, O(k * kc * w) work; no host
+ * synchronisation, no allocation, no atomics: capturable in a hipGraph and bitwise reproducible. */
+int rihip_rank_topk_diverse(const double* scores, const int64_t* cand, const float* retrieval_scores, int64_t nq, int kc,
+                            int k, const double* vec_tab, int64_t n_rows, int64_t ld, int col0, int w, double diversity,
+                            int64_t* out_ids, double* out_scores, float* out_retrieval_scores, void* stream);
+
 /* ---- seen-item exclusion ----------------------------------------------------------------------
  * Not in the reference, which serves and evaluates every retrieved candidate whether the user has rated it or not
  * (src/serving/recommender.py:269-387, src/pipelines/run_pipeline.py:166-220; SURVEY.md section 3.4, hazard ii).  Replaces the

@@ -135,6 +135,8 @@ SIGNATURES = {
     "rihip_bpr_step_persistent": (C.c_int, [vp, vp]),
     "rihip_rank_features_widths": (C.c_int, [vp, vp, vp]),
     "rihip_rank_topk": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "rihip_rank_topk_diverse": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, c_i64, c_i64, C.c_int, C.c_int, C.c_double,
+                                          vp, vp, vp, vp]),
     "rihip_exclude_topk": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp, c_i64, vp, C.c_int, vp, vp, vp, vp, vp]),
     "rihip_eval_nparts": (C.c_int, []),
     "rihip_eval_topk": (C.c_int, [vp, c_i64, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, c_i64,

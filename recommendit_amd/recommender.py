@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import rerank as RR
 from .faiss_index import FAISSIndex
 from .ranker import LightGBMRanker
 from .seen import SeenItems, overfetch_k, plan_overfetch
@@ -24,6 +25,7 @@ from .two_tower import N_GENRES, TwoTowerModel
 
 USER_SCALARS = [("avg_rating", 3.5), ("log_rating_count", 0.0), ("recency_score", 0.5), ("gender_encoded", 0.0),
                 ("age_normalized", 0.3), ("occupation_normalized", 0.3)]            # recommender.py:227-232
+_DEFAULT = object()     # "use the constructor's diversity" (None turns the stage off for one call)
 ITEM_SCALARS = [("avg_rating", 3.5), ("log_rating_count", 0.0), ("popularity_score", 0.0), ("rating_stddev", 0.0),
                 ("year_normalized", 0.5)]                                           # recommender.py:234-238
 
@@ -177,19 +179,34 @@ def build_ranking_features_device(store: GpuFeatureStore, user_ids: torch.Tensor
 class GpuRecommendationPipeline:
     def __init__(self, model: TwoTowerModel, index: FAISSIndex, ranker: LightGBMRanker, store: GpuFeatureStore,
                  top_k_candidates: int = 500, top_k_results: int = 20, feature_log_rows: int = 0,
-                 seen: Optional[SeenItems] = None):
+                 seen: Optional[SeenItems] = None, diversity: Optional[float] = None,
+                 diversity_vectors: Optional[torch.Tensor] = None):
         """defaults = settings.TOP_K_CANDIDATES / TOP_K_RESULTS (src/config.py:11-12).
 
         seen (not in the reference, which recommends what the user has already rated: SURVEY.md §3.4 hazard ii): a
         store of excluded item ids per user id; with one attached, retrieval over-fetches and a device filter drops
         each user's items, so features, the feature log, the ranker and the top-k still see top_k_candidates columns.
 
+        diversity (not in the reference, whose chain ends in nlargest): None = the last stage is the plain top-k by
+        ranker score, as ever.  A number in [0, 1] = greedy MMR re-ranking instead (rerank.py; the definition is at
+        rihip_rank_topk_diverse in recommendit_hip.h): each pick maximises (1 - diversity) * normalised score -
+        diversity * largest cosine to the items already picked, so 0 is the plain top-k again and larger values trade
+        ranker score for avg_diversity, the metric the evaluation reports.  diversity_vectors: the vectors the cosine is
+        taken over, a device float64 [n, w <= 256] tensor indexed by item id (e.g. item-tower embeddings); None = the
+        genre columns of the feature store's item table, i.e. exactly intra_list_diversity's vectors.  The stage only
+        replaces the one behind seen-item exclusion and item_filter, so it composes with both, and it is one launch
+        without synchronisation: graph=True works.
+
         feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
         device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
         serving_features(), detect_skew(), reset_feature_log().  0 leaves the chain as it is."""
         self.model, self.index, self.ranker, self.store = model, index, ranker, store
         self.top_k_candidates, self.top_k_results = top_k_candidates, top_k_results
-        self._graphs: Dict[Tuple[int, int, Optional[int]], Any] = {}
+        self._graphs: Dict[Tuple[int, int, Optional[int], Optional[float]], Any] = {}
+        self.diversity = None if diversity is None else RR.check_diversity(diversity)
+        if diversity_vectors is not None:
+            RR.check_table(diversity_vectors)
+        self.diversity_vectors = diversity_vectors
         self.seen = seen
         self._pin: Dict[int, Any] = {}
         self._defer = os.environ.get("RIHIP_SERVE_DEFER", "1") != "0"   # 0: exactness check inside the search (experiments)
@@ -205,9 +222,28 @@ class GpuRecommendationPipeline:
         0 whenever the over-fetch was planned from the attached store"""
         return self.index.exclusion_deficit()
 
+    def _diversity_stage(self, diversity, k: int):
+        """the checked last stage of one call: None (plain top-k) or (weight, table, col0, width); ValueError for a bad
+        weight or a shape outside the kernel's limits, before anything is launched"""
+        d = self.diversity if diversity is _DEFAULT else diversity
+        if d is None:
+            return None
+        d = RR.check_diversity(d)
+        if self.diversity_vectors is not None:
+            tab = self.diversity_vectors
+            col0, w = RR.check_table(tab)
+        else:
+            tab, col0, w = None, 5, N_GENRES          # the item table, fetched where the chain runs
+        RR.check_shape(min(self.top_k_candidates, max(int(self.index.index.ntotal), 1)), k, w)
+        if tab is None:
+            tab = self.store.device_tables()[1]
+        elif not tab.is_cuda:
+            raise ValueError("diversity_vectors must live on the device")
+        return d, tab, col0, w
+
     @torch.no_grad()
     def recommend_batch(self, user_ids, k: Optional[int] = None, graph: bool = False,
-                        exclude_seen: Optional[bool] = None, item_filter=None
+                        exclude_seen: Optional[bool] = None, item_filter=None, diversity=_DEFAULT
                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """recommendations of a batch of users (outputs: _recommend).  exclude_seen: drop each user's items of the
         attached seen store from retrieval; None = yes iff a store is attached.  With host ids the batch is served in
@@ -219,8 +255,12 @@ class GpuRecommendationPipeline:
         passing items, -1 padded when fewer than top_k_candidates pass; features, ranker and top-k run as on any short
         retrieval result, and with a seen store the candidates are filter AND not-seen (one group at the batch's
         longest seen list).  The filtered search synchronises the stream for its exactness check, so it cannot be
-        captured: graph=True with a filter raises ValueError."""
+        captured: graph=True with a filter raises ValueError.
+
+        diversity: overrides the constructor's value for this call (a number in [0, 1], or None for the plain top-k);
+        the outputs are then in MMR selection order, not in score order."""
         k = k or self.top_k_results
+        div = self._diversity_stage(diversity, k)
         if exclude_seen and self.seen is None:
             raise ValueError("exclude_seen=True without a seen store (set_seen)")
         if item_filter is not None:
@@ -236,25 +276,25 @@ class GpuRecommendationPipeline:
                     most = int(self.seen.counts_of(host).max()) if host.size else 0
                 if most:
                     k_eff = overfetch_k(min(self.top_k_candidates, ntotal), most, ntotal, int(L.lib().rihip_ip_index_max_k()))
-            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff, item_filter=item_filter)
+            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff, item_filter=item_filter, div=div)
         if self.seen is None or exclude_seen is False:
-            return self._recommend(user_ids, k, graph, None)
+            return self._recommend(user_ids, k, graph, None, div)
         ntotal = self.index.index.ntotal
         kc = min(self.top_k_candidates, ntotal)
         k_max = int(L.lib().rihip_ip_index_max_k())
         if graph or (isinstance(user_ids, torch.Tensor) and user_ids.is_cuda):
             return self._recommend(user_ids, k, graph, overfetch_k(kc, self.seen.max_count, ntotal, k_max)
-                                   if self.seen.max_count else None)
+                                   if self.seen.max_count else None, div)
         host = np.asarray(user_ids.tolist() if isinstance(user_ids, torch.Tensor) else user_ids, dtype=np.int64)
         extra = self.seen.counts_of(host)
         if not extra.any():
-            return self._recommend(user_ids, k, False, None)
+            return self._recommend(user_ids, k, False, None, div)
         plan = plan_overfetch(extra, kc, ntotal, k_max)
         if len(plan) == 1:
-            return self._recommend(user_ids, k, False, plan[0][0])
+            return self._recommend(user_ids, k, False, plan[0][0], div)
         outs = None
         for k_eff, pos in plan:
-            part = self._recommend(host[pos].tolist(), k, False, k_eff if extra[pos].any() else None)
+            part = self._recommend(host[pos].tolist(), k, False, k_eff if extra[pos].any() else None, div)
             if outs is None:
                 outs = tuple(torch.empty((host.shape[0],) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device)
                              for p in part)
@@ -263,7 +303,7 @@ class GpuRecommendationPipeline:
                 o.index_copy_(0, sel, p)
         return outs
 
-    def _recommend(self, user_ids, k: int, graph: bool, k_eff: Optional[int]
+    def _recommend(self, user_ids, k: int, graph: bool, k_eff: Optional[int], div=None
                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """-> (item_ids i64 [nq,k], ranker scores f64 [nq,k], retrieval scores f32 [nq,k]) on device; -1 padded
         where retrieval returned fewer than k candidates.  Ties in the ranker score keep retrieval order
@@ -276,25 +316,27 @@ class GpuRecommendationPipeline:
 
         k_eff: None = retrieval as it is; else retrieval fetches k_eff candidates and the seen filter keeps the
         first top_k_candidates allowed ones (a consumer of the search like the stages behind it: it runs again with
-        the chain after an exactness re-do)."""
+        the chain after an exactness re-do).
+
+        div: None = the last stage is rihip_rank_topk; else _diversity_stage's tuple and it is rihip_rank_topk_diverse."""
         # The retrieval stage's exactness check is deferred to the END of the chain (FAISSIndex.set_deferred_check): the
         # thresholded IVF pass of a large batch used to stop for a host round trip in the middle of the chain (a 54 us
         # hole at 256 requests, and the reason such batches could not be captured as a hipGraph).  In the rare case that
         # queries had to be re-done exactly, the chain runs again on the corrected candidates (not deferred).
         if not self._defer:
-            out = self._replay(user_ids, k, k_eff) if graph else None
+            out = self._replay(user_ids, k, k_eff, div) if graph else None
             if out is not None:
                 return out[0]
-            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff)
+            return self._chain(self._ids_to_device(user_ids), k, k_eff=k_eff, div=div)
         self.index.set_deferred_check(True)
         try:
-            out = self._replay(user_ids, k, k_eff) if graph else None
+            out = self._replay(user_ids, k, k_eff, div) if graph else None
             uid = None
             if out is not None:
                 out, redone = out
             else:
                 uid = self._ids_to_device(user_ids)
-                out = self._chain(uid, k, k_eff=k_eff)
+                out = self._chain(uid, k, k_eff=k_eff, div=div)
                 redone = self.index.finish_search()
         finally:
             self.index.set_deferred_check(False)
@@ -303,7 +345,7 @@ class GpuRecommendationPipeline:
                 uid = self._ids_to_device(user_ids)
             if self._log is not None:       # the batch is logged again with its final candidates: drop the first rows
                 L.check(L.lib().rihip_feature_log_rewind(self._log[3].data_ptr(), L.stream_ptr()), "feature_log_rewind")
-            out = self._chain(uid, k, k_eff=k_eff)
+            out = self._chain(uid, k, k_eff=k_eff, div=div)
         return out
 
     def _ids_to_device(self, user_ids) -> torch.Tensor:
@@ -326,22 +368,25 @@ class GpuRecommendationPipeline:
         ev.record()
         return dev_t
 
-    def _graph_state(self):
+    def _graph_state(self, div=None):
         """everything a captured chain bakes in besides the torch-owned tensors of its own pool: the library's scratch
         generation (handle-owned buffers that are freed when they grow, nprobe, id map, index / forest content) and the
-        identity of the feature tables and of the three stage objects"""
+        identity of the feature tables and of the three stage objects; with a diversified last stage (div) also its
+        weight and the identity of its vector table"""
         ut, it = self.store.device_tables()
         return (int(L.lib().rihip_scratch_generation()), ut.data_ptr(), it.data_ptr(), id(self.index), id(self.ranker),
                 id(self.model), self.top_k_candidates, tuple(self.ranker.feature_names),
                 None if self._log is None else (self._log[0].data_ptr(), self._log[0].shape[0]),
                 None if self.seen is None else (self.seen.offsets.data_ptr(), self.seen.items.data_ptr(),
-                                                self.seen.n_users))
+                                                self.seen.n_users),
+                None if div is None else (div[0], div[1].data_ptr(), tuple(div[1].shape), tuple(div[1].stride()),
+                                          div[2], div[3]))
 
-    def _replay(self, user_ids, k: int, k_eff: Optional[int] = None):
+    def _replay(self, user_ids, k: int, k_eff: Optional[int] = None, div=None):
         nq = len(user_ids)
-        key = (nq, k, k_eff)
+        key = (nq, k, k_eff, None if div is None else div[0])
         ent = self._graphs.get(key)
-        if ent is not None and ent is not False and ent[3] != self._graph_state():
+        if ent is not None and ent is not False and ent[3] != self._graph_state(div):
             # an eager call (or a capture of a larger shape) grew a scratch buffer, nprobe changed, the feature tables
             # were reloaded, ...: the pointers inside this graph are stale -- drop it and capture again
             ent = None
@@ -355,16 +400,16 @@ class GpuRecommendationPipeline:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):      # warm-up: scratch buffers, LDS grants, lazy module loads
                     for _ in range(2):
-                        self._chain(su, k, log=False, k_eff=k_eff)
+                        self._chain(su, k, log=False, k_eff=k_eff, div=div)
                         self.index.finish_search()
                 cur.wait_stream(side)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    out = self._chain(su, k, k_eff=k_eff)
+                    out = self._chain(su, k, k_eff=k_eff, div=div)
                 deferred = self.index.search_pending()      # the captured search left its exactness check to the caller
                 self.index.set_deferred_check(True)         # (capture ran nothing: drop the pending state)
-                ent = (g, su, out, self._graph_state(), deferred)   # state recorded AFTER capture: the warm-up may have grown scratch
+                ent = (g, su, out, self._graph_state(div), deferred)   # state recorded AFTER capture: the warm-up may have grown scratch
             except Exception:                        # a path with a host sync cannot be captured: stay eager for this shape
                 torch.cuda.synchronize()
                 ent = False
@@ -377,8 +422,8 @@ class GpuRecommendationPipeline:
         # a replay runs no host code: the failure count of its deferred search is read here (one synchronisation)
         return out, (self.index.last_fail_count() if deferred else 0)
 
-    def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None, item_filter=None
-               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None, item_filter=None,
+               div=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
@@ -399,6 +444,8 @@ class GpuRecommendationPipeline:
             self._append_log(X, uid, cand)
         scores = self.ranker.predict_device(X)
         k = min(k, kc)
+        if div is not None:
+            return RR.launch(scores, cand, rs, k, div[0], div[1], div[2], div[3])
         ids = torch.empty((nq, k), dtype=torch.int64, device=cand.device)
         top = torch.empty((nq, k), dtype=torch.float64, device=cand.device)
         trs = torch.empty((nq, k), dtype=torch.float32, device=cand.device)
@@ -477,9 +524,12 @@ class GpuRecommendationPipeline:
         return S.detect_training_serving_skew_device(train_features, serving, threshold, numeric_cols, columns)
 
     def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False,
-                            exclude_seen: Optional[bool] = None, item_filter=None) -> List[Dict[str, Any]]:
-        """item_filter: as in recommend_batch (graph=True with a filter raises ValueError)"""
-        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen, item_filter=item_filter)
+                            exclude_seen: Optional[bool] = None, item_filter=None, diversity=_DEFAULT
+                            ) -> List[Dict[str, Any]]:
+        """item_filter, diversity: as in recommend_batch (graph=True with a filter raises ValueError); with a diversity
+        the list is in selection order and "rank" is the position in it"""
+        ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen, item_filter=item_filter,
+                                           diversity=diversity)
         out = []
         for rank, (i, s, r) in enumerate(zip(ids[0].tolist(), sc[0].tolist(), rs[0].tolist()), start=1):
             if i >= 0:
