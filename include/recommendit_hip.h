@@ -428,6 +428,28 @@ int64_t rihip_gbdt_feature_names(void* handle, char* buf, int64_t buf_len); /* '
 int rihip_gbdt_feature_importance(void* handle, int importance_type, double* out_host);
 int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int ldx, double* out, void* stream);
 
+/* Per-feature contributions to the raw score (lgb.Booster.predict(X, pred_contrib=True)): TreeSHAP with
+ * path-dependent covers (Lundberg, Erion, Lee: "Consistent individualized feature attribution for tree ensembles",
+ * Algorithm 2) over the leaf_count / internal_count lines of the model text.
+ *   out[r, f] = sum over trees and root-to-leaf paths P of  (one_f - zero_f) * U_f(P, r) * leaf_value(P)    (f < F)
+ *   out[r, F] = sum over trees of  sum_leaves leaf_value * leaf_count / count(root)     (the expected value)
+ * A path keeps one element per distinct feature it splits on: zero_f is the product of count(child on the path) /
+ * count(node) over its splits on f; one_f is 1 when row r goes to the path's child at every one of them (the decision
+ * rule of rihip_gbdt_predict, every decision type) and 0 otherwise.  U_f is the sum of the path weights -- EXTEND over
+ * the root's dummy element and all elements -- with element f unwound again.  A tree of one leaf adds its value to
+ * out[r, F] only.  For an average_output model every column is divided by the tree count, so out[r, :] sums to what
+ * rihip_gbdt_predict returns for row r (up to f64 rounding).
+ * X device f32 [n, ldx]; out device f64 [n, F + 1], F = rihip_gbdt_num_features.  f64 arithmetic throughout, no
+ * floating-point atomics: two calls are bitwise equal and a row's result does not depend on the other rows.  Enqueues
+ * on `stream`, no host synchronisation; the path tables are built on the first call and the scratch (at most 64 MiB,
+ * longer calls run as several row blocks) belongs to the handle.
+ * rihip_gbdt_has_counts: 1 when every tree with a split carries both count lines.
+ * Errors (non-zero, reason in rihip_last_error, nothing launched): a model without counts; a non-positive
+ * internal_count or leaf_count; a tree of more than 128 leaves; a path with more than 64 distinct features;
+ * more than 65535 trees. */
+int rihip_gbdt_has_counts(void* handle);
+int rihip_gbdt_predict_contrib(void* handle, const float* X, int64_t n, int ldx, double* out, void* stream);
+
 /* ---- ranking-feature assembly ----------------------------------------------------------------
  * Replaces RecommendationPipeline._build_ranking_features (src/serving/recommender.py:213-263) and the
  * feature-store fetch in front of it (recommender.py:319-322) with GPU-resident float64 tables:

@@ -126,6 +126,8 @@ SIGNATURES = {
     "rihip_gbdt_feature_names": (c_i64, [vp, C.c_char_p, c_i64]),
     "rihip_gbdt_feature_importance": (C.c_int, [vp, C.c_int, vp]),
     "rihip_gbdt_predict": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp]),
+    "rihip_gbdt_has_counts": (C.c_int, [vp]),
+    "rihip_gbdt_predict_contrib": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp]),
     "rihip_lambdamart_train": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, c_i64, C.c_int, vp, C.c_char_p,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]),
     "rihip_free": (None, [vp]),

@@ -18,7 +18,9 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <string>
 #include <utility>
@@ -82,6 +84,11 @@ struct Forest {
   std::vector<int> rec_chunk_off;    // [n_chunks8+1] record index of each chunk's first record
   std::vector<int> rec_root;         // per tree: byte offset of its root record inside its chunk
   uint2* d_rec = nullptr; int* d_rec_chunk_off = nullptr; int* d_rec_root = nullptr;
+  // covers (leaf_count / internal_count of the model text), host side, aligned with `leaves` / `nodes`; has_counts is
+  // false when a tree with a split lacks either line.  Only rihip_gbdt_predict_contrib reads them.
+  bool has_counts = false;
+  std::vector<long long> leaf_cnt, node_cnt;
+  struct ContribPlan* contrib = nullptr;   // built on the first contribution call (gbdt_contrib section below)
 };
 
 struct PredArgs {
@@ -491,7 +498,7 @@ int parse_model(const std::string& text, Forest* F) {
   bool in_tree = false, done = false;
   struct RawTree {
     int num_leaves = 0, num_cat = 0;
-    std::vector<long long> split_feature, decision_type, left, right, cat_b, cat_w;
+    std::vector<long long> split_feature, decision_type, left, right, cat_b, cat_w, leaf_count, internal_count;
     std::vector<double> threshold, leaf_value, split_gain;
   };
   std::vector<RawTree> trees;
@@ -518,6 +525,8 @@ int parse_model(const std::string& text, Forest* F) {
       else if (k == "left_child") t.left = parse_list<long long>(v);
       else if (k == "right_child") t.right = parse_list<long long>(v);
       else if (k == "leaf_value") t.leaf_value = parse_list<double>(v);
+      else if (k == "leaf_count") t.leaf_count = parse_list<long long>(v);
+      else if (k == "internal_count") t.internal_count = parse_list<long long>(v);
       else if (k == "cat_boundaries") t.cat_b = parse_list<long long>(v);
       else if (k == "cat_threshold") t.cat_w = parse_list<long long>(v);
       else if (k == "is_linear") { if (atoi(v.c_str()) != 0) { rihip_set_error("gbdt: linear trees unsupported"); return RIHIP_ERR_SHAPE; } }
@@ -533,8 +542,14 @@ int parse_model(const std::string& text, Forest* F) {
   F->tree_node_off.push_back(0); F->tree_leaf_off.push_back(0);
   F->tree_cat_b_off.clear(); F->tree_cat_w_off.clear();
   bool any_cat = false;
+  F->has_counts = true;
   for (auto& t : trees) {
     const int ni = t.num_leaves > 1 ? t.num_leaves - 1 : 0;
+    const bool counted = ni == 0 || ((int)t.leaf_count.size() >= t.num_leaves && (int)t.internal_count.size() >= ni);
+    if (!counted) F->has_counts = false;
+    for (int i = 0; i < ni; ++i) F->node_cnt.push_back(counted ? t.internal_count[i] : 0);
+    for (int i = 0; i < (t.num_leaves > 1 ? t.num_leaves : 1); ++i)
+      F->leaf_cnt.push_back(counted && i < (int)t.leaf_count.size() ? t.leaf_count[i] : 0);
     if ((int)t.leaf_value.size() < (t.num_leaves > 0 ? t.num_leaves : 1) && !(t.num_leaves <= 1 && t.leaf_value.empty())) {
       rihip_set_error("gbdt: tree with %d leaves has %zu leaf values", t.num_leaves, t.leaf_value.size()); return RIHIP_ERR_IO;
     }
@@ -590,12 +605,312 @@ int upload(const std::vector<T>& v, T** d) {
   return RIHIP_OK;
 }
 
+// ---------------------------------- TreeSHAP contributions --------------------------------------
+// rihip_gbdt_predict_contrib: phi[row, f] = sum over root-to-leaf paths of (one_f - zero_f) * unwound_sum_f * leaf_value
+// (Lundberg et al., "Consistent individualized feature attribution for tree ensembles", Algorithm 2, path-dependent
+// covers), restated path-parallel.  Host, once per forest: every tree is flattened into its paths; a path keeps one
+// ELEMENT per distinct feature with zero_fraction = product of count(child on the path) / count(node) over the path's
+// splits on that feature, and a (care, want) pair of masks over the tree's <= 127 internal nodes: one_fraction is 1 iff
+// the row's go-left bits agree with `want` on every `care` node.  The go-left bits come from decide_left, so every
+// decision type agrees with predict.
+//
+// Device: a path with D elements owns min(D + 1, 64) consecutive lanes of a 64-lane BIN (paths of one tree, longest
+// first): lane j of the path holds the path weight w[j] of the EXTEND recurrence and element j + 1.  EXTEND step l
+// reads w[j - 1] from the lane below and the fractions of element l from its lane; the unwound sum of a lane's element
+// walks w[D - 1 .. 0] with one broadcast per step.  (w[64] of a 64-element path, which fills the bin, lives in `wtop`.)
+// All of it in f64: the unwind divides by products of small cover fractions and cancels.
+//
+// Reproducible without floating-point atomics: a bin's lanes stage their contributions in LDS, lane u of the bin owns
+// the bin's u-th distinct feature and adds the staged values of that feature in lane order into its wave's own
+// accumulator row; a wave takes every 4th bin of the chunk in order; the 4 waves and then the chunks are added in fixed
+// order.  Nothing depends on the other rows of the call.
+constexpr int SH_MAX_LEAVES = 128;   // leaves per tree (=> 127 internal nodes: two 64-bit go-left words)
+constexpr int SH_MAX_DEPTH = 64;     // distinct features on one path
+constexpr int SH_ROWS = 4;           // rows per workgroup: a bin's lane records are loaded once for all of them
+constexpr int SH_CHUNK_TREES = 8;    // trees per chunk (grid.y): 63 chunks at 500 trees, so 20 rows still fill the chip
+constexpr int64_t SH_PART_BYTES = 64ll << 20;   // partial buffer: longer calls run as several row blocks
+
+struct ShapSlot {   // one lane of one bin, 64 bytes
+  double z, leaf;                 // zero_fraction of the lane's element; the path's leaf value
+  unsigned long long care[2], want[2];
+  unsigned long long umask;       // reduce phase: lanes of the bin whose element has feature `ufeat`
+  int info;                       // bits 0-5 j, 6-12 D, 13-18 first lane of the path, 19 lane holds an element, 20 lane in a path
+  int ufeat;                      // reduce phase: the feature this lane owns in the bin, or -1
+};
+static_assert(sizeof(ShapSlot) == 64, "ShapSlot must be 64 bytes");
+
+struct ContribPlan {
+  std::vector<ShapSlot> slots;          // [n_bins * 64]
+  std::vector<int> bin_info;            // per bin: tree | dmax << 16
+  std::vector<int> chunk_tree, chunk_bin;   // [n_chunks + 1]
+  double expected = 0.0;                // sum over trees of sum(leaf_value * leaf_count) / root_count
+  ShapSlot* d_slots = nullptr; int *d_bin_info = nullptr, *d_chunk_tree = nullptr, *d_chunk_bin = nullptr;
+  double* d_part = nullptr; int64_t part_elems = 0;
+};
+
+struct ContribArgs {
+  const ShapSlot* slots; const int *bin_info, *chunk_tree, *chunk_bin;
+  const Node* nodes; const int *tree_node_off, *cat_b, *cat_w, *tree_cat_b_off, *tree_cat_w_off;
+  const float* X; int64_t n; int F; int ldx;
+  double* part;   // [n_chunks, n, F]
+};
+
+__global__ __launch_bounds__(256) void gbdt_contrib_kernel(ContribArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float xS[SH_ROWS][F_MAX];
+  __shared__ unsigned long long glS[SH_ROWS][SH_CHUNK_TREES][2];
+  __shared__ double cS[4][SH_ROWS][64];
+  __shared__ double accS[4][SH_ROWS][F_MAX];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int chunk = blockIdx.y;
+  const int64_t row0 = (int64_t)blockIdx.x * SH_ROWS;
+  const int t0 = a.chunk_tree[chunk], t1 = a.chunk_tree[chunk + 1];
+  const int b0 = a.chunk_bin[chunk], b1 = a.chunk_bin[chunk + 1];
+  for (int i = tid; i < SH_ROWS * a.F; i += 256) {
+    const int r = i / a.F, f = i - r * a.F;
+    xS[r][f] = (row0 + r < a.n) ? a.X[(row0 + r) * a.ldx + f] : 0.f;
+  }
+  for (int i = tid; i < 4 * SH_ROWS * F_MAX; i += 256) (&accS[0][0][0])[i] = 0.0;
+  __syncthreads();
+  // go-left bit of every internal node, per (row, tree of the chunk): lane i decides nodes i and i + 64
+  for (int p = w; p < SH_ROWS * (t1 - t0); p += 4) {
+    const int r = p / (t1 - t0), tt = p - r * (t1 - t0), t = t0 + tt;
+    const int nb = a.tree_node_off[t], nn = a.tree_node_off[t + 1] - nb;
+    const int* cb = a.cat_b ? a.cat_b + a.tree_cat_b_off[t] : nullptr;
+    const int* cw = a.cat_w ? a.cat_w + a.tree_cat_w_off[t] : nullptr;
+    bool l0 = false, l1 = false;
+    if (lane < nn) { const Node nd = a.nodes[nb + lane]; l0 = decide_left(xS[r][nd.feat], nd, cb, cw); }
+    if (lane + 64 < nn) { const Node nd = a.nodes[nb + lane + 64]; l1 = decide_left(xS[r][nd.feat], nd, cb, cw); }
+    const unsigned long long m0 = __ballot(l0), m1 = __ballot(l1);
+    if (lane == 0) { glS[r][tt][0] = m0; glS[r][tt][1] = m1; }
+  }
+  __syncthreads();
+  for (int bb = b0; bb < b1; bb += 4) {   // every wave runs every iteration: the barriers below are workgroup-wide
+    const int bin = bb + w;
+    const bool on = bin < b1;
+    ShapSlot s;
+    int tt = 0, dmax = 0;
+    if (on) {
+      s = a.slots[(size_t)bin * 64 + lane];
+      const int bi = a.bin_info[bin];
+      tt = (bi & 0xFFFF) - t0; dmax = bi >> 16;
+    } else {
+      s.z = 1.0; s.leaf = 0.0; s.care[0] = s.care[1] = s.want[0] = s.want[1] = 0; s.umask = 0; s.info = 0; s.ufeat = -1;
+    }
+    const int j = s.info & 63, D = (s.info >> 6) & 127, base = (s.info >> 13) & 63;
+    const bool has_elem = (s.info >> 19) & 1, in_path = (s.info >> 20) & 1;
+    for (int r = 0; r < SH_ROWS; ++r) {
+      double c = 0.0;
+      if (on && row0 + r < a.n) {   // wave-uniform
+        const unsigned long long g0 = glS[r][tt][0], g1 = glS[r][tt][1];
+        const bool o = (((g0 ^ s.want[0]) & s.care[0]) | ((g1 ^ s.want[1]) & s.care[1])) == 0;
+        const unsigned long long obits = __ballot(has_elem && o);
+        // EXTEND: after the root's dummy element w = [1]; step l adds element l (held by lane base + l - 1)
+        double wt = (in_path && j == 0) ? 1.0 : 0.0, wtop = 0.0;
+        for (int l = 1; l <= dmax; ++l) {
+          const int src = (base + l - 1) & 63;
+          const double pz = __shfl(s.z, src);
+          const double po = ((obits >> src) & 1) ? 1.0 : 0.0;
+          double wprev = __shfl_up(wt, 1);
+          if (j == 0) wprev = 0.0;
+          if (l == 64) wtop = (po * __shfl(wt, 63) * 64.0) / 65.0;   // a 64-element path fills the bin: w[64]
+          if (in_path && l <= D)
+            wt = (pz * wt * (double)(l - j)) / (double)(l + 1) + (po * wprev * (double)j) / (double)(l + 1);
+        }
+        // unwound sum of the lane's element: the weights of the path with that element taken out again
+        const double wl = __shfl(wt, (base + D) & 63);
+        double next_one = D == 64 ? wtop : wl, total = 0.0;
+        const double dl1 = (double)(D + 1);
+        for (int jj = dmax - 1; jj >= 0; --jj) {
+          const double wj = __shfl(wt, (base + jj) & 63);
+          if (has_elem && jj < D) {
+            if (o) {
+              const double tmp = (next_one * dl1) / (double)(jj + 1);
+              total += tmp;
+              next_one = wj - tmp * s.z * ((double)(D - jj) / dl1);
+            } else {
+              total += (wj / s.z) / ((double)(D - jj) / dl1);
+            }
+          }
+        }
+        if (has_elem) c = total * ((o ? 1.0 : 0.0) - s.z) * s.leaf;
+      }
+      cS[w][r][lane] = c;
+    }
+    __syncthreads();
+    if (s.ufeat >= 0) {
+      for (int r = 0; r < SH_ROWS; ++r) {
+        double sum = 0.0;
+        for (unsigned long long m = s.umask; m; m &= m - 1) sum += cS[w][r][__builtin_ctzll(m)];
+        accS[w][r][s.ufeat] += sum;
+      }
+    }
+    __syncthreads();   // the next bin's contributions overwrite cS
+  }
+  __syncthreads();
+  for (int i = tid; i < SH_ROWS * a.F; i += 256) {
+    const int r = i / a.F, f = i - r * a.F;
+    if (row0 + r < a.n)
+      a.part[((size_t)chunk * a.n + (row0 + r)) * a.F + f] = ((accS[0][r][f] + accS[1][r][f]) + accS[2][r][f]) + accS[3][r][f];
+  }
+}
+
+// out[row, f] = scale * sum over chunks (fixed order); out[row, F] = scale * expected
+__global__ void gbdt_contrib_reduce_kernel(const double* __restrict__ part, int n_chunks, int64_t n, int F, double expected,
+                                           double scale, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * (F + 1)) return;
+  const int64_t row = i / (F + 1);
+  const int f = (int)(i - row * (F + 1));
+  double s = expected;
+  if (f < F) {
+    s = 0.0;
+    for (int c = 0; c < n_chunks; ++c) s += part[((size_t)c * n + row) * F + f];
+  }
+  out[i] = s * scale;
+}
+
+// Flattens the forest into bins of path lanes.  Non-zero return (reason in rihip_last_error) for a forest without
+// counts, a non-positive count, a tree over SH_MAX_LEAVES or a path over SH_MAX_DEPTH distinct features.
+int build_contrib_plan(Forest* F) {
+  RIHIP_REQUIRE(F->has_counts, RIHIP_ERR_STATE,
+                "gbdt_predict_contrib: the model has no leaf_count / internal_count lines (TreeSHAP needs the covers)");
+  RIHIP_REQUIRE(F->n_trees <= 0xFFFF, RIHIP_ERR_SHAPE, "gbdt_predict_contrib: %d trees; at most 65535 are supported", F->n_trees);
+  ContribPlan* P = new ContribPlan();
+  struct PathEl { int feat; double z; unsigned long long care[2], want[2]; };
+  struct Path { std::vector<PathEl> el; double leaf; };
+  int rc = RIHIP_OK;
+  P->chunk_tree.push_back(0); P->chunk_bin.push_back(0);
+  for (int t = 0; t < F->n_trees && rc == RIHIP_OK; ++t) {
+    if (t > 0 && t % SH_CHUNK_TREES == 0) { P->chunk_tree.push_back(t); P->chunk_bin.push_back((int)P->bin_info.size()); }
+    const int nb = F->tree_node_off[t], nn = F->tree_node_off[t + 1] - nb;
+    const int lb = F->tree_leaf_off[t], nl = F->tree_leaf_off[t + 1] - lb;
+    if (nn == 0) { P->expected += F->leaves[lb]; continue; }   // a single leaf: its value goes to the expected column only
+    if (nl > SH_MAX_LEAVES || nn > SH_MAX_LEAVES - 1) {
+      rihip_set_error("gbdt_predict_contrib: tree %d has %d leaves; at most %d leaves per tree are supported", t, nl, SH_MAX_LEAVES);
+      rc = RIHIP_ERR_SHAPE; break;
+    }
+    for (int i = 0; i < nn && rc == RIHIP_OK; ++i)
+      if (F->node_cnt[nb + i] <= 0) {
+        rihip_set_error("gbdt_predict_contrib: tree %d has a non-positive internal_count (%lld at node %d)", t, F->node_cnt[nb + i], i);
+        rc = RIHIP_ERR_STATE;
+      }
+    for (int i = 0; i < nl && rc == RIHIP_OK; ++i)
+      if (F->leaf_cnt[lb + i] <= 0) {
+        rihip_set_error("gbdt_predict_contrib: tree %d has a non-positive leaf_count (%lld at leaf %d)", t, F->leaf_cnt[lb + i], i);
+        rc = RIHIP_ERR_STATE;
+      }
+    if (rc != RIHIP_OK) break;
+    double ev = 0.0;
+    for (int i = 0; i < nl; ++i) ev += F->leaves[lb + i] * (double)F->leaf_cnt[lb + i];
+    P->expected += ev / (double)F->node_cnt[nb + F->tree_root[t]];
+    // depth-first over the tree, left child first; `trail` is the splits from the root to the current node
+    std::vector<Path> paths;
+    struct Step { int node; bool left; };
+    std::vector<Step> trail;
+    std::function<void(int)> visit = [&](int node) {
+      if (rc != RIHIP_OK) return;
+      if (node >= 0) {
+        if ((int)trail.size() >= nn) { rihip_set_error("gbdt_predict_contrib: tree %d has a cycle", t); rc = RIHIP_ERR_IO; return; }
+        const Node& nd = F->nodes[nb + node];
+        trail.push_back({node, true}); visit(nd.left); trail.pop_back();
+        trail.push_back({node, false}); visit(nd.right); trail.pop_back();
+        return;
+      }
+      Path p; p.leaf = F->leaves[lb + ~node];
+      for (const Step& st : trail) {
+        const Node& nd = F->nodes[nb + st.node];
+        const int child = st.left ? nd.left : nd.right;
+        const double ratio = (double)(child >= 0 ? F->node_cnt[nb + child] : F->leaf_cnt[lb + ~child]) / (double)F->node_cnt[nb + st.node];
+        size_t e = 0;
+        while (e < p.el.size() && p.el[e].feat != nd.feat) ++e;
+        if (e == p.el.size()) p.el.push_back({nd.feat, 1.0, {0, 0}, {0, 0}});
+        p.el[e].z *= ratio;
+        p.el[e].care[st.node >> 6] |= 1ull << (st.node & 63);
+        if (st.left) p.el[e].want[st.node >> 6] |= 1ull << (st.node & 63);
+      }
+      if ((int)p.el.size() > SH_MAX_DEPTH) {
+        rihip_set_error("gbdt_predict_contrib: a path of tree %d has %zu distinct features; at most %d per path are supported",
+                        t, p.el.size(), SH_MAX_DEPTH);
+        rc = RIHIP_ERR_SHAPE; return;
+      }
+      paths.push_back(std::move(p));
+    };
+    visit(F->tree_root[t]);
+    if (rc != RIHIP_OK) break;
+    // longest paths first (stable), then next-fit into 64-lane bins: a bin's paths have similar lengths
+    std::vector<int> order(paths.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return paths[x].el.size() > paths[y].el.size(); });
+    int fill = 64;   // lanes used in the open bin (64 = none open)
+    for (int pi : order) {
+      const Path& p = paths[pi];
+      const int D = (int)p.el.size(), len = D + 1 > 64 ? 64 : D + 1;
+      if (fill + len > 64) {
+        ShapSlot z; memset(&z, 0, sizeof(z)); z.z = 1.0; z.ufeat = -1;
+        P->slots.insert(P->slots.end(), 64, z);
+        P->bin_info.push_back(t);
+        fill = 0;
+      }
+      ShapSlot* bs = P->slots.data() + (P->bin_info.size() - 1) * 64;
+      if (D > (P->bin_info.back() >> 16)) P->bin_info.back() = t | (D << 16);
+      for (int j = 0; j < len; ++j) {
+        ShapSlot& s = bs[fill + j];
+        s.leaf = p.leaf;
+        s.info = j | (D << 6) | (fill << 13) | ((j < D ? 1 : 0) << 19) | (1 << 20);
+        if (j < D) {
+          const PathEl& e = p.el[j];
+          s.z = e.z; s.care[0] = e.care[0]; s.care[1] = e.care[1]; s.want[0] = e.want[0]; s.want[1] = e.want[1];
+          s.ufeat = -2 - e.feat;   // the element's own feature, until the owners are assigned below
+        }
+      }
+      fill += len;
+    }
+  }
+  if (rc != RIHIP_OK) { delete P; return rc; }
+  P->chunk_tree.push_back(F->n_trees); P->chunk_bin.push_back((int)P->bin_info.size());
+  // reduce phase: lane u of a bin owns the bin's u-th distinct feature (order of first appearance over the lanes)
+  for (size_t b = 0; b < P->bin_info.size(); ++b) {
+    ShapSlot* bs = P->slots.data() + b * 64;
+    int feat[64], nu = 0, own[64];
+    unsigned long long um[64];
+    for (int l = 0; l < 64; ++l) {
+      feat[l] = ((bs[l].info >> 19) & 1) ? -2 - bs[l].ufeat : -1;
+      if (feat[l] < 0) continue;
+      int u = 0;
+      while (u < nu && own[u] != feat[l]) ++u;
+      if (u == nu) { own[nu] = feat[l]; um[nu] = 0; ++nu; }
+      um[u] |= 1ull << l;
+    }
+    for (int l = 0; l < 64; ++l) { bs[l].ufeat = l < nu ? own[l] : -1; bs[l].umask = l < nu ? um[l] : 0; }
+  }
+  if (!P->slots.empty()) {
+    rc = upload(P->slots, &P->d_slots);
+    if (!rc) rc = upload(P->bin_info, &P->d_bin_info);
+  }
+  if (!rc) rc = upload(P->chunk_tree, &P->d_chunk_tree);
+  if (!rc) rc = upload(P->chunk_bin, &P->d_chunk_bin);
+  if (rc != RIHIP_OK) {
+    hipFree(P->d_slots); hipFree(P->d_bin_info); hipFree(P->d_chunk_tree); hipFree(P->d_chunk_bin);
+    delete P; return rc;
+  }
+  F->contrib = P;
+  return RIHIP_OK;
+}
+
+void destroy_contrib_plan(ContribPlan* P) {
+  if (!P) return;
+  hipFree(P->d_slots); hipFree(P->d_bin_info); hipFree(P->d_chunk_tree); hipFree(P->d_chunk_bin); hipFree(P->d_part);
+  delete P;
+}
+
 void destroy_forest(Forest* F) {
   if (!F) return;
   rihip_bump_generation();
   hipFree(F->d_nodes); hipFree(F->d_leaves); hipFree(F->d_tree_node_off); hipFree(F->d_tree_leaf_off); hipFree(F->d_tree_root);
   hipFree(F->d_chunk); hipFree(F->d_cat_b); hipFree(F->d_cat_w); hipFree(F->d_tree_cat_b_off); hipFree(F->d_tree_cat_w_off);
   hipFree(F->d_part); hipFree(F->d_nodes8); hipFree(F->d_chunk8); hipFree(F->d_depth8); hipFree(F->d_rec); hipFree(F->d_rec_chunk_off); hipFree(F->d_rec_root);
+  destroy_contrib_plan(F->contrib);
   delete F;
 }
 
@@ -752,5 +1067,50 @@ extern "C" int rihip_gbdt_predict(void* handle, const float* X, int64_t n, int l
   const double scale = F->average_output ? 1.0 / (double)F->n_trees : 1.0;
   hipLaunchKernelGGL(gbdt_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, F->d_part, n_chunks, n, scale, out);
   RIHIP_CHECK_LAUNCH();
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_gbdt_has_counts(void* handle) { return handle && ((Forest*)handle)->has_counts ? 1 : 0; }
+
+// X: device f32 [n, ldx]; out: device f64 [n, n_features + 1] (definition: include/recommendit_hip.h)
+extern "C" int rihip_gbdt_predict_contrib(void* handle, const float* X, int64_t n, int ldx, double* out, void* stream) {
+  Forest* F = (Forest*)handle;
+  RIHIP_REQUIRE(F && X && out && n >= 0, RIHIP_ERR_ARG, "gbdt_predict_contrib: bad arguments");
+  RIHIP_REQUIRE(ldx >= F->n_features, RIHIP_ERR_SHAPE, "gbdt_predict_contrib: %d feature columns given, model needs %d", ldx, F->n_features);
+  if (!F->contrib) { const int rc = build_contrib_plan(F); if (rc != RIHIP_OK) return rc; }
+  if (n == 0) return RIHIP_OK;
+  ContribPlan* P = F->contrib;
+  hipStream_t st = (hipStream_t)stream;
+  const int nf = F->n_features, n_chunks = (int)P->chunk_tree.size() - 1;
+  const double scale = (F->average_output && F->n_trees > 0) ? 1.0 / (double)F->n_trees : 1.0;
+  const bool any_bins = !P->bin_info.empty() && nf > 0;
+  // rows per launch: the [n_chunks, rows, F] partials stay within SH_PART_BYTES (a multiple of the row tile, so a row's
+  // workgroup -- and its result -- is the same in every block)
+  int64_t blk = SH_PART_BYTES / (int64_t)(sizeof(double) * (size_t)n_chunks * (nf > 0 ? nf : 1));
+  blk = blk / SH_ROWS * SH_ROWS;
+  if (blk < SH_ROWS) blk = SH_ROWS;
+  if (blk > n) blk = n;
+  if (any_bins && P->part_elems < (int64_t)n_chunks * blk * nf) {
+    if (P->d_part) { hipFree(P->d_part); rihip_bump_generation(); }   // graphs that captured the old buffer are stale
+    P->d_part = nullptr; P->part_elems = 0;
+    RIHIP_CHECK_HIP(hipMalloc((void**)&P->d_part, sizeof(double) * (size_t)n_chunks * blk * nf));
+    P->part_elems = (int64_t)n_chunks * blk * nf;
+  }
+  for (int64_t r0 = 0; r0 < n; r0 += blk) {
+    const int64_t nb = n - r0 < blk ? n - r0 : blk;
+    if (any_bins) {
+      ContribArgs a;
+      a.slots = P->d_slots; a.bin_info = P->d_bin_info; a.chunk_tree = P->d_chunk_tree; a.chunk_bin = P->d_chunk_bin;
+      a.nodes = F->d_nodes; a.tree_node_off = F->d_tree_node_off; a.cat_b = F->d_cat_b; a.cat_w = F->d_cat_w;
+      a.tree_cat_b_off = F->d_tree_cat_b_off; a.tree_cat_w_off = F->d_tree_cat_w_off;
+      a.X = X + r0 * ldx; a.n = nb; a.F = nf; a.ldx = ldx; a.part = P->d_part;
+      hipLaunchKernelGGL(gbdt_contrib_kernel, dim3((unsigned)((nb + SH_ROWS - 1) / SH_ROWS), n_chunks), dim3(256), 0, st, a);
+      RIHIP_CHECK_LAUNCH();
+    }
+    const int64_t tot = nb * (nf + 1);
+    hipLaunchKernelGGL(gbdt_contrib_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P->d_part,
+                       any_bins ? n_chunks : 0, nb, nf, P->expected, scale, out + r0 * (nf + 1));
+    RIHIP_CHECK_LAUNCH();
+  }
   return RIHIP_OK;
 }

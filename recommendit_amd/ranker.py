@@ -73,8 +73,24 @@ class _Forest:
                                            L.stream_ptr()), "gbdt_predict")
         return out
 
-    def predict(self, X: np.ndarray) -> np.ndarray:
+    def has_counts(self) -> bool:
+        """True when the model text carried leaf_count / internal_count for every tree with a split."""
+        return bool(L.lib().rihip_gbdt_has_counts(self._h))
+
+    def predict_contrib_device(self, X: torch.Tensor) -> torch.Tensor:
+        """X f32 [n, >=n_features] on device -> f64 [n, n_features + 1] on device: TreeSHAP contribution of every
+        feature to the raw score and, last, the expected value (lgb.Booster.predict(pred_contrib=True) layout; the
+        definition is in include/recommendit_hip.h).  Each row sums to predict_device of that row."""
+        X = X.to(dtype=torch.float32).contiguous()
+        out = torch.empty((X.shape[0], self.num_feature() + 1), dtype=torch.float64, device=X.device)
+        L.check(L.lib().rihip_gbdt_predict_contrib(self._h, X.data_ptr(), X.shape[0], X.shape[1], out.data_ptr(),
+                                                   L.stream_ptr()), "gbdt_predict_contrib")
+        return out
+
+    def predict(self, X: np.ndarray, pred_contrib: bool = False) -> np.ndarray:
         Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(L.device())
+        if pred_contrib:
+            return self.predict_contrib_device(Xd).cpu().numpy()
         return self.predict_device(Xd).cpu().numpy()
 
     def __del__(self):
@@ -265,17 +281,26 @@ class LightGBMRanker:
         self.model = _Forest(h.value)
 
     # -- inference (ranker.py:161-174) --------------------------------------------------------
-    def predict(self, features_df: pd.DataFrame) -> np.ndarray:
+    def predict(self, features_df: pd.DataFrame, pred_contrib: bool = False) -> np.ndarray:
+        """Raw scores [n]; with ``pred_contrib`` the TreeSHAP contributions [n, n_features + 1] (last column: the
+        expected value), as lgb.Booster.predict(pred_contrib=True) lays them out."""
         if not self._trained or self.model is None:
             raise RuntimeError("Model not trained. Call train() first.")
         X = features_df[self.feature_names].values.astype(np.float32)
-        return self.model.predict(X)
+        return self.model.predict(X, pred_contrib=pred_contrib)
 
     def predict_device(self, X: torch.Tensor) -> torch.Tensor:
         """Device-resident scoring (not in the reference): X f32 [n, n_features] in feature_names order."""
         if not self._trained or self.model is None:
             raise RuntimeError("Model not trained. Call train() first.")
         return self.model.predict_device(X)
+
+    def predict_contrib_device(self, X: torch.Tensor) -> torch.Tensor:
+        """Device-resident explanation (not in the reference): X f32 [n, n_features] in feature_names order ->
+        f64 [n, n_features + 1] contributions, the expected value last."""
+        if not self._trained or self.model is None:
+            raise RuntimeError("Model not trained. Call train() first.")
+        return self.model.predict_contrib_device(X)
 
     # -- analysis (ranker.py:180-197) ---------------------------------------------------------
     def feature_importance(self, importance_type: str = "gain") -> Dict[str, float]:

@@ -523,15 +523,53 @@ class GpuRecommendationPipeline:
         serving = [S._Segment(ring, list(self.ranker.feature_names), ri), S._Segment(ids, ["user_id", "item_id"], ri)]
         return S.detect_training_serving_skew_device(train_features, serving, threshold, numeric_cols, columns)
 
+    # ---- explanation (not in the reference) ----------------------------------------------------------------------
+    @torch.no_grad()
+    def explain_batch(self, user_ids, item_ids, top: Optional[int] = None):
+        """Why these items: the TreeSHAP contribution of every ranking feature to the ranker score of each (user, item)
+        pair (LightGBMRanker.predict_contrib_device; definition at rihip_gbdt_predict_contrib in recommendit_hip.h).
+
+        item_ids: [nq, k] item ids per user, typically what recommend_batch just returned; only these pairs' features
+        are built (k rows per user, not top_k_candidates).  Returns contributions f64 [nq, k, F + 1] on the device, F =
+        len(ranker.feature_names), the expected value last: a pair's row sums to its ranker score.  Rows of padding
+        (item id -1) are zero.  With top=n also (indices i64 [nq, k, n], values f64 [nq, k, n]) of the n features of
+        largest |contribution| per pair, largest first.  A separate call after the serve chain: nothing is captured."""
+        uid = self._ids_to_device(user_ids)
+        items = torch.as_tensor(item_ids, dtype=torch.int64).to(uid.device)
+        if items.dim() != 2 or items.shape[0] != uid.shape[0]:
+            raise ValueError(f"explain_batch: item_ids must be [nq, k] with nq = {uid.shape[0]} users, got {tuple(items.shape)}")
+        nq, k = items.shape
+        nf = len(self.ranker.feature_names)
+        if top is not None and not 1 <= int(top) <= nf:
+            raise ValueError(f"explain_batch: top={top} outside 1..{nf}")
+        if nq == 0 or k == 0:
+            phi = torch.zeros((nq, k, nf + 1), dtype=torch.float64, device=uid.device)
+        else:
+            X = build_ranking_features_device(self.store, uid, items.contiguous(), self.ranker.feature_names)
+            phi = self.ranker.predict_contrib_device(X).view(nq, k, nf + 1)
+            phi = torch.where((items >= 0).unsqueeze(-1), phi, torch.zeros((), dtype=phi.dtype, device=phi.device))
+        if top is None:
+            return phi
+        idx = torch.topk(phi[..., :nf].abs(), int(top), dim=-1).indices
+        return phi, idx, torch.gather(phi[..., :nf], -1, idx)
+
     def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False,
-                            exclude_seen: Optional[bool] = None, item_filter=None, diversity=_DEFAULT
-                            ) -> List[Dict[str, Any]]:
+                            exclude_seen: Optional[bool] = None, item_filter=None, diversity=_DEFAULT,
+                            explain: Optional[int] = None) -> List[Dict[str, Any]]:
         """item_filter, diversity: as in recommend_batch (graph=True with a filter raises ValueError); with a diversity
-        the list is in selection order and "rank" is the position in it"""
+        the list is in selection order and "rank" is the position in it.  explain=n adds "contributions" to every
+        result: {feature name: contribution} of the n features that moved its score most (explain_batch)."""
         ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen, item_filter=item_filter,
                                            diversity=diversity)
+        why = None
+        if explain:
+            _, fi, fv = self.explain_batch([user_id], ids, top=int(explain))
+            names = list(self.ranker.feature_names)
+            why = [{names[j]: float(v) for j, v in zip(jr, vr)} for jr, vr in zip(fi[0].tolist(), fv[0].tolist())]
         out = []
         for rank, (i, s, r) in enumerate(zip(ids[0].tolist(), sc[0].tolist(), rs[0].tolist()), start=1):
             if i >= 0:
                 out.append({"item_id": int(i), "score": float(s), "rank": rank, "retrieval_score": float(r)})
+                if why is not None:
+                    out[-1]["contributions"] = why[rank - 1]
         return out
