@@ -1,7 +1,9 @@
-// Handle of the inner-product index shared by topk.hip (search) and ivf.hip (k-means, list layout, state I/O).
+// Handle of the inner-product index shared by the search (topk.hip and the kernel files behind search_kernels.h), ivf.hip
+// (k-means, list layout, state I/O) and index_update.hip.
 #pragma once
 #include "common.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace rihip_index {
@@ -15,7 +17,7 @@ template <typename T>
 struct DevBuf {
   T* p = nullptr;
   int64_t n = 0;
-  int reserve(int64_t want) {
+  __attribute__((noinline)) int reserve(int64_t want) {   // (one copy per element type for the driver's ~40 call sites)
     if (n >= want) return RIHIP_OK;
     if (p) { hipFree(p); rihip_bump_generation(); }   // a graph that captured the old pointer is stale now
     p = nullptr; n = 0;
@@ -69,7 +71,6 @@ struct IpIndex {
   // failed queries (unfiltered pass) into the same output rows
   bool defer_check = false, defer_ok = false;
   struct { bool active = false; const float* Q = nullptr; int64_t nq = 0; int k = 0; float* out_s = nullptr; int64_t* out_r = nullptr; } pending;
-  const int* redo_slots = nullptr;   // internal: search_chunk runs only the unfiltered IVF pass, results to these rows
   hipEvent_t ev_fail = nullptr;      // recorded behind the failure count's copy of a deferred search (not while capturing)
   bool ev_recorded = false;
 };
@@ -87,9 +88,19 @@ inline void free_index_arrays(IpIndex* h) {
   h->N = 0; h->Np = 0; h->ivf = false; h->nlist = 0; h->list_len.clear();
 }
 
+// The kernels are instantiated for the widths 32, 64 and 128: f(std::integral_constant<int, D>{}) for d == D.
+template <typename F>
+int dispatch_d(int d, F&& f) {
+  if (d == 32) f(std::integral_constant<int, 32>{});
+  else if (d == 64) f(std::integral_constant<int, 64>{});
+  else if (d == 128) f(std::integral_constant<int, 128>{});
+  else { rihip_set_error("ip_index: unsupported embed_dim=%d (32/64/128)", d); return RIHIP_ERR_SHAPE; }
+  return RIHIP_OK;
+}
+
 // zero-pad n rows of width du (device) into rows of width d (device)
 int pad_rows(const float* src, int64_t n, int du, int d, float* dst, hipStream_t st);
-// flat index: (re)build the bf16 filter copy and the row-norm bound (topk.hip)
+// flat index: (re)build the bf16 filter copy and the row-norm bound (scan_bf16.hip)
 int prepare_flat(IpIndex* h, hipStream_t st);
 // upload the per-list offsets/lengths the list-major scan reads (from the host copy list_len; ivf.hip)
 int derive_ivf_aux(IpIndex* h, hipStream_t st);

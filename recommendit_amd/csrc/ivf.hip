@@ -178,10 +178,9 @@ namespace rihip_index {
 int launch_assign(int d, const float* X, int64_t N, const float* C, int nlist, int* assign, hipStream_t st) {
   const int64_t nblk = (N + 127) / 128;
   const dim3 mg((unsigned)(nblk < 2048 ? nblk : 2048));
-  if (d == 128) hipLaunchKernelGGL((ivf_assign_mfma_kernel<128>), mg, dim3(256), 0, st, X, N, C, nlist, assign);
-  else if (d == 64) hipLaunchKernelGGL((ivf_assign_mfma_kernel<64>), mg, dim3(256), 0, st, X, N, C, nlist, assign);
-  else if (d == 32) hipLaunchKernelGGL((ivf_assign_mfma_kernel<32>), mg, dim3(256), 0, st, X, N, C, nlist, assign);
-  else { rihip_set_error("ip_index: unsupported embed_dim=%d (32/64/128)", d); return RIHIP_ERR_SHAPE; }
+  RCCHK(dispatch_d(d, [&](auto D) {
+    hipLaunchKernelGGL((ivf_assign_mfma_kernel<decltype(D)::value>), mg, dim3(256), 0, st, X, N, C, nlist, assign);
+  }));
   RIHIP_CHECK_LAUNCH();
   return RIHIP_OK;
 }

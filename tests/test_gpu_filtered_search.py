@@ -1,4 +1,4 @@
-"""GPU: filtered retrieval -- per-query tag predicates tested inside the index scan (csrc/topk.hip, FILT instantiations).
+"""GPU: filtered retrieval -- per-query tag predicates tested inside the index scan (csrc/scan_f32.hip and csrc/ivf_search.hip, FILT instantiations; driver: csrc/topk.hip).
 
 Every comparison is EQUALITY of scores and ids on every query, ties included.  Vectors, queries and injected centroids are
 small integers (-3..3) searched with normalized=True, so every inner product is exact in f32 and f64 alike.  The oracle

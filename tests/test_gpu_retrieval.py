@@ -225,11 +225,37 @@ def test_two_precision_search_equals_all_f32():
         assert set(r1[q]) == set(r2[q]) or np.abs(s1[q, -1] - s1[q, -2]) < 1e-6
 
 
-def test_wide_filter_equals_the_narrow_filter_and_all_f32(monkeypatch):
-    """`RIHIP_FILTER_WIDE=1` sends batches of more than 512 queries at d = 128 to the 1 024-query LDS-DMA filter
-    (`scan_bf16_wide_kernel`, an opt-in experiment: DESIGN.md section 9); it must hand the re-score the same survivors as
-    the 256-query filter: identical results, also on a corpus that is not a whole number of 64-row stages, with a partly
-    filled last query block and with self-matches."""
+@pytest.mark.parametrize("d", [32, 64, 128])
+@pytest.mark.parametrize("k", [2049, 4000])
+def test_two_precision_large_k_unfused_rescore(d, k):
+    """k > 2048 on a flat two-precision index (N > 65 536) takes the unfused re-score: the survivors' segments are
+    compacted, an approximate k-th score is selected, the survivors are re-scored in f32, selected and checked by
+    separate launches instead of the fused refinement.  At N = 66 000 the sample stride is 66 000 // 32 768 = 2, so
+    S = 33 000 sample rows, m = k * S / N = k / 2 and rank = ceil(1.5 * (m + 4 sqrt(m) + 4)); nine queries are one query
+    block, so the sample pass has min(2 * 256, ceil(33 000 / 64) = 516) = 512 corpus splits = 1 024 streams of 8 scores,
+    and the register top-T sample is taken while 4 * rank <= 8 192.
+      k = 2 049: m = 1 024.5, rank = 1 735, 4 * rank = 6 940 <= 8 192  ->  register top-T sample;
+      k = 4 000: m = 2 000,   rank = 3 275, 4 * rank = 13 100 > 8 192  ->  dense sample.
+    The result is the exact top-k and equals the all-f32 search."""
+    from recommendit_amd import FAISSIndex, _lib
+    rng = np.random.RandomState(1000 * d + k)
+    N, nq = 66_000, 9
+    X, Q = fx.unit_rows(rng, N, d), fx.unit_rows(rng, nq, d)
+    idx = FAISSIndex(embed_dim=d, exact=True)
+    idx.build_ivf_index(X, list(range(N)))
+    s2, r2 = idx.batch_search(Q, k=k)              # default: two-precision
+    _check_topk(s2, r2, Q, X, k)
+    _lib.check(_lib.lib().rihip_ip_index_set_two_precision(idx.index._h, 0))
+    s1, r1 = idx.batch_search(Q, k=k)              # all-f32
+    np.testing.assert_allclose(s2, s1, atol=1e-6, rtol=0)
+    for q in range(nq):
+        assert set(r1[q]) == set(r2[q]) or np.abs(s1[q, -1] - s1[q, -2]) < 1e-6, q
+
+
+def test_two_precision_partial_last_stage_and_query_block():
+    """The bf16 filter on a corpus that is not a whole number of 64-row stages, with a partly filled last query block
+    (700 = 2 x 256 + 188) and self-matches in the last (partial) stage: exact, equal to the all-f32 search, also at other k
+    (other thresholds / segment capacities) on the same index."""
     from recommendit_amd import FAISSIndex, _lib
     rng = np.random.RandomState(21)
     N, d, nq, k = 150_003, 128, 700, 500
@@ -237,26 +263,18 @@ def test_wide_filter_equals_the_narrow_filter_and_all_f32(monkeypatch):
     Q[:5] = X[-5:]                                 # self-matches in the last (partial) stage
     idx = FAISSIndex(embed_dim=d, exact=True)
     idx.build_ivf_index(X, list(range(N)))
-    sn, rn = idx.batch_search(Q, k=k)              # 256-query filter (the default)
-    monkeypatch.setenv("RIHIP_FILTER_WIDE", "1")
-    sw, rw = idx.batch_search(Q, k=k)              # wide filter
-    # the same survivors reach the exact re-score; its f32 summation order depends on where a candidate sits in its
-    # segment, so scores may differ in the last bit and near-ties may swap places: same SETS, scores to 1e-6
-    np.testing.assert_allclose(sw, sn, atol=1e-6, rtol=0)
-    for q in range(nq):
-        assert set(rw[q]) == set(rn[q]) or np.abs(sn[q, -1] - sn[q, -2]) < 1e-6, q
-    assert (rw == rn).mean() > 0.999
-    assert (rw[:5, 0] == np.arange(N - 5, N)).all()
+    s2, r2 = idx.batch_search(Q, k=k)              # default: two-precision
+    assert (r2[:5, 0] == np.arange(N - 5, N)).all()
     sel = rng.choice(nq, 32, replace=False)
-    _check_topk(sw[sel], rw[sel], Q[sel], X, k)
+    _check_topk(s2[sel], r2[sel], Q[sel], X, k)
     _lib.check(_lib.lib().rihip_ip_index_set_two_precision(idx.index._h, 0))
     s1, r1 = idx.batch_search(Q, k=k)              # all-f32
-    np.testing.assert_allclose(sw, s1, atol=1e-6, rtol=0)
-    assert (r1 == rw).mean() > 0.999
+    np.testing.assert_allclose(s2, s1, atol=1e-6, rtol=0)
+    assert (r1 == r2).mean() > 0.999
     for k2 in (10, 100):                           # other k (other thresholds / segment capacities) on the same index
         _lib.check(_lib.lib().rihip_ip_index_set_two_precision(idx.index._h, 1))
-        s2, r2 = idx.batch_search(Q, k=k2)
-        _check_topk(s2[sel], r2[sel], Q[sel], X, k2)
+        s3, r3 = idx.batch_search(Q, k=k2)
+        _check_topk(s3[sel], r3[sel], Q[sel], X, k2)
 
 
 def test_two_precision_scratch_reuse_across_batch_sizes():
@@ -314,6 +332,27 @@ def test_ivf_large_lists_thresholded_path():
     ref_sc, ref_rows = R.topk_ip_exact(Q, X, k)
     recall = np.mean([len(set(rows5[q]) & set(ref_rows[q])) / k for q in range(nq)])
     assert recall > 0.3, recall
+
+
+def test_ivf_thresholded_path_at_d32():
+    """The sampled-threshold IVF search at the narrowest kernel width.  With nprobe == nlist the result is the exact
+    top-k.  The three conditions that select the thresholded path (and not the unfiltered pass) are asserted from the
+    index's own list sizes."""
+    from recommendit_amd import FAISSIndex, _lib
+    rng = np.random.RandomState(32)
+    N, d, nq, k, nlist, nprobe = 120_000, 32, 80, 10, 4, 4
+    X, Q = fx.unit_rows(rng, N, d), fx.unit_rows(rng, nq, d)
+    ivf = FAISSIndex(embed_dim=d, n_lists=nlist, n_probe=nprobe)
+    ivf.build_ivf_index(X, list(range(N)), kmeans_iters=3)
+    sizes = np.empty(nlist, dtype=np.int64)
+    _lib.check(_lib.lib().rihip_ip_index_list_sizes(ivf.index._h, sizes.ctypes.data))
+    cap_full = int(np.sort(sizes)[::-1][:nprobe].sum())        # rows of the nprobe longest lists
+    cap_df = (int(sizes.max()) + 63) // 64 * 64 * nprobe       # dense slots of the unfiltered pass per query
+    assert cap_full > 16384
+    assert 4 * k <= cap_full / 16
+    assert nq * cap_df > 2 ** 23
+    sc, rows = ivf.batch_search(Q, k=k)
+    _check_topk(sc, rows, Q, X, k)
 
 
 @pytest.mark.parametrize("kind", ["flat_small", "flat_two_precision", "ivf"])

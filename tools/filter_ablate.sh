@@ -10,7 +10,7 @@ for so in "$@"; do
 import csv, glob
 f = glob.glob("$O/**/s_kernel_stats.csv", recursive=True)[0]
 for r in csv.DictReader(open(f)):
-    if "scan_bf16_kernel<128, 0>" in r["Name"] or "scan_bf16_wide" in r["Name"]:
+    if "scan_bf16_kernel<128, 0>" in r["Name"]:
         print(f"$so {r['Name'][:60]:60s} calls {r['Calls']:>4s} avg {float(r['AverageNs'])/1e3:8.1f} us min {float(r['MinNs'])/1e3:8.1f}")
 EOF
 done
