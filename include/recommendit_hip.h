@@ -297,7 +297,14 @@ int rihip_gather_rows(const float* table, int64_t n_rows, const int64_t* ids, in
  * early_stopping_rounds.  model_text receives a malloc'd LightGBM-format text model (free with rihip_free):
  * rihip_gbdt_create_from_text loads it.  history (host, nullable): [n_rounds][2][n_eval_at] NDCG of train / valid
  * (valid = NaN without a validation set).  Synchronous.  Algorithm and its NumPy restatement: csrc/gbdt_train.hip,
- * oracle/lambdamart_np.py (lightgbm itself is not available offline: parity unpinned). */
+ * oracle/lambdamart_np.py (lightgbm itself is not available offline: parity unpinned).
+ * The ideal DCG (gradients and NDCG) takes the labels from the highest LABEL down, so label_gain must be non-decreasing.
+ * Refused before anything is launched, reason in rihip_last_error: RIHIP_ERR_SHAPE for a group outside 1..16384;
+ * RIHIP_ERR_ARG for F outside 1..255, group sizes that do not sum to n, num_leaves outside 2..128, max_bin outside
+ * 2..255, truncation_level outside 1..32, n_label_gain outside 2..32, n_eval_at outside 1..8, an eval_at < 1,
+ * n_estimators / bin_sample / min_child_samples / early_stopping_rounds < 1, a learning_rate, feature_fraction or sigmoid
+ * that is not finite and > 0, a reg_alpha, reg_lambda or min_sum_hessian that is not finite and >= 0, hist_bits other
+ * than 0, 20, 40, and a label_gain that decreases (or holds a NaN). */
 typedef struct rihip_lambdamart_params {
   int num_leaves, n_estimators, min_child_samples, max_bin, truncation_level, early_stopping_rounds, lambdarank_norm,
       bin_sample;
@@ -317,6 +324,16 @@ int rihip_lambdamart_train(const float* X, const float* y, const int32_t* groups
                            const float* Xv, const float* yv, const int32_t* groups_v, int64_t nv, int ngv,
                            const rihip_lambdamart_params* params, const char* feature_names, char** model_text,
                            int* best_iteration, int* n_rounds, double* history, void* stream);
+/* The gradient pass of one boosting round on its own -- the code rihip_lambdamart_train runs, not a copy: the stable
+ * segmented sort of every query by descending score (+0.0 and -0.0 are one score), LambdarankNDCG::
+ * GetGradientsForOneQuery per query, and the scatter back to document order.  scores device f64 [n], labels device f32
+ * [n] (a label below 0 counts as 0, one above n_label_gain - 1 as n_label_gain - 1), groups HOST int32 [ng], label_gain
+ * HOST f64 [n_label_gain]; out: lam, hes device f64 [n] in document order, sorted device int32 [n]: the row (0 .. n-1)
+ * at every rank position, the queries one after another.  The checks of groups, n_label_gain, label_gain, sigmoid and
+ * truncation_level are the trainer's.  Synchronous. */
+int rihip_lambdarank_gradients(const double* scores, const float* labels, const int32_t* groups, int64_t n, int ng,
+                               const double* label_gain, int n_label_gain, double sigmoid, int truncation_level,
+                               int lambdarank_norm, double* lam, double* hes, int32_t* sorted, void* stream);
 void rihip_free(void* p);
 
 /* ---- inner-product index -------------------------------------------------------------------

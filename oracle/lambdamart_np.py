@@ -114,7 +114,9 @@ def bin_matrix(X: np.ndarray, bounds: List[np.ndarray], nanbin: Optional[Sequenc
 
 # ------------------------------------------------------------------ lambdarank objective
 def _max_dcg(labels: np.ndarray, k: int, gain: np.ndarray) -> float:
-    g = np.sort(gain[labels.astype(np.int64)])[::-1][:k]
+    """ideal DCG at k: the documents from the highest LABEL down (what the kernels do; equal to "by gain" exactly when
+    label_gain does not decrease, which is all the trainer accepts)"""
+    g = gain[np.sort(labels.astype(np.int64))[::-1][:k]]
     return float((g / np.log2(np.arange(g.size) + 2.0)).sum())
 
 

@@ -130,6 +130,8 @@ SIGNATURES = {
     "rihip_gbdt_predict_contrib": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp]),
     "rihip_lambdamart_train": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, c_i64, C.c_int, vp, C.c_char_p,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]),
+    "rihip_lambdarank_gradients": (C.c_int, [vp, vp, vp, c_i64, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp,
+                                             vp, vp]),
     "rihip_free": (None, [vp]),
     "rihip_sample_negatives": (C.c_int, [vp, c_i64, vp, c_i64, vp, c_i64, c_i64, C.c_uint64, C.c_int, vp, vp, vp]),
     "rihip_bpr_step_persistent_supported": (C.c_int, [c_i64, C.c_int, C.c_int]),

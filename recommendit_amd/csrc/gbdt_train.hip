@@ -21,7 +21,9 @@
 //   binning        <= 255 bins per feature, upper bounds from a strided sample of <= 200 000 rows (host), rows binned
 //                  on the device (one byte per value: 145 MB for ML-1M's 2.9 M x 50 ranking rows)
 //   gradients      one stable segmented radix sort of all query groups by score (rocPRIM), then one workgroup per
-//                  query: pairs (i < truncation_level, j > i) of different labels, fp64
+//                  query: pairs (i < truncation_level, j > i) of different labels, fp64 (gradient_pass(); also exported
+//                  on its own as rihip_lambdarank_gradients, which tests/test_gpu_lambdamart_kernels.py compares with a
+//                  long-double reference)
 //   histograms     (gq, hq, count) per (feature, bin) of a leaf in LDS (int32, 1024-row chunks), summed in int64;
 //                  smaller child built, larger child = parent - smaller
 //   split search   one wave per feature, prefix over the bins, gain = ThresholdL1(G)^2/(H+l2) in double
@@ -66,6 +68,7 @@ struct SplitInfo { double gain; int feature, bin; long long glq, hlq, cl; long l
 
 __device__ __forceinline__ uint64_t d2ord_desc(double v) {  // ascending radix order == descending score
   uint64_t u = (uint64_t)__double_as_longlong(v);
+  if ((u << 1) == 0) u = 0;   // -0.0 is the score +0.0 (std::stable_sort by '>' keeps the two in document order)
   u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
   return ~u;
 }
@@ -557,59 +560,135 @@ struct Tree {
   std::vector<double> thr, gain, leaf, int_val, int_w, leaf_w; std::vector<long long> leaf_cnt;
 };
 
-struct Dataset {
+// every device allocation of a call: freed when the call returns, on whichever path
+struct DeviceArena {
+  std::vector<void*> ptrs;
+  void* pinned = nullptr;
+  DeviceArena() = default;
+  DeviceArena(const DeviceArena&) = delete;
+  DeviceArena& operator=(const DeviceArena&) = delete;
+  ~DeviceArena() { for (void* q : ptrs) hipFree(q); if (pinned) hipHostFree(pinned); }
+  template <typename P> hipError_t get(P** p, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+    if (e == hipSuccess) ptrs.push_back(q);
+    *p = reinterpret_cast<P*>(q);
+    return e;
+  }
+};
+
+struct Dataset {   // (the memory belongs to the call's DeviceArena)
   int64_t n = 0; int ng = 0;
   uint8_t* Xb = nullptr; float* y = nullptr; double* score = nullptr; int64_t* goff = nullptr;
   uint64_t *key = nullptr, *key2 = nullptr; int *val = nullptr, *sorted = nullptr; void* temp = nullptr; size_t temp_bytes = 0;
   int* goff32b = nullptr; int* goff32e = nullptr;
   double* ndcg = nullptr;
-  void release() {
-    hipFree(Xb); hipFree(y); hipFree(score); hipFree(goff); hipFree(key); hipFree(key2); hipFree(val); hipFree(sorted);
-    hipFree(temp); hipFree(goff32b); hipFree(goff32e); hipFree(ndcg);
-  }
 };
 
-int make_dataset(Dataset* D, const float* X, const float* y, const int32_t* groups, int64_t n, int F, int ng,
-                 const double* d_ub, const int* d_nb, const int* d_nanbin, int nk, hipStream_t st) {
+// host only: every group 1..MAX_GROUP documents, the sizes sum to n
+int check_groups(const int32_t* groups, int64_t n, int ng, const char* who) {
+  int64_t tot = 0;
+  for (int q = 0; q < ng; ++q) {
+    RIHIP_REQUIRE(groups[q] > 0 && groups[q] <= MAX_GROUP, RIHIP_ERR_SHAPE, "%s: query group of %d documents (1..%d supported)", who, groups[q], MAX_GROUP);
+    tot += groups[q];
+  }
+  RIHIP_REQUIRE(tot == n && n < (1ll << 31), RIHIP_ERR_ARG, "%s: group sizes sum to %lld, n = %lld", who, (long long)tot, (long long)n);
+  return RIHIP_OK;
+}
+// host only: what the gradient pass needs of its arguments
+int check_grad_args(const double* label_gain, int n_label_gain, double sigmoid, int truncation_level, const char* who) {
+  RIHIP_REQUIRE(truncation_level >= 1 && truncation_level <= MAX_T, RIHIP_ERR_ARG, "%s: truncation_level in [1,%d]", who, MAX_T);
+  RIHIP_REQUIRE(label_gain && n_label_gain >= 2 && n_label_gain <= 32, RIHIP_ERR_ARG, "%s: label_gain of 2..32 entries", who);
+  RIHIP_REQUIRE(sigmoid > 0.0 && sigmoid <= 1.7976931348623157e308, RIHIP_ERR_ARG, "%s: sigmoid must be finite and > 0", who);
+  RIHIP_REQUIRE(label_gain[0] == label_gain[0], RIHIP_ERR_ARG, "%s: label_gain[0] is NaN", who);
+  for (int l = 1; l < n_label_gain; ++l)
+    RIHIP_REQUIRE(label_gain[l] >= label_gain[l - 1], RIHIP_ERR_ARG,
+                  "%s: label_gain[%d] < label_gain[%d] (the ideal DCG is taken in label order: gains must not decrease)", who, l, l - 1);
+  return RIHIP_OK;
+}
+
+// group offsets and the buffers of the segmented sort (the groups were checked by check_groups)
+int make_groups(Dataset* D, DeviceArena* A, const int32_t* groups, int64_t n, int ng, hipStream_t st) {
   D->n = n; D->ng = ng;
   std::vector<int64_t> off(ng + 1, 0);
   std::vector<int> ob(ng), oe(ng);
   for (int q = 0; q < ng; ++q) {
-    RIHIP_REQUIRE(groups[q] > 0 && groups[q] <= MAX_GROUP, RIHIP_ERR_SHAPE, "lambdamart: query group of %d documents (1..%d supported)", groups[q], MAX_GROUP);
     off[q + 1] = off[q] + groups[q];
     ob[q] = (int)off[q]; oe[q] = (int)off[q + 1];
   }
-  RIHIP_REQUIRE(off[ng] == n && n < (1ll << 31), RIHIP_ERR_ARG, "lambdamart: group sizes sum to %lld, n = %lld", (long long)off[ng], (long long)n);
-  TCHK(hipMalloc((void**)&D->Xb, (size_t)n * F));
-  TCHK(hipMalloc((void**)&D->y, sizeof(float) * n));
-  TCHK(hipMalloc((void**)&D->score, sizeof(double) * n));
-  TCHK(hipMalloc((void**)&D->goff, sizeof(int64_t) * (ng + 1)));
-  TCHK(hipMalloc((void**)&D->goff32b, sizeof(int) * ng));
-  TCHK(hipMalloc((void**)&D->goff32e, sizeof(int) * ng));
-  TCHK(hipMalloc((void**)&D->key, sizeof(uint64_t) * n));
-  TCHK(hipMalloc((void**)&D->key2, sizeof(uint64_t) * n));
-  TCHK(hipMalloc((void**)&D->val, sizeof(int) * n));
-  TCHK(hipMalloc((void**)&D->sorted, sizeof(int) * n));
-  TCHK(hipMalloc((void**)&D->ndcg, sizeof(double) * (size_t)ng * nk));
-  TCHK(hipMemcpyAsync(D->y, y, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-  TCHK(hipMemsetAsync(D->score, 0, sizeof(double) * n, st));
+  TCHK(A->get(&D->goff, sizeof(int64_t) * (ng + 1)));
+  TCHK(A->get(&D->goff32b, sizeof(int) * ng));
+  TCHK(A->get(&D->goff32e, sizeof(int) * ng));
+  TCHK(A->get(&D->key, sizeof(uint64_t) * n));
+  TCHK(A->get(&D->key2, sizeof(uint64_t) * n));
+  TCHK(A->get(&D->val, sizeof(int) * n));
+  TCHK(A->get(&D->sorted, sizeof(int) * n));
   TCHK(hipMemcpyAsync(D->goff, off.data(), sizeof(int64_t) * (ng + 1), hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(D->goff32b, ob.data(), sizeof(int) * ng, hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(D->goff32e, oe.data(), sizeof(int) * ng, hipMemcpyHostToDevice, st));
-  TCHK(hipStreamSynchronize(st));
-  hipLaunchKernelGGL(bin_rows_kernel, dim3((unsigned)((n * F + 255) / 256)), dim3(256), 0, st, X, n, F, d_ub, d_nb, d_nanbin, D->Xb);
-  TCHK(hipGetLastError());
+  TCHK(hipStreamSynchronize(st));   // the host vectors above must outlive the copies
   TCHK(rocprim::segmented_radix_sort_pairs(nullptr, D->temp_bytes, D->key, D->key2, D->val, D->sorted, (unsigned)n, (unsigned)ng,
                                            D->goff32b, D->goff32e, 0, 64, st));
-  TCHK(hipMalloc(&D->temp, D->temp_bytes ? D->temp_bytes : 16));
+  TCHK(A->get(&D->temp, D->temp_bytes));
+  return RIHIP_OK;
+}
+
+int make_dataset(Dataset* D, DeviceArena* A, const float* X, const float* y, const int32_t* groups, int64_t n, int F, int ng,
+                 const double* d_ub, const int* d_nb, const int* d_nanbin, int nk, hipStream_t st) {
+  TCHK(A->get(&D->Xb, (size_t)n * F));
+  TCHK(A->get(&D->y, sizeof(float) * n));
+  TCHK(A->get(&D->score, sizeof(double) * n));
+  TCHK(A->get(&D->ndcg, sizeof(double) * (size_t)ng * nk));
+  TCHK(hipMemcpyAsync(D->y, y, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+  TCHK(hipMemsetAsync(D->score, 0, sizeof(double) * n, st));
+  TRC(make_groups(D, A, groups, n, ng, st));
+  hipLaunchKernelGGL(bin_rows_kernel, dim3((unsigned)((n * F + 255) / 256)), dim3(256), 0, st, X, n, F, d_ub, d_nb, d_nanbin, D->Xb);
+  TCHK(hipGetLastError());
   return RIHIP_OK;
 }
 // stable sort of every query group by descending score -> D->sorted (document index per rank position)
 int sort_groups(Dataset* D, hipStream_t st) {
   hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)((D->n + 255) / 256)), dim3(256), 0, st, D->score, D->n, D->key, D->val);
+  TCHK(hipGetLastError());
   size_t tb = D->temp_bytes;
   TCHK(rocprim::segmented_radix_sort_pairs(D->temp, tb, D->key, D->key2, D->val, D->sorted, (unsigned)D->n, (unsigned)D->ng,
                                            D->goff32b, D->goff32e, 0, 64, st));
+  return RIHIP_OK;
+}
+// the dynamic LDS the kernels of this file ask for, granted once per process (a 16 384-document query takes 147 520 B)
+int grant_lds() {
+  static bool granted = false;
+  if (granted) return RIHIP_OK;
+  TCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(lambdarank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_GROUP * 9 + 64));
+  TCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(hist_kernel<int>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH * NBIN * 3 * 4));
+  TCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(hist_kernel<long long>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH * NBIN * 3 * 4));
+  granted = true;
+  return RIHIP_OK;
+}
+size_t grad_lds_bytes(const int32_t* groups, int ng) {
+  int mg = 1;
+  for (int q = 0; q < ng; ++q) mg = std::max(mg, (int)groups[q]);
+  return (size_t)mg * 9 + 64;
+}
+
+// The gradient pass of one boosting round (the trainer and rihip_lambdarank_gradients both run THIS): sort every query
+// by D->score, then after_sort(&go) -- the trainer evaluates its metrics on the fresh order there and clears `go` when
+// the run is over --, then the pair gradients in rank order (ga.lam / ga.hes) and their scatter to document order
+// (lam / hes) with the largest magnitudes in d_mx (enqueued, not waited for).
+template <typename AfterSort>
+int gradient_pass(Dataset* D, const GradArgs& ga, size_t grad_lds, double* lam, double* hes, unsigned long long* d_mx,
+                  hipStream_t st, AfterSort&& after_sort) {
+  TRC(sort_groups(D, st));
+  bool go = true;
+  TRC(after_sort(&go));
+  if (!go) return RIHIP_OK;
+  const int64_t n = D->n;
+  hipLaunchKernelGGL(lambdarank_kernel, dim3(D->ng), dim3(256), grad_lds, st, ga);
+  TCHK(hipGetLastError());
+  TCHK(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long) * 2, st));
+  hipLaunchKernelGGL(unsort_absmax_kernel, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st, ga.lam, ga.hes,
+                     D->sorted, n, lam, hes, d_mx);
+  TCHK(hipGetLastError());
   return RIHIP_OK;
 }
 int eval_ndcg(Dataset* D, const double* d_gain, int n_gain, const int* d_ks, int nk, std::vector<double>* out, hipStream_t st) {
@@ -664,6 +743,31 @@ std::string tree_to_text(const Tree& t, int index, double shrinkage) {
 
 extern "C" void rihip_free(void* p) { free(p); }
 
+extern "C" int rihip_lambdarank_gradients(const double* scores, const float* labels, const int32_t* groups, int64_t n, int ng,
+                                          const double* label_gain, int n_label_gain, double sigmoid, int truncation_level,
+                                          int lambdarank_norm, double* lam, double* hes, int32_t* sorted, void* stream) {
+  RIHIP_REQUIRE(scores && labels && groups && lam && hes && sorted && n > 0 && ng > 0, RIHIP_ERR_ARG, "lambdarank_gradients: bad arguments");
+  TRC(check_grad_args(label_gain, n_label_gain, sigmoid, truncation_level, "lambdarank_gradients"));
+  TRC(check_groups(groups, n, ng, "lambdarank_gradients"));
+  hipStream_t st = (hipStream_t)stream;
+  DeviceArena arena;
+  Dataset D;
+  D.score = const_cast<double*>(scores); D.y = const_cast<float*>(labels);   // the caller's: read only
+  TRC(make_groups(&D, &arena, groups, n, ng, st));
+  double *ls = nullptr, *hs = nullptr, *d_gain = nullptr; unsigned long long* d_mx = nullptr;
+  TCHK(arena.get(&ls, sizeof(double) * n)); TCHK(arena.get(&hs, sizeof(double) * n));
+  TCHK(arena.get(&d_gain, sizeof(double) * n_label_gain)); TCHK(arena.get(&d_mx, sizeof(unsigned long long) * 2));
+  TCHK(hipMemcpyAsync(d_gain, label_gain, sizeof(double) * n_label_gain, hipMemcpyHostToDevice, st));
+  TRC(grant_lds());
+  GradArgs ga;
+  ga.score = D.score; ga.label = D.y; ga.sorted = D.sorted; ga.goff = D.goff; ga.ng = ng; ga.gain_tab = d_gain;
+  ga.n_gain = n_label_gain; ga.sigmoid = sigmoid; ga.T = truncation_level; ga.norm = lambdarank_norm; ga.lam = ls; ga.hes = hs;
+  TRC(gradient_pass(&D, ga, grad_lds_bytes(groups, ng), lam, hes, d_mx, st, [](bool*) -> int { return RIHIP_OK; }));
+  TCHK(hipMemcpyAsync(sorted, D.sorted, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
+  TCHK(hipStreamSynchronize(st));
+  return RIHIP_OK;
+}
+
 extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int32_t* groups, int64_t n, int F, int ng,
                                       const float* Xv, const float* yv, const int32_t* groups_v, int64_t nv, int ngv,
                                       const rihip_lambdamart_params* p, const char* feature_names, char** model_text,
@@ -671,11 +775,26 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
   RIHIP_REQUIRE(X && y && groups && p && model_text && n > 0 && F > 0 && F <= 255 && ng > 0, RIHIP_ERR_ARG, "lambdamart_train: bad arguments");
   RIHIP_REQUIRE(p->num_leaves >= 2 && p->num_leaves <= 128 && p->n_estimators >= 1 && p->max_bin >= 2 && p->max_bin <= 255,
                 RIHIP_ERR_ARG, "lambdamart_train: num_leaves in [2,128], max_bin in [2,255]");
-  RIHIP_REQUIRE(p->truncation_level >= 1 && p->truncation_level <= MAX_T, RIHIP_ERR_ARG, "lambdamart_train: truncation_level in [1,%d]", MAX_T);
   RIHIP_REQUIRE(p->n_eval_at >= 1 && p->n_eval_at <= 8 && p->n_label_gain >= 2 && p->n_label_gain <= 32, RIHIP_ERR_ARG, "lambdamart_train: eval_at / label_gain sizes");
+  TRC(check_grad_args(p->label_gain, p->n_label_gain, p->sigmoid, p->truncation_level, "lambdamart_train"));
   RIHIP_REQUIRE(p->hist_bits == 0 || p->hist_bits == 20 || p->hist_bits == 40, RIHIP_ERR_ARG, "lambdamart_train: hist_bits = 20 or 40");
+  RIHIP_REQUIRE(p->bin_sample >= 1 && p->min_child_samples >= 1 && p->early_stopping_rounds >= 1, RIHIP_ERR_ARG,
+                "lambdamart_train: bin_sample %d, min_child_samples %d, early_stopping_rounds %d must be >= 1", p->bin_sample,
+                p->min_child_samples, p->early_stopping_rounds);
+  {
+    auto pos = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };          // finite and > 0 (false for NaN)
+    auto nonneg = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };
+    RIHIP_REQUIRE(pos(p->learning_rate), RIHIP_ERR_ARG, "lambdamart_train: learning_rate must be finite and > 0");
+    RIHIP_REQUIRE(pos(p->feature_fraction), RIHIP_ERR_ARG, "lambdamart_train: feature_fraction must be finite and > 0");
+    RIHIP_REQUIRE(nonneg(p->reg_alpha) && nonneg(p->reg_lambda) && nonneg(p->min_sum_hessian), RIHIP_ERR_ARG,
+                  "lambdamart_train: reg_alpha, reg_lambda, min_sum_hessian must be finite and >= 0");
+  }
+  for (int t = 0; t < p->n_eval_at; ++t)
+    RIHIP_REQUIRE(p->eval_at[t] >= 1, RIHIP_ERR_ARG, "lambdamart_train: eval_at[%d] = %d (must be >= 1)", t, p->eval_at[t]);
   hipStream_t st = (hipStream_t)stream;
   const bool has_valid = Xv && yv && groups_v && nv > 0 && ngv > 0;
+  TRC(check_groups(groups, n, ng, "lambdamart"));
+  if (has_valid) TRC(check_groups(groups_v, nv, ngv, "lambdamart"));
   const int nk = p->n_eval_at;
   // 2^40 levels: the sums of n values stay below 2^62 (fewer levels for more than 2^22 rows)
   int bits = p->hist_bits == 40 ? 40 : 20;
@@ -727,22 +846,23 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
       nb[f] = k;
     }
   }
+  DeviceArena arena;   // every device buffer below: freed on every return
   double* d_ub = nullptr; int* d_nb = nullptr; double* d_gain = nullptr; int* d_ks = nullptr; int* d_nanbin = nullptr;
-  TCHK(hipMalloc((void**)&d_ub, sizeof(double) * ub.size()));
-  TCHK(hipMalloc((void**)&d_nb, sizeof(int) * F));
-  TCHK(hipMalloc((void**)&d_nanbin, sizeof(int) * F));
+  TCHK(arena.get(&d_ub, sizeof(double) * ub.size()));
+  TCHK(arena.get(&d_nb, sizeof(int) * F));
+  TCHK(arena.get(&d_nanbin, sizeof(int) * F));
   TCHK(hipMemcpy(d_nanbin, nanbin.data(), sizeof(int) * F, hipMemcpyHostToDevice));
-  TCHK(hipMalloc((void**)&d_gain, sizeof(double) * p->n_label_gain));
-  TCHK(hipMalloc((void**)&d_ks, sizeof(int) * nk));
+  TCHK(arena.get(&d_gain, sizeof(double) * p->n_label_gain));
+  TCHK(arena.get(&d_ks, sizeof(int) * nk));
   TCHK(hipMemcpy(d_ub, ub.data(), sizeof(double) * ub.size(), hipMemcpyHostToDevice));
   TCHK(hipMemcpy(d_nb, nb.data(), sizeof(int) * F, hipMemcpyHostToDevice));
   TCHK(hipMemcpy(d_gain, p->label_gain, sizeof(double) * p->n_label_gain, hipMemcpyHostToDevice));
   TCHK(hipMemcpy(d_ks, p->eval_at, sizeof(int) * nk, hipMemcpyHostToDevice));
 
   Dataset T, V;
-  int rc = make_dataset(&T, X, y, groups, n, F, ng, d_ub, d_nb, d_nanbin, nk, st);
-  if (rc == RIHIP_OK && has_valid) rc = make_dataset(&V, Xv, yv, groups_v, nv, F, ngv, d_ub, d_nb, d_nanbin, nk, st);
-  if (rc) { T.release(); V.release(); hipFree(d_ub); hipFree(d_nb); hipFree(d_nanbin); hipFree(d_gain); hipFree(d_ks); return rc; }
+  int rc = make_dataset(&T, &arena, X, y, groups, n, F, ng, d_ub, d_nb, d_nanbin, nk, st);
+  if (rc == RIHIP_OK && has_valid) rc = make_dataset(&V, &arena, Xv, yv, groups_v, nv, F, ngv, d_ub, d_nb, d_nanbin, nk, st);
+  if (rc) return rc;
 
   // ---- training scratch
   const int NL = p->num_leaves;
@@ -753,27 +873,20 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
   int *d_feat = nullptr, *d_bin = nullptr, *d_lc = nullptr, *d_rc = nullptr;
   long long* hist = nullptr; long long* d_sum = nullptr; unsigned long long* d_mx = nullptr; unsigned char* d_used = nullptr;
   SplitInfo* d_split = nullptr; SplitInfo* d_featbest = nullptr; unsigned* d_done = nullptr;
-  hipMalloc((void**)&ls, sizeof(double) * n); hipMalloc((void**)&hs, sizeof(double) * n);
-  hipMalloc((void**)&lam, sizeof(double) * n); hipMalloc((void**)&hes, sizeof(double) * n);
-  hipMalloc(&gq, (wide ? 8 : 4) * (size_t)n); hipMalloc(&hq, (wide ? 8 : 4) * (size_t)n);
-  hipMalloc((void**)&rowsA, sizeof(int) * n); hipMalloc((void**)&rowsB, sizeof(int) * n);
-  hipMalloc((void**)&d_cur, sizeof(int) * 2 * 128);      // a cursor pair per split of a tree (num_leaves <= 128)
-  hipMalloc((void**)&hist, sizeof(long long) * HSZ * (size_t)NL); hipMalloc((void**)&d_sum, sizeof(long long) * 2);
-  hipMalloc((void**)&d_mx, sizeof(unsigned long long) * 2); hipMalloc((void**)&d_used, F);
-  hipMalloc((void**)&d_split, sizeof(SplitInfo) * 2);
-  hipMalloc((void**)&d_featbest, sizeof(SplitInfo) * 2 * (size_t)F); hipMalloc((void**)&d_done, sizeof(unsigned));
-  if (d_done) hipMemsetAsync(d_done, 0, sizeof(unsigned), st);
-  hipMalloc((void**)&d_feat, sizeof(int) * NL); hipMalloc((void**)&d_bin, sizeof(int) * NL);
-  hipMalloc((void**)&d_lc, sizeof(int) * NL); hipMalloc((void**)&d_rc, sizeof(int) * NL); hipMalloc((void**)&d_leafv, sizeof(double) * NL);
-  if (hipGetLastError() != hipSuccess || !d_cur || !d_leafv) { rihip_set_error("lambdamart_train: device allocation failed"); return RIHIP_ERR_HIP; }
-  const size_t grad_lds = [&] { int mg = 1; for (int q = 0; q < ng; ++q) mg = std::max(mg, (int)groups[q]); return (size_t)mg * 9 + 64; }();
-  static bool granted = false;
-  if (!granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lambdarank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_GROUP * 9 + 64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hist_kernel<int>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH * NBIN * 3 * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hist_kernel<long long>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH * NBIN * 3 * 4);
-    granted = true;
-  }
+  TCHK(arena.get(&ls, sizeof(double) * n)); TCHK(arena.get(&hs, sizeof(double) * n));
+  TCHK(arena.get(&lam, sizeof(double) * n)); TCHK(arena.get(&hes, sizeof(double) * n));
+  TCHK(arena.get(&gq, (wide ? 8 : 4) * (size_t)n)); TCHK(arena.get(&hq, (wide ? 8 : 4) * (size_t)n));
+  TCHK(arena.get(&rowsA, sizeof(int) * n)); TCHK(arena.get(&rowsB, sizeof(int) * n));
+  TCHK(arena.get(&d_cur, sizeof(int) * 2 * 128));      // a cursor pair per split of a tree (num_leaves <= 128)
+  TCHK(arena.get(&hist, sizeof(long long) * HSZ * (size_t)NL)); TCHK(arena.get(&d_sum, sizeof(long long) * 2));
+  TCHK(arena.get(&d_mx, sizeof(unsigned long long) * 2)); TCHK(arena.get(&d_used, (size_t)F));
+  TCHK(arena.get(&d_split, sizeof(SplitInfo) * 2));
+  TCHK(arena.get(&d_featbest, sizeof(SplitInfo) * 2 * (size_t)F)); TCHK(arena.get(&d_done, sizeof(unsigned)));
+  TCHK(hipMemsetAsync(d_done, 0, sizeof(unsigned), st));
+  TCHK(arena.get(&d_feat, sizeof(int) * NL)); TCHK(arena.get(&d_bin, sizeof(int) * NL));
+  TCHK(arena.get(&d_lc, sizeof(int) * NL)); TCHK(arena.get(&d_rc, sizeof(int) * NL)); TCHK(arena.get(&d_leafv, sizeof(double) * NL));
+  const size_t grad_lds = grad_lds_bytes(groups, ng);
+  TRC(grant_lds());
 
   auto build_hist = [&](int* rows, int64_t b0, int64_t len, long long* dst) -> int {
     TCHK(hipMemsetAsync(dst, 0, sizeof(long long) * HSZ, st));
@@ -797,7 +910,8 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
                        p->reg_lambda, p->min_child_samples, p->min_sum_hessian, split_order, slots, (const long long*)nullptr, -1, d_featbest, d_done);
   };
   SplitInfo* h_split = nullptr;   // pinned: the per-split read-back is on the critical path of the tree growth
-  if (hipHostMalloc((void**)&h_split, sizeof(SplitInfo) * 2) != hipSuccess) h_split = nullptr;
+  if (hipHostMalloc((void**)&h_split, sizeof(SplitInfo) * 2) != hipSuccess) { h_split = nullptr; (void)hipGetLastError(); }
+  arena.pinned = h_split;
 
   std::vector<Tree> trees;
   std::vector<double> hist_rows;      // [round][2][nk]
@@ -809,33 +923,32 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
   ga.n_gain = p->n_label_gain; ga.sigmoid = p->sigmoid; ga.T = p->truncation_level; ga.norm = p->lambdarank_norm; ga.lam = ls; ga.hes = hs;
   bool stop = false;
   for (int it = 0; it <= p->n_estimators && rc == RIHIP_OK; ++it) {
-    rc = sort_groups(&T, st);
-    if (rc) break;
-    if (it > 0) {   // metrics of the model with `it` trees
-      std::vector<double> tr, va;
-      rc = eval_ndcg(&T, d_gain, p->n_label_gain, d_ks, nk, &tr, st);
-      if (rc == RIHIP_OK && has_valid) { rc = sort_groups(&V, st); if (rc == RIHIP_OK) rc = eval_ndcg(&V, d_gain, p->n_label_gain, d_ks, nk, &va, st); }
-      if (rc) break;
-      for (int t = 0; t < nk; ++t) hist_rows.push_back(tr[t]);
-      for (int t = 0; t < nk; ++t) hist_rows.push_back(has_valid ? va[t] : NAN);
-      rounds = it;
-      if (has_valid) {
-        // lightgbm.early_stopping semantics (callback.py, first_metric_only=False): every validation metric keeps its
-        // own best score / best iteration; the metrics are visited in order and the FIRST one whose patience ran out
-        // stops the run and names best_iteration; a run that reaches n_estimators reports metric 0's best iteration
-        if (best_val.empty()) { best_val = va; best_itr.assign(nk, it); best_it = it; }
-        else for (int t = 0; t < nk && !stop; ++t) {
-          if (va[t] > best_val[t]) { best_val[t] = va[t]; best_itr[t] = it; }
-          else if (it - best_itr[t] >= p->early_stopping_rounds) { stop = true; best_it = best_itr[t]; }
-        }
-        if (!stop) best_it = best_itr[0];
-      } else best_it = it;
-    }
-    if (it == p->n_estimators || stop) break;
-    // ---- gradients
-    hipLaunchKernelGGL(lambdarank_kernel, dim3(ng), dim3(256), grad_lds, st, ga);
-    hipMemsetAsync(d_mx, 0, sizeof(unsigned long long) * 2, st);
-    hipLaunchKernelGGL(unsort_absmax_kernel, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st, ls, hs, T.sorted, n, lam, hes, d_mx);
+    // sort, the metrics of the model with `it` trees on the fresh order, then (unless the run ends here) the gradients
+    bool grads = false;
+    rc = gradient_pass(&T, ga, grad_lds, lam, hes, d_mx, st, [&](bool* go) -> int {
+      if (it > 0) {
+        std::vector<double> tr, va;
+        TRC(eval_ndcg(&T, d_gain, p->n_label_gain, d_ks, nk, &tr, st));
+        if (has_valid) { TRC(sort_groups(&V, st)); TRC(eval_ndcg(&V, d_gain, p->n_label_gain, d_ks, nk, &va, st)); }
+        for (int t = 0; t < nk; ++t) hist_rows.push_back(tr[t]);
+        for (int t = 0; t < nk; ++t) hist_rows.push_back(has_valid ? va[t] : NAN);
+        rounds = it;
+        if (has_valid) {
+          // lightgbm.early_stopping semantics (callback.py, first_metric_only=False): every validation metric keeps its
+          // own best score / best iteration; the metrics are visited in order and the FIRST one whose patience ran out
+          // stops the run and names best_iteration; a run that reaches n_estimators reports metric 0's best iteration
+          if (best_val.empty()) { best_val = va; best_itr.assign(nk, it); best_it = it; }
+          else for (int t = 0; t < nk && !stop; ++t) {
+            if (va[t] > best_val[t]) { best_val[t] = va[t]; best_itr[t] = it; }
+            else if (it - best_itr[t] >= p->early_stopping_rounds) { stop = true; best_it = best_itr[t]; }
+          }
+          if (!stop) best_it = best_itr[0];
+        } else best_it = it;
+      }
+      grads = *go = !(it == p->n_estimators || stop);
+      return RIHIP_OK;
+    });
+    if (rc || !grads) break;
     unsigned long long mxb[2];
     if (hipMemcpyAsync(mxb, d_mx, sizeof(mxb), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rihip_set_error("lambdamart_train: gradient pass failed: %s", hipGetErrorString(hipGetLastError())); rc = RIHIP_ERR_HIP; break; }
     double gm, hm; memcpy(&gm, &mxb[0], 8); memcpy(&hm, &mxb[1], 8);
@@ -987,11 +1100,6 @@ extern "C" int rihip_lambdamart_train(const float* X, const float* y, const int3
     trees.push_back(std::move(tree));
   }
   hipStreamSynchronize(st);
-  hipFree(ls); hipFree(hs); hipFree(lam); hipFree(hes); hipFree(gq); hipFree(hq); hipFree(rowsA); hipFree(rowsB); hipFree(d_cur);
-  hipFree(hist); hipFree(d_sum); hipFree(d_mx); hipFree(d_used); hipFree(d_split); hipFree(d_featbest); hipFree(d_done);
-  if (h_split) hipHostFree(h_split);
-  hipFree(d_feat); hipFree(d_bin); hipFree(d_lc); hipFree(d_rc); hipFree(d_leafv);
-  T.release(); V.release(); hipFree(d_ub); hipFree(d_nb); hipFree(d_nanbin); hipFree(d_gain); hipFree(d_ks);
   if (rc) return rc;
 
   // ---- LightGBM text model (Booster.save_model layout, src/models/ranker.py:203-209)
