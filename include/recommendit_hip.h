@@ -528,6 +528,43 @@ int rihip_exclude_topk(const float* scores, const int64_t* ids, int64_t nq, int 
                        const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items, int k,
                        float* out_scores, int64_t* out_ids, const int* out_slot, int* deficit, void* stream);
 
+/* ---- cold-start users: closed-form fold-in ------------------------------------------------------
+ * Not in the reference, which answers a user without a trained row with _popularity_recommendations only
+ * (src/serving/recommender.py:304-307, :393-410).  Gives such a user a query vector in the space the index searches
+ * and the ranking-feature row the ranker reads, from a rating history, in one launch.
+ * A cold user is a SLOT s in 0..nq-1 (not a user id).  Its history is row s of a CSR: hist_offsets i64 [nq + 1]
+ * (ascending, inside [0, n_entries]; a row outside reads as empty) into hist_items i32 / hist_ratings i32 [n_entries]:
+ * item ids ascending and unique inside a row (the convention of rihip_exclude_topk, so the row doubles as the slot's
+ * exclusion list), ratings 1..5.
+ * V f32 [n_rows, ldv >= d]: the item vectors as stored in the index, L2-normalised.  row_of i32 [n_ids]: item id -> row
+ * of V, a value outside [0, n_rows) = not stored.  mu f64 [d]: the mean of the stored vectors.  min_rating 1..5 (4 =
+ * the trainer's positive threshold).  weighting 0: w = 1; 1: w = r - (min_rating - 1).  beta in [0, 1].
+ * Per slot:
+ *   P = the entries with r >= min_rating, 0 <= item < n_ids and row_of[item] stored;  W = sum over P of w (an integer)
+ *   m = (sum over P of w * V[row_of[item]]) / W - beta * mu, accumulated in f64;  n = sqrt(sum_c m_c^2)
+ *   P empty or n < 1e-12: flags[s] = 1 and q[s] = 0;  otherwise flags[s] = 0 and q[s] = (float)(m / n).
+ * beta = 1: the gradient at u = 0 of sum_p E_n log sigmoid(u.v_p - u.v_n) with uniform negatives is 1/2 sum_p (v_p - mu),
+ * so q is the direction of one full-batch BPR step from the origin in tower-output space; beta = 0 is the plain mean
+ * of the liked items.
+ * rows f64 [nq, 24]: the slot's row in the user-table layout of rihip_rank_features_build, with the arithmetic of
+ * rihip_ltr_stats / rihip_ltr_finalize (integer accumulators: order-independent, bit-exact).  Valid entries are those
+ * with item >= 0 and a rating 1..5; cnt and sum run over all of them; row[0] = sum / cnt; row[1] =
+ * (double)(float)log1p(cnt); genre preference: every entry with r >= 4 (the reference's constant, not min_rating) and
+ * 0 < item < n_item_rows adds r - 3 to each genre g with item_tab[item, 5 + g] != 0 (item_tab f64 [n_item_rows, 23],
+ * nullable with n_item_rows = 0) and counts towards L; v_g = acc_g / L (0 when L = 0), divided by its L2 norm (sum of
+ * squares over g = 0..17 in order, each term a fused multiply-add) when that is > 0.  row[2..5] (recency, gender, age, occupation) = user_meta f64
+ * [nq, 4], or 0.5, 0, 0.3, 0.3 when it is NULL.  cnt = 0: the full defaults row (3.5, 0, 0.5, 0, 0.3, 0.3, zeros).
+ * err (device int, zeroed here, OR-ed): bit 0 = an item id < 0, bit 1 = a rating outside 1..5; such entries are
+ * skipped everywhere, and no id is used as an address before it is range-checked.
+ * 1 <= d <= 256; nq = 0 launches nothing; anything else out of range is RIHIP_ERR_ARG and nothing is launched.  One
+ * launch, no host synchronisation, no allocation, no atomics but the error word: capturable in a hipGraph, and two
+ * calls agree bit for bit. */
+int rihip_fold_in_users(const int64_t* hist_offsets, const int32_t* hist_items, const int32_t* hist_ratings, int64_t nq,
+                        int64_t n_entries, const float* V, int64_t n_rows, int64_t ldv, int d, const int32_t* row_of,
+                        int64_t n_ids, const double* mu, int min_rating, int weighting, double beta,
+                        const double* item_tab, int64_t n_item_rows, const double* user_meta, float* q, double* rows,
+                        int* flags, int* err, void* stream);
+
 /* ---- evaluation report ------------------------------------------------------------------------
  * Replaces the per-user loop of evaluate_model (src/evaluation/metrics.py:301-384) and the component functions it
  * calls: ndcg_at_k (:20-69, binary relevance), recall_at_k (:72-87), precision_at_k (:90-99), mrr (:104-118),

@@ -7,8 +7,9 @@ from .two_tower import ItemTower, TwoTowerModel, UserTower, N_GENRES  # noqa: F4
 from .faiss_index import FAISSIndex  # noqa: F401
 from .ranker import LightGBMRanker  # noqa: F401
 from .seen import SeenItems  # noqa: F401  (not in the reference: per-user exclusion of seen items, seen.py)
+from .coldstart import UserHistories  # noqa: F401  (not in the reference: cold-start users from rating histories, coldstart.py)
 from .rerank import mmr_rerank_device  # noqa: F401  (not in the reference: diversified top-k, rerank.py)
 from ._lib import have_gpu  # noqa: F401  (the switch a caller guards the swap with: INTEGRATION.md §1)
 
-__all__ = ["TwoTowerModel", "UserTower", "ItemTower", "FAISSIndex", "LightGBMRanker", "SeenItems", "mmr_rerank_device", "N_GENRES",
+__all__ = ["TwoTowerModel", "UserTower", "ItemTower", "FAISSIndex", "LightGBMRanker", "SeenItems", "UserHistories", "mmr_rerank_device", "N_GENRES",
            "have_gpu"]

@@ -142,6 +142,8 @@ SIGNATURES = {
     "rihip_rank_topk_diverse": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, c_i64, c_i64, C.c_int, C.c_int, C.c_double,
                                           vp, vp, vp, vp]),
     "rihip_exclude_topk": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp, c_i64, vp, C.c_int, vp, vp, vp, vp, vp]),
+    "rihip_fold_in_users": (C.c_int, [vp, vp, vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, vp, c_i64, vp, C.c_int, C.c_int,
+                                      C.c_double, vp, c_i64, vp, vp, vp, vp, vp, vp]),
     "rihip_eval_nparts": (C.c_int, []),
     "rihip_eval_topk": (C.c_int, [vp, c_i64, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, c_i64,
                                   vp, vp]),

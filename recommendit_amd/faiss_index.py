@@ -151,6 +151,7 @@ class FAISSIndex:
         self._deficit: Optional[torch.Tensor] = None
         self._tags: Optional[torch.Tensor] = None      # int32 bit patterns [ntotal] on the device, row order
         self._pred_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}   # shared predicates already on the device
+        self._vec_cache: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None   # item_vectors_device()
 
     @property
     def _item_id_to_faiss_idx(self) -> Dict[int, int]:
@@ -215,6 +216,7 @@ class FAISSIndex:
         self.item_ids = np.asarray(item_ids, dtype=np.int64)
         self._item_ids_dev = torch.from_numpy(self.item_ids).to(x_dev.device)
         self._tags = None
+        self._vec_cache = None
         logger.info("Index built: %d vectors, %d lists, probe=%d", self.index.ntotal, self.n_lists, self.n_probe)
 
     # -- live catalogue (faiss add_with_ids / remove_ids; not in the reference, which rebuilds offline) ----------
@@ -263,6 +265,7 @@ class FAISSIndex:
         if rc != 0 and bad_kind.value != 0:
             raise ValueError(L.lib().rihip_last_error().decode("utf-8", "replace"))
         L.check(rc, "ip_index_update")
+        self._vec_cache = None
         if n_dropped.value == 0 and n_add == 0:
             return 0, 0
         self._item_ids_dev = out[:n_total.value]
@@ -415,6 +418,25 @@ class FAISSIndex:
         x = np.empty((self.index.ntotal, self.embed_dim), dtype=np.float32)
         L.check(L.lib().rihip_ip_index_reconstruct(self.index._h, x.ctypes.data), "ip_index_reconstruct")
         return x
+
+    def item_vectors_device(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(V f32 [N, d], row_of i32 [max item id + 1], mu f64 [d]) on the device (not in the reference): the stored
+        vectors in row order, item id -> row (-1 = not stored) and the mean of the stored vectors -- the inputs of the
+        cold-start fold-in (coldstart.fold_in_users_device).  Built from the handle on the first call and kept until the
+        index is built, loaded or updated again, so an item removed from the live catalogue stops contributing."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        if self._vec_cache is None:
+            dev = self._item_ids_dev.device
+            ids = self.item_ids
+            if ids.shape[0] and (ids.min() < 0 or ids.max() >= 2 ** 31 - 1):
+                raise ValueError("item_vectors_device: item ids must lie in [0, 2**31 - 1) (row_of is indexed by item id)")
+            V = torch.from_numpy(self.reconstruct()).to(dev)
+            row_of = torch.full((int(ids.max()) + 1 if ids.shape[0] else 0,), -1, dtype=torch.int32, device=dev)
+            row_of[self._item_ids_dev] = torch.arange(ids.shape[0], dtype=torch.int32, device=dev)
+            mu = V.double().mean(0) if ids.shape[0] else torch.zeros(self.embed_dim, dtype=torch.float64, device=dev)
+            self._vec_cache = (V, row_of, mu)
+        return self._vec_cache
 
     def assign_lists(self, x_dev: torch.Tensor) -> torch.Tensor:
         """int32 [n] on device: arg-max-IP list of each f32 [n,d] device row (the IndexFlatIP quantizer)."""
@@ -696,6 +718,7 @@ class FAISSIndex:
         h = C.c_void_p()
         L.check(L.lib().rihip_ip_index_load(str(load_path).encode(), C.byref(h)), "ip_index_load")
         obj.index = _IndexHandle(h.value, obj)
+        obj._vec_cache = None
         obj.index.nprobe = meta["n_probe"]
         obj.item_ids = np.asarray(meta["item_ids"], dtype=np.int64)
         obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())

@@ -9,6 +9,7 @@ the caller for single requests (drop-in through the three model classes); this m
 """
 from __future__ import annotations
 
+import math
 import os
 
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -18,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import rerank as RR
+from .coldstart import UserHistories, fold_in_users_device
 from .faiss_index import FAISSIndex
 from .ranker import LightGBMRanker
 from .seen import SeenItems, overfetch_k, plan_overfetch
@@ -154,10 +156,13 @@ class GpuFeatureStore:
 
 
 def build_ranking_features_device(store: GpuFeatureStore, user_ids: torch.Tensor, cand_ids: torch.Tensor,
-                                  feature_names: Sequence[str]) -> torch.Tensor:
-    """X f32 [nq*kc, len(feature_names)] on device (the matrix ranker.predict would see)."""
+                                  feature_names: Sequence[str], user_tab: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """X f32 [nq*kc, len(feature_names)] on device (the matrix ranker.predict would see).  user_tab: a device f64
+    [n, 24] table that user_ids index instead of the store's user table (the transient rows of cold-start users)."""
     lib = L.lib()
     ut, it = store.device_tables()
+    if user_tab is not None:
+        ut = user_tab
     key = tuple(feature_names)
     col_map = store._col_maps.get(key) if hasattr(store, "_col_maps") else None
     if col_map is None or col_map.device != ut.device:   # one H2D copy per feature list, not per request
@@ -209,6 +214,8 @@ class GpuRecommendationPipeline:
         self.diversity_vectors = diversity_vectors
         self.seen = seen
         self._pin: Dict[int, Any] = {}
+        self._popularity: Optional[torch.Tensor] = None       # set_popularity's order (None: the default)
+        self._pop_default: Optional[Tuple[Any, Any, torch.Tensor]] = None
         self._defer = os.environ.get("RIHIP_SERVE_DEFER", "1") != "0"   # 0: exactness check inside the search (experiments)
         self._log: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None
         self.reset_feature_log(feature_log_rows)
@@ -423,8 +430,14 @@ class GpuRecommendationPipeline:
         return out, (self.index.last_fail_count() if deferred else 0)
 
     def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None, item_filter=None,
-               div=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        q = self.model.get_user_embeddings(uid, as_tensor=True)
+               div=None, q: Optional[torch.Tensor] = None, user_tab: Optional[torch.Tensor] = None,
+               seen: Optional[SeenItems] = None, log_uid: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """q, user_tab, seen, log_uid (the cold-start chain): precomputed normalised queries instead of the user tower,
+        a table uid indexes instead of the store's user table, the exclusion store uid indexes instead of the attached
+        one, and the user ids the feature log records instead of uid"""
+        if q is None:
+            q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
         if item_filter is None:
@@ -437,11 +450,11 @@ class GpuRecommendationPipeline:
             kc = min(self.top_k_candidates, self.index.index.ntotal)
             fs = torch.empty((nq, kc), dtype=torch.float32, device=cand.device)
             fc = torch.empty((nq, kc), dtype=torch.int64, device=cand.device)
-            self.index.filter_excluded(rs, cand, kc, self.seen, uid, fs, fc)
+            self.index.filter_excluded(rs, cand, kc, self.seen if seen is None else seen, uid, fs, fc)
             rs, cand = fs, fc
-        X = build_ranking_features_device(self.store, uid, cand, self.ranker.feature_names)
+        X = build_ranking_features_device(self.store, uid, cand, self.ranker.feature_names, user_tab)
         if log and self._log is not None:
-            self._append_log(X, uid, cand)
+            self._append_log(X, uid if log_uid is None else log_uid, cand)
         scores = self.ranker.predict_device(X)
         k = min(k, kc)
         if div is not None:
@@ -452,6 +465,153 @@ class GpuRecommendationPipeline:
         L.check(L.lib().rihip_rank_topk(scores.data_ptr(), cand.data_ptr(), rs.data_ptr(), nq, kc, k, ids.data_ptr(),
                                         top.data_ptr(), trs.data_ptr(), L.stream_ptr()), "rank_topk")
         return ids, top, trs
+
+    # ---- cold-start users (not in the reference beyond the popularity fallback) ------------------------------------
+    def set_popularity(self, item_ids) -> None:
+        """the order the popularity fallback serves (most popular first; the reference's _popularity_fallback list,
+        recommender.py:393-410); None = back to the default: the items stored in the index by the item table's
+        log_rating_count, descending, ties to the lower item id"""
+        if item_ids is None:
+            self._popularity = None
+            return
+        ids = np.asarray(item_ids.detach().cpu().numpy() if isinstance(item_ids, torch.Tensor) else item_ids,
+                         dtype=np.int64).reshape(-1)
+        if ids.shape[0] and ids.min() < 0:
+            raise ValueError("set_popularity: negative item id")
+        self._popularity = torch.from_numpy(ids.copy()).to(L.device())
+
+    def popularity_order(self) -> torch.Tensor:
+        """device i64 item ids, most popular first: what set_popularity set, else the default order (rebuilt when the
+        index or the item table changes)"""
+        if self._popularity is not None:
+            return self._popularity
+        ids, tab = self.index.item_ids, self.store.device_tables()[1]
+        c = self._pop_default
+        if c is None or c[0] is not ids or c[1] is not tab:
+            host = np.unique(np.asarray(ids, dtype=np.int64))
+            val = np.zeros(host.shape[0], dtype=np.float64)          # an id outside the table: the default row's 0.0
+            ok = (host >= 0) & (host < self.store.item.shape[0])
+            val[ok] = self.store.item[host[ok], 1]
+            order = np.lexsort((host, -val))
+            c = self._pop_default = (ids, tab, torch.from_numpy(host[order]).to(L.device()))
+        return c[2]
+
+    def _popularity_rows(self, hist: UserHistories, slots: np.ndarray, k: int, width: int, exclude_history: bool,
+                         item_filter) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """the reference's _popularity_recommendations for the slots `slots` of hist: the first k entries of the
+        popularity order that pass item_filter and (exclude_history) are not in the slot's history -> (ids i64, scores
+        f64 = 1 - rank / (k + 1), retrieval scores f32 = 0) [len(slots), width], -1 / -inf / -inf where the list runs out"""
+        dev = L.device()
+        pop = self.popularity_order()
+        if item_filter is None:         # nothing but a slot's own items can be skipped: a prefix of the order is enough
+            pop = pop[:width + (int(hist.counts[slots].max()) if exclude_history and slots.shape[0] else 0)]
+        nf, npop = int(slots.shape[0]), int(pop.shape[0])
+        ok = torch.ones((nf, npop), dtype=torch.bool, device=dev)
+        if item_filter is not None:
+            if self.index._tags is None:
+                raise ValueError("item_filter needs item tags: call set_item_tags() first")
+            from .faiss_index import item_filter_words
+            if isinstance(item_filter, torch.Tensor):
+                item_filter = item_filter.detach().cpu().numpy()
+            words = torch.from_numpy(item_filter_words(item_filter, hist.n)[slots].astype(np.int64)).to(dev)
+            _, row_of, _ = self.index.item_vectors_device()
+            row = torch.full_like(pop, -1)
+            inside = pop < row_of.shape[0]
+            row[inside] = row_of[pop[inside]].to(torch.int64)
+            tag = torch.where(row >= 0, self.index._tags[row.clamp(min=0)].to(torch.int64) & 0xFFFFFFFF,
+                              torch.zeros_like(pop))[None, :]          # an id that is not stored carries no tag
+            any_of, all_of, none_of = words[:, 0:1], words[:, 1:2], words[:, 2:3]
+            ok &= ((any_of == 0) | ((tag & any_of) != 0)) & ((tag & all_of) == all_of) & ((tag & none_of) == 0)
+        if exclude_history and npop:
+            off, items, _ = hist.host
+            cnt = hist.counts[slots]
+            local = np.repeat(np.arange(nf, dtype=np.int64), cnt)
+            pos = np.concatenate([np.arange(off[s], off[s + 1]) for s in slots]) if nf else np.zeros(0, np.int64)
+            keys = torch.from_numpy((local << 32) | items[pos.astype(np.int64)].astype(np.int64)).to(dev)
+            grid = (torch.arange(nf, device=dev, dtype=torch.int64)[:, None] << 32) | pop[None, :]
+            ok &= ~torch.isin(grid, keys)
+        ids = torch.full((nf, width), -1, dtype=torch.int64, device=dev)
+        rank = torch.cumsum(ok, dim=1) - 1                 # the 0-based position of every allowed entry in its list
+        r, c = torch.nonzero(ok & (rank < width), as_tuple=True)
+        ids[r, rank[r, c]] = pop[c]
+        # (on the host: a true f64 division, where a device tensor / scalar multiplies by the reciprocal)
+        score = torch.from_numpy(1.0 - np.arange(1, width + 1, dtype=np.float64) / np.float64(k + 1)).to(dev)
+        filled = ids >= 0
+        sc = torch.where(filled, score[None, :], torch.full((), -math.inf, dtype=torch.float64, device=dev))
+        rs = torch.where(filled, torch.zeros((), dtype=torch.float32, device=dev),
+                         torch.full((), -math.inf, dtype=torch.float32, device=dev))
+        return ids, sc, rs
+
+    @torch.no_grad()
+    def recommend_cold_batch(self, histories: UserHistories, k: Optional[int] = None, exclude_history: bool = True,
+                             item_filter=None, diversity=_DEFAULT, user_meta=None, labels=None, beta: float = 1.0,
+                             weighting: str = "uniform", min_rating: int = 4
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Serve users who have no trained row, from their rating histories (coldstart.UserHistories; slot s of the
+        batch is history s) -> (item ids i64, ranker scores f64, retrieval scores f32 [nq, k], fallback bool [nq]) on
+        the device.
+
+        Each history is folded in (coldstart.fold_in_users_device over the index's own vectors,
+        FAISSIndex.item_vectors_device: the definition is at rihip_fold_in_users) into a query vector and a transient
+        user-table row, and the serve chain runs on those: search, seen-item exclusion, features, ranker, top-k or MMR.
+        Not the reference's behaviour, and its retrieval quality is not pinned.
+        exclude_history: a slot is never recommended an item of its own history (the history doubles as its exclusion
+        list: one over-fetched search at the longest history, ValueError beyond the search limit as in recommend_batch).
+        item_filter, diversity: as in recommend_batch.  user_meta f64 [nq, 4]: recency, gender, age, occupation of the
+        slots (None = the serving defaults).  labels: the user ids the feature log records for the slots (default -1).
+        beta, weighting, min_rating: the fold-in's parameters.
+
+        fallback[s] = True: the slot has no usable history (no stored item rated >= min_rating, or a vanishing
+        direction) and was served the reference's _popularity_recommendations instead: the first k entries of
+        popularity_order() that pass item_filter and (exclude_history) are not in its history, score 1 - rank / (k + 1),
+        retrieval score 0, -1 padded; no diversity stage, nothing logged.  The chain runs eager with the search's
+        synchronous exactness check, like the item_filter branch of recommend_batch: there is no graph= option."""
+        if not isinstance(histories, UserHistories):
+            raise ValueError("recommend_cold_batch: histories must be a coldstart.UserHistories")
+        k = k or self.top_k_results
+        div = self._diversity_stage(diversity, k)
+        dev = L.device()
+        nq = histories.n
+        ntotal = self.index.index.ntotal
+        kc = min(self.top_k_candidates, ntotal)
+        width = min(k, kc)
+        if labels is not None:
+            labels = torch.as_tensor(labels, dtype=torch.int64).reshape(-1)
+            if labels.shape[0] != nq:
+                raise ValueError(f"{labels.shape[0]} labels for {nq} histories")
+        V, row_of, mu = self.index.item_vectors_device()
+        q, rows, flags = fold_in_users_device(histories, V, row_of, mu, min_rating, weighting, beta,
+                                              self.store.device_tables()[1], user_meta)
+        fallback = flags != 0
+        ids = torch.full((nq, width), -1, dtype=torch.int64, device=dev)
+        sc = torch.full((nq, width), -math.inf, dtype=torch.float64, device=dev)
+        rs = torch.full((nq, width), -math.inf, dtype=torch.float32, device=dev)
+        if nq == 0:
+            return ids, sc, rs, fallback
+        fb_host = fallback.cpu().numpy()
+        warm, cold = np.nonzero(~fb_host)[0], np.nonzero(fb_host)[0]
+        if warm.shape[0]:
+            whole = warm.shape[0] == nq
+            most = int(histories.counts[warm].max()) if exclude_history else 0
+            k_eff = overfetch_k(kc, most, ntotal, int(L.lib().rihip_ip_index_max_k())) if most else None
+            uid = torch.arange(nq, dtype=torch.int64, device=dev) if whole else torch.from_numpy(warm).to(dev)
+            log_uid = torch.full((warm.shape[0],), -1, dtype=torch.int64, device=dev) if labels is None \
+                else labels[torch.from_numpy(warm)].to(dev)
+            from .faiss_index import _sub_filter
+            out = self._chain(uid, k, k_eff=k_eff, div=div, q=q if whole else q[uid].contiguous(), user_tab=rows,
+                              item_filter=item_filter if item_filter is None or whole else _sub_filter(item_filter, uid),
+                              seen=histories.as_seen(), log_uid=log_uid)
+            if whole:
+                ids, sc, rs = out
+            else:
+                for dst, src in zip((ids, sc, rs), out):
+                    dst.index_copy_(0, uid, src)
+        if cold.shape[0]:
+            sel = torch.from_numpy(cold).to(dev)
+            for dst, src in zip((ids, sc, rs), self._popularity_rows(histories, cold, k, width, exclude_history,
+                                                                     item_filter)):
+                dst.index_copy_(0, sel, src)
+        return ids, sc, rs, fallback
 
     # ---- serving feature log -------------------------------------------------------------------------------------
     def reset_feature_log(self, rows: Optional[int] = None) -> None:
@@ -555,10 +715,25 @@ class GpuRecommendationPipeline:
 
     def get_recommendations(self, user_id: int, k: Optional[int] = None, graph: bool = False,
                             exclude_seen: Optional[bool] = None, item_filter=None, diversity=_DEFAULT,
-                            explain: Optional[int] = None) -> List[Dict[str, Any]]:
+                            explain: Optional[int] = None, history=None) -> List[Dict[str, Any]]:
         """item_filter, diversity: as in recommend_batch (graph=True with a filter raises ValueError); with a diversity
         the list is in selection order and "rank" is the position in it.  explain=n adds "contributions" to every
-        result: {feature name: contribution} of the n features that moved its score most (explain_batch)."""
+        result: {feature name: contribution} of the n features that moved its score most (explain_batch).
+
+        history=[(item id, rating), ...] (not in the reference): serve this rating history instead of user_id's trained
+        row (recommend_cold_batch of the one history; user_id is only what the feature log records; exclude_seen=False
+        keeps the history's own items in; graph and explain are not offered).  Every result then carries "cold": True,
+        and "fallback": True when the history was unusable and the popularity list was served."""
+        if history is not None:
+            if graph or explain:
+                raise ValueError("get_recommendations(history=...) runs the eager cold-start chain: no graph=, no explain=")
+            ids, sc, rs, fb = self.recommend_cold_batch(UserHistories.from_lists([list(history)]), k,
+                                                        exclude_history=exclude_seen is not False,
+                                                        item_filter=item_filter, diversity=diversity, labels=[user_id])
+            fell = bool(fb[0].item())
+            return [{"item_id": int(i), "score": float(s), "rank": rank, "retrieval_score": float(r), "cold": True,
+                     "fallback": fell}
+                    for rank, (i, s, r) in enumerate(zip(ids[0].tolist(), sc[0].tolist(), rs[0].tolist()), start=1) if i >= 0]
         ids, sc, rs = self.recommend_batch([user_id], k, graph=graph, exclude_seen=exclude_seen, item_filter=item_filter,
                                            diversity=diversity)
         why = None
