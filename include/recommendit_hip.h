@@ -198,6 +198,36 @@ int rihip_inbatch_sweep(int mode_user, const float* owners, int64_t n_owner, int
                         int precision, void* stream);
 int rihip_sum_partials(const double* part, int64_t n, double scale, float* out, void* stream);
 
+/* In-batch sampled softmax with temperature, logQ correction and accidental-hit masking (not in the reference).
+ * A row's global index is its offset argument plus its local index; user i (global gu = user_goff + i) has the item of
+ * global index gu as its positive partner.
+ *   logit    l_ij = inv_temp <u_i, y_j> - logq_j    logq: nullable float[n_items] (NULL = 0); applies to the diagonal too
+ *   mask     pair (i, j) is dropped iff the id arrays are given, j is not i's partner and item_ids[j] == user_pos_ids[i]
+ *            (user_pos_ids[i] = id of i's positive; both int64, NULL together); the diagonal is never masked
+ *   softmax  lse_i = log sum_{j unmasked} exp(l_ij);  p_ij = exp(l_ij - lse_i), 0 where masked
+ *   loss     (1/n_global) sum_i (lse_i - l_ii)
+ *   d_users[i] = (inv_temp/n_global) (sum_j p_ij y_j - y_partner)
+ *   d_items[j] = (inv_temp/n_global) (sum_i p_ij u_i - u_partner)
+ * Finite and accurate for any finite logits (a running row maximum is subtracted; nothing relies on unit rows).
+ * rihip_inbatch_softmax_user_sweep: owners = users, swept = items.  Writes d_users, lse[n_users] and
+ *   rihip_inbatch_softmax_loss_parts(n_users) doubles to loss_part (loss = rihip_sum_partials with scale 1/n_global).
+ *   Every user's partner must lie inside the swept items (item_goff <= user_goff and user_goff + n_users <=
+ *   item_goff + n_items), else RIHIP_ERR_ARG: a log-sum-exp over a slice of the items is meaningless.
+ * rihip_inbatch_softmax_item_sweep: owners = items, swept = users.  Reads lse[n_users] and user_pos_ids[n_users] of the
+ *   swept users, logq[n_items] and item_ids[n_items] of its owners; writes d_items.  An item whose partner user lies
+ *   outside the swept users gets no -u_partner term, so d_items is additive over slices of the users.
+ * d: any multiple of 16 up to 256 (exact-f32 MFMA).  inv_temp finite and > 0.  One launch each, no atomics, no host
+ * synchronisation: bitwise reproducible and capturable in a graph. */
+int64_t rihip_inbatch_softmax_loss_parts(int64_t n_users);
+int rihip_inbatch_softmax_user_sweep(const float* users, int64_t n_users, int64_t user_goff, const float* items,
+                                     int64_t n_items, int64_t item_goff, int d, float inv_temp, const float* logq,
+                                     const int64_t* user_pos_ids, const int64_t* item_ids, int64_t n_global,
+                                     float* d_users, float* lse, double* loss_part, void* stream);
+int rihip_inbatch_softmax_item_sweep(const float* items, int64_t n_items, int64_t item_goff, const float* users,
+                                     int64_t n_users, int64_t user_goff, int d, float inv_temp, const float* logq,
+                                     const int64_t* item_ids, const int64_t* user_pos_ids, const float* lse,
+                                     int64_t n_global, float* d_items, void* stream);
+
 /* Stored-G form of the same loss (two_tower.py:132-160), the default when memory allows: the user pass is the
  * mode_user=1 sweep that ALSO writes the weights sigma(s_ij - s_ii) (0 on the diagonal; G = weight/(B(B-1))) to `gmat`
  * (rihip_inbatch_gmat_floats(n_users, n_items) floats, 32x32-blocked G^T); the item pass is then a plain exact-f32

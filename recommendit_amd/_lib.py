@@ -48,6 +48,11 @@ SIGNATURES = {
     "rihip_inbatch_sweep": (C.c_int, [C.c_int, vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, vp, vp, c_i64, vp, vp, vp,
                                       vp, C.c_int, vp]),
     "rihip_sum_partials": (C.c_int, [vp, c_i64, C.c_double, vp, vp]),
+    "rihip_inbatch_softmax_loss_parts": (c_i64, [c_i64]),
+    "rihip_inbatch_softmax_user_sweep": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, C.c_float, vp, vp, vp,
+                                                   c_i64, vp, vp, vp, vp]),
+    "rihip_inbatch_softmax_item_sweep": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, C.c_float, vp, vp, vp,
+                                                   vp, c_i64, vp, vp]),
     "rihip_inbatch_gmat_floats": (c_i64, [c_i64, c_i64]),
     "rihip_inbatch_user_pass": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, vp, c_i64, vp, vp, vp, vp, vp,
                                           C.c_int, vp]),

@@ -169,16 +169,32 @@ class UserItemDataset:
                                "item as the negative (a user rated almost the whole catalogue)", n_bad)
 
 
+def item_log_q(item_ids: np.ndarray, n_rows: int) -> np.ndarray:
+    """logQ of the in-batch softmax: log(count_j / n) for every item-table row j, counted over the n training pairs
+    ``item_ids`` that batches are drawn from (a row's item appears as an in-batch negative with that probability).  A
+    row that never appears gets the log of the smallest positive probability."""
+    cnt = np.bincount(np.asarray(item_ids, dtype=np.int64), minlength=n_rows).astype(np.float64)
+    assert len(cnt) == n_rows and cnt.sum() > 0
+    prob = cnt / cnt.sum()
+    prob[cnt == 0] = prob[cnt > 0].min()
+    return np.log(prob).astype(np.float32)
+
+
 class EmbeddingTrainer:
     def __init__(self, data_dir: str = "data/ml-1m", model_output_path: str = "models/two_tower.pt",
                  embed_dim: int = 64, epochs: int = 10, batch_size: int = 1024, learning_rate: float = 1e-3,
                  device: Optional[str] = None, loss_mode: str = "sampled", table_opt: str = "dense",
-                 dropout: float = 0.1, seed: int = 0):
+                 dropout: float = 0.1, seed: int = 0, temperature: float = 0.05, logq_correction: bool = True,
+                 mask_duplicates: bool = True):
         """Defaults = the reference's settings (src/config.py:13,:24-26); `device` is accepted for
-        signature compatibility -- training always runs on the HIP device."""
+        signature compatibility -- training always runs on the HIP device.
+        loss_mode="softmax" (not in the reference): in-batch sampled softmax with `temperature` (0.05 is a customary
+        starting value, not a measured optimum), the logQ correction from the training pairs' item counts
+        (item_log_q) and masking of duplicate items in a batch."""
         self.data_dir, self.model_output_path = data_dir, model_output_path
         self.embed_dim, self.epochs, self.batch_size, self.learning_rate = embed_dim, epochs, batch_size, learning_rate
         self.loss_mode, self.table_opt, self.dropout, self.seed = loss_mode, table_opt, dropout, seed
+        self.temperature, self.logq_correction, self.mask_duplicates = temperature, logq_correction, mask_duplicates
         self.device = L.device()
         self.history: List[Dict] = []
 
@@ -196,8 +212,12 @@ class EmbeddingTrainer:
         dataset = UserItemDataset(ratings_df, item_genre_dict, all_item_ids)
         torch.manual_seed(self.seed)
         model = TwoTowerModel(n_users, n_items, embed_dim=self.embed_dim, hidden_dim=128, dropout=self.dropout)
+        extra = {}
+        if self.loss_mode == "softmax":
+            logq = torch.from_numpy(item_log_q(dataset.item_ids, n_items + 1)) if self.logq_correction else None
+            extra = dict(temperature=self.temperature, item_logq=logq, mask_duplicates=self.mask_duplicates)
         trainer = HipBPRTrainer(model, self.batch_size, lr=self.learning_rate, weight_decay=1e-5, max_norm=1.0,
-                                loss_mode=self.loss_mode, table_opt=self.table_opt, seed=self.seed)
+                                loss_mode=self.loss_mode, table_opt=self.table_opt, seed=self.seed, **extra)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(self.seed)
         Path(self.model_output_path).parent.mkdir(parents=True, exist_ok=True)

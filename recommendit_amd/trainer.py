@@ -11,7 +11,8 @@ Two optimiser modes for the embedding tables:
 MLP parameters are always dense (one flat buffer: one grad-norm pass + one Adam launch).
 
 Two loss modes: ``sampled`` (one explicit negative per positive -- what the reference trains
-with) and ``inbatch`` (TwoTowerModel.in_batch_bpr_loss, never called by the reference trainer).
+with) and ``inbatch`` (TwoTowerModel.in_batch_bpr_loss, never called by the reference trainer).  ``softmax`` (not in the
+reference): the in-batch sampled softmax with temperature, logQ correction and duplicate masking.
 
 Multi-GPU (one process per GPU, torch.distributed/RCCL; opt-in with ``distributed=True``): user rows are sharded
 (each rank trains pairs whose user row it owns: zero communication for user rows).  The item table is either
@@ -114,7 +115,8 @@ class HipBPRTrainer:
                  table_opt: str = "dense", seed: int = 0, process_group=None, user_row_offset: int = 0,
                  inbatch_precision: int = 0, use_graph: bool = False, inbatch_store_g=None,
                  distributed: bool = False, item_shard: str = "replicate", exchange_cap: Optional[int] = None,
-                 persistent: Optional[bool] = None):
+                 persistent: Optional[bool] = None, temperature: float = 0.05,
+                 item_logq: Optional[torch.Tensor] = None, mask_duplicates: bool = True):
         """distributed=True (or a process_group): this trainer is one rank of a collective job -- EVERY rank of the
         group must construct it and call step() in lock-step.  Default False even when torch.distributed is
         initialised, so that a single-rank trainer inside a distributed program never issues collectives.
@@ -127,8 +129,20 @@ class HipBPRTrainer:
         Opt-in: measured on MI355X it is SLOWER than the seven launches today (0.124 vs 0.074 ms at the ML-1M
         B = 256 shape: each of the three grid barriers needs an L2 write-back + invalidate across the 8 XCDs, and the
         runtime-shape tile code it is built from is latency-bound) -- see DESIGN.md §9.  None / False = the multi-launch
-        path."""
-        assert loss_mode in ("sampled", "inbatch") and table_opt in ("dense", "sparse")
+        path.
+        loss_mode="softmax": in-batch sampled softmax (rihip_inbatch_softmax_*) in place of the in-batch BPR passes;
+        step() takes the same [B] ids as "inbatch".  temperature divides the cosine scores (0.05 is a customary starting
+        value, not a measured optimum); item_logq: f32 tensor over the item table's rows, log of each item's sampling
+        probability, gathered by the step's item ids on the device (the logQ correction; None = none);
+        mask_duplicates: rows whose item equals another row's positive are dropped from that row's softmax.  Single GPU
+        for now."""
+        assert loss_mode in ("sampled", "inbatch", "softmax") and table_opt in ("dense", "sparse")
+        if loss_mode == "softmax":
+            if not (temperature > 0):
+                raise ValueError(f"HipBPRTrainer: temperature must be > 0, got {temperature}")
+            if distributed or process_group is not None:
+                raise ValueError("HipBPRTrainer: loss_mode='softmax' is single-GPU for now (the rectangular "
+                                 "rihip_inbatch_softmax_* entries are ready; the multi-GPU trainer wiring is not)")
         assert item_shard in ("replicate", "rows")
         self.lib = L.lib()
         self.model = model
@@ -243,6 +257,18 @@ class HipBPRTrainer:
                                     self.lib.rihip_inbatch_workspace_floats(Gall, B, d)),), **f32)
         self.n_lparts = self.lib.rihip_inbatch_loss_parts(B, Gall)
         self.gmat = None
+        if loss_mode == "softmax":
+            self.inv_temp = 1.0 / float(temperature)
+            self.mask_duplicates = bool(mask_duplicates)
+            self.item_logq = None
+            if item_logq is not None:
+                self.item_logq = item_logq.to(device=self.dev, dtype=torch.float32).contiguous()
+                if self.item_logq.shape != (self.itab.shape[0],):
+                    raise ValueError(f"item_logq must have one entry per item-table row ({self.itab.shape[0]}), got "
+                                     f"{tuple(self.item_logq.shape)}")
+                self.logq_b = torch.empty((B,), **f32)
+            self.lse = torch.empty((B,), **f32)
+            self.n_lparts = self.lib.rihip_inbatch_softmax_loss_parts(B)
         if loss_mode == "inbatch":
             self.pos = torch.empty((B,), **f32); self.r = torch.empty((B,), **f32)
             # stored-G form (exact f32 only): G^T of the local users x all items stays in HBM between the two passes
@@ -487,6 +513,8 @@ class HipBPRTrainer:
             if self.dist:  # mean over the global batch
                 self.dU.div_(self.world); self.dI.div_(self.world)
                 self.loss.div_(self.world)   # (summed over the ranks together with the squared norms below)
+        elif self.loss_mode == "softmax":
+            self._softmax(item_ids, st)
         else:
             self._inbatch(st)
 
@@ -708,6 +736,22 @@ class HipBPRTrainer:
             self._loss_fold = None   # (summed over the ranks together with the squared norms in step())
         else:   # summed by the clip-coefficient launch
             self._loss_fold = (self.lpart.data_ptr(), self.n_lparts, 1.0 / (G * (G - 1.0)))
+
+
+    def _softmax(self, item_ids: torch.Tensor, st: int) -> None:
+        """in-batch sampled softmax: the two sweeps fill dU, dI and the loss partials that the clip-coefficient launch sums"""
+        lib, B, d = self.lib, self.B, self.d
+        lq = None
+        if self.item_logq is not None:
+            torch.index_select(self.item_logq, 0, item_ids, out=self.logq_b)
+            lq = self.logq_b.data_ptr()
+        ids = item_ids.data_ptr() if self.mask_duplicates else None
+        self._timed(lib.rihip_inbatch_softmax_user_sweep, "inbatch_softmax_user_sweep", self.U.data_ptr(), B, 0,
+                    self.I.data_ptr(), B, 0, d, self.inv_temp, lq, ids, ids, B, self.dU.data_ptr(), self.lse.data_ptr(),
+                    self.lpart.data_ptr(), st)
+        self._timed(lib.rihip_inbatch_softmax_item_sweep, "inbatch_softmax_item_sweep", self.I.data_ptr(), B, 0,
+                    self.U.data_ptr(), B, 0, d, self.inv_temp, lq, ids, ids, self.lse.data_ptr(), B, self.dI.data_ptr(), st)
+        self._loss_fold = (self.lpart.data_ptr(), self.n_lparts, 1.0 / B)
 
 
 def cosine_lr(lr0: float, epoch: int, t_max: int) -> float:

@@ -246,6 +246,50 @@ class _InBatchFn(torch.autograd.Function):
         return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1])
 
 
+def softmax_loss_and_grads(U: torch.Tensor, I: torch.Tensor, inv_temp: float, logq: Optional[torch.Tensor] = None,
+                           item_ids: Optional[torch.Tensor] = None):
+    """Single-GPU in-batch sampled softmax (include/recommendit_hip.h: rihip_inbatch_softmax_*), square form: U, I [B,d],
+    row i of I is user i's positive, n_global = B, user_pos_ids = item_ids.  Returns (loss, dU, dI, lse) on the device;
+    two launches and the partial sum, no host synchronisation."""
+    lib = L.lib()
+    dev = L.device()
+    Uc, Ic = L.f32c(U), L.f32c(I)
+    B, d = Uc.shape
+    lq = None if logq is None else L.f32c(logq).reshape(-1)
+    ids = None if item_ids is None else L.i64c(item_ids).reshape(-1)
+    if (lq is not None and lq.numel() != B) or (ids is not None and ids.numel() != B):
+        raise ValueError(f"logq and item_ids must have one entry per row of the batch ({B})")
+    st = L.stream_ptr()
+    dU, dI = torch.empty_like(Uc), torch.empty_like(Ic)
+    lse = torch.empty((B,), dtype=torch.float32, device=dev)
+    nparts = lib.rihip_inbatch_softmax_loss_parts(B)
+    part = torch.empty((nparts,), dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    L.check(lib.rihip_inbatch_softmax_user_sweep(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, inv_temp, L.ptr(lq),
+                                                 L.ptr(ids), L.ptr(ids), B, dU.data_ptr(), lse.data_ptr(),
+                                                 part.data_ptr(), st), "inbatch_softmax_user_sweep")
+    L.check(lib.rihip_inbatch_softmax_item_sweep(Ic.data_ptr(), B, 0, Uc.data_ptr(), B, 0, d, inv_temp, L.ptr(lq),
+                                                 L.ptr(ids), L.ptr(ids), lse.data_ptr(), B, dI.data_ptr(), st),
+            "inbatch_softmax_item_sweep")
+    L.check(lib.rihip_sum_partials(part.data_ptr(), nparts, 1.0 / B, loss.data_ptr(), st), "sum_partials")
+    return loss, dU, dI, lse
+
+
+class _InBatchSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, I, inv_temp, logq, item_ids):
+        loss, dU, dI, _ = softmax_loss_and_grads(U, I, inv_temp, logq, item_ids)
+        ctx.save_for_backward(dU, dI)
+        ctx.in_devs = (U.device, I.device)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dU, dI = ctx.saved_tensors
+        g = g.to(dU.device)
+        return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None, None, None
+
+
 class TwoTowerModel(nn.Module):
     """two_tower.py:75-251 with HIP towers / losses."""
 
@@ -278,6 +322,21 @@ class TwoTowerModel(nn.Module):
         """two_tower.py:132-160 (closed form of the per-row python loop)."""
         in_dev = user_emb.device
         loss = _InBatchFn.apply(user_emb, item_emb)
+        return loss if in_dev.type == "cuda" else loss.to(in_dev)
+
+    def in_batch_softmax_loss(self, user_emb, item_emb, temperature: float = 0.05, logq=None, item_ids=None
+                              ) -> torch.Tensor:
+        """In-batch sampled softmax (not in the reference): mean over the rows of -log softmax_j(l_ij)[i] with
+        l_ij = <u_i, y_j> / temperature - logq[j].  ``logq`` [B]: log of each row's item's sampling probability (the
+        logQ correction; None = none).  ``item_ids`` [B]: another row that carries the same item as row i's positive is
+        dropped from row i's softmax (None = no masking).  temperature = 0.05 is a customary starting value for
+        L2-normalised towers, not a measured optimum."""
+        if not (temperature > 0):
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if user_emb.shape[0] < 1 or user_emb.shape != item_emb.shape:
+            raise ValueError("in_batch_softmax_loss needs user_emb and item_emb of the same shape [B >= 1, d]")
+        in_dev = user_emb.device
+        loss = _InBatchSoftmaxFn.apply(user_emb, item_emb, 1.0 / float(temperature), logq, item_ids)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     # -- inference helpers (two_tower.py:166-210) ---------------------------------------------
