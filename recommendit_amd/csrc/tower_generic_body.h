@@ -163,6 +163,7 @@ __device__ __forceinline__ void gen_bwd_data_tile(const GenBwd& g, float* smem, 
       dot += __shfl_xor(dot, 1, 64);
       dot += __shfl_xor(dot, 2, 64);
       dot += __shfl_xor(dot, 4, 64);
+      if (den <= 1e-12f) dot = 0.f;  // clamp branch of F.normalize: out = y/eps, d out/dy = 1/eps
       const float inv = ok ? 1.f / den : 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
