@@ -228,6 +228,44 @@ int rihip_inbatch_softmax_item_sweep(const float* items, int64_t n_items, int64_
                                      const int64_t* item_ids, const int64_t* user_pos_ids, const float* lse,
                                      int64_t n_global, float* d_items, void* stream);
 
+/* In-batch hard-negative BPR: every user trains against the m highest-scoring other items of the batch (online hard-
+ * negative mining; not in the reference).  Indices are global as above: user i has gu = user_goff + i, item j has
+ * gi = item_goff + j, user i's positive partner is the item with gi == gu.  Every user's partner must lie inside the
+ * given items (item_goff <= user_goff and user_goff + n_users <= item_goff + n_items), else RIHIP_ERR_ARG.
+ *   score     s_ij = <u_i, y_j>, exact-f32 MFMA; s_ii is the partner's score from the same sweep
+ *   eligible  item j for user i iff j is not i's partner and, when the id arrays are given, item_ids[j] !=
+ *             user_pos_ids[i] (the softmax mask; both int64, NULL together)
+ *   order     eligible items by (score descending, global item index ascending): a total order, so the result does not
+ *             depend on the order in which tiles or lanes deliver candidates; -0 and +0 are one score
+ *   N_i       the items at ranks skip .. skip+m-1 of that order (fewer may exist); c_i = |N_i|, 0 <= c_i <= m
+ *   loss      (1/n_global) sum_i [c_i > 0] (1/c_i) sum_{j in N_i} softplus(s_ij - s_ii)
+ *   w_ij      sigma(s_ij - s_ii) / (n_global c_i) for j in N_i;  W_i = sum_j w_ij
+ *   d_users[i] = sum_{j in N_i} w_ij y_j - W_i y_partner
+ *   d_items[j] = sum_{i : j in N_i} w_ij u_i - [j is the partner of a given user i] W_i u_i
+ *   softplus(z) = fmaxf(z,0) + log1pf(__expf(-|z|)), sigma(z) = 1/(1 + __expf(-z)), as in the in-batch BPR sweeps.
+ * d_items covers all given items, exact zeros where nothing lands, and is additive over slices of the users.
+ * Limits: 1 <= m <= 32, skip >= 0, skip + m <= 64, n_items < 2^31, n_users (m + 1) < 2^31, d any multiple of 16 up to
+ * 256.  Inputs must be finite: non-finite scores give an unspecified selection, but never an index outside
+ * [0, n_items) or -1 and never a fault.  A row with c_i = 0 has zero loss and zero gradient (no 0/0).  Two rows that
+ * carry the same item id count as two negatives, as in in-batch BPR.
+ * rihip_inbatch_hard_select: neg_idx int32[n_users, m] = LOCAL item indices in rank order, -1 in empty slots (empties
+ *   come last); neg_score f32[n_users, m], 0 in empty slots; pos_score f32[n_users] = s_ii.  One launch.
+ * rihip_inbatch_hard_grads: reads what select wrote (a slot whose index is outside [0, n_items) counts as empty);
+ *   writes d_users, d_items and rihip_inbatch_hard_loss_parts(n_users) doubles to loss_part (one per 128 users; loss =
+ *   rihip_sum_partials with scale 1/n_global).  workspace: rihip_inbatch_hard_workspace_bytes(n_users, n_items, m)
+ *   bytes (-1 for sizes outside the limits), 256-byte aligned.  d_items is built by a stable sort of the n_users (m + 1)
+ *   (item, pair) entries and one walk per item in ascending pair order.
+ * No float atomics, no allocation, no host synchronisation: bitwise reproducible and capturable in a graph. */
+int rihip_inbatch_hard_select(const float* users, int64_t n_users, int64_t user_goff, const float* items,
+                              int64_t n_items, int64_t item_goff, int d, int m, int skip, const int64_t* user_pos_ids,
+                              const int64_t* item_ids, int* neg_idx, float* neg_score, float* pos_score, void* stream);
+int64_t rihip_inbatch_hard_loss_parts(int64_t n_users);
+int64_t rihip_inbatch_hard_workspace_bytes(int64_t n_users, int64_t n_items, int m);
+int rihip_inbatch_hard_grads(const float* users, int64_t n_users, int64_t user_goff, const float* items, int64_t n_items,
+                             int64_t item_goff, int d, int m, const int* neg_idx, const float* neg_score,
+                             const float* pos_score, int64_t n_global, float* d_users, float* d_items, double* loss_part,
+                             void* workspace, void* stream);
+
 /* Stored-G form of the same loss (two_tower.py:132-160), the default when memory allows: the user pass is the
  * mode_user=1 sweep that ALSO writes the weights sigma(s_ij - s_ii) (0 on the diagonal; G = weight/(B(B-1))) to `gmat`
  * (rihip_inbatch_gmat_floats(n_users, n_items) floats, 32x32-blocked G^T); the item pass is then a plain exact-f32

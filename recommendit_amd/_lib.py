@@ -53,6 +53,12 @@ SIGNATURES = {
                                                    c_i64, vp, vp, vp, vp]),
     "rihip_inbatch_softmax_item_sweep": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, C.c_float, vp, vp, vp,
                                                    vp, c_i64, vp, vp]),
+    "rihip_inbatch_hard_select": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                            vp, vp]),
+    "rihip_inbatch_hard_loss_parts": (c_i64, [c_i64]),
+    "rihip_inbatch_hard_workspace_bytes": (c_i64, [c_i64, c_i64, C.c_int]),
+    "rihip_inbatch_hard_grads": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, C.c_int, vp, vp, vp, c_i64, vp, vp,
+                                           vp, vp, vp]),
     "rihip_inbatch_gmat_floats": (c_i64, [c_i64, c_i64]),
     "rihip_inbatch_user_pass": (C.c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, vp, c_i64, vp, vp, vp, vp, vp,
                                           C.c_int, vp]),

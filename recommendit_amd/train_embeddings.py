@@ -24,7 +24,7 @@ import torch
 from . import _lib as L
 from .synthetic import GENRES, N_GENRES
 from .trainer import HipBPRTrainer, cosine_lr
-from .two_tower import TwoTowerModel
+from .two_tower import TwoTowerModel, _check_hard_args
 
 logger = logging.getLogger(__name__)
 GENRE_TO_IDX = {g: i for i, g in enumerate(GENRES)}
@@ -185,12 +185,17 @@ class EmbeddingTrainer:
                  embed_dim: int = 64, epochs: int = 10, batch_size: int = 1024, learning_rate: float = 1e-3,
                  device: Optional[str] = None, loss_mode: str = "sampled", table_opt: str = "dense",
                  dropout: float = 0.1, seed: int = 0, temperature: float = 0.05, logq_correction: bool = True,
-                 mask_duplicates: bool = True):
+                 mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0):
         """Defaults = the reference's settings (src/config.py:13,:24-26); `device` is accepted for
         signature compatibility -- training always runs on the HIP device.
         loss_mode="softmax" (not in the reference): in-batch sampled softmax with `temperature` (0.05 is a customary
         starting value, not a measured optimum), the logQ correction from the training pairs' item counts
-        (item_log_q) and masking of duplicate items in a batch."""
+        (item_log_q) and masking of duplicate items in a batch.
+        loss_mode="hard" (not in the reference): in-batch BPR against each row's `n_hard` highest-scoring other items
+        (ranks hard_skip .. hard_skip + n_hard - 1); 8 is a customary starting value, not a measured optimum."""
+        if loss_mode == "hard":
+            _check_hard_args(n_hard, hard_skip)
+        self.n_hard, self.hard_skip = n_hard, hard_skip
         self.data_dir, self.model_output_path = data_dir, model_output_path
         self.embed_dim, self.epochs, self.batch_size, self.learning_rate = embed_dim, epochs, batch_size, learning_rate
         self.loss_mode, self.table_opt, self.dropout, self.seed = loss_mode, table_opt, dropout, seed
@@ -216,6 +221,8 @@ class EmbeddingTrainer:
         if self.loss_mode == "softmax":
             logq = torch.from_numpy(item_log_q(dataset.item_ids, n_items + 1)) if self.logq_correction else None
             extra = dict(temperature=self.temperature, item_logq=logq, mask_duplicates=self.mask_duplicates)
+        if self.loss_mode == "hard":
+            extra = dict(n_hard=self.n_hard, hard_skip=self.hard_skip, mask_duplicates=self.mask_duplicates)
         trainer = HipBPRTrainer(model, self.batch_size, lr=self.learning_rate, weight_decay=1e-5, max_norm=1.0,
                                 loss_mode=self.loss_mode, table_opt=self.table_opt, seed=self.seed, **extra)
         gen = torch.Generator(device=self.device)

@@ -12,7 +12,8 @@ MLP parameters are always dense (one flat buffer: one grad-norm pass + one Adam 
 
 Two loss modes: ``sampled`` (one explicit negative per positive -- what the reference trains
 with) and ``inbatch`` (TwoTowerModel.in_batch_bpr_loss, never called by the reference trainer).  ``softmax`` (not in the
-reference): the in-batch sampled softmax with temperature, logQ correction and duplicate masking.
+reference): the in-batch sampled softmax with temperature, logQ correction and duplicate masking.  ``hard`` (not in the
+reference): in-batch BPR against every row's n_hard highest-scoring other items (online hard-negative mining).
 
 Multi-GPU (one process per GPU, torch.distributed/RCCL; opt-in with ``distributed=True``): user rows are sharded
 (each rank trains pairs whose user row it owns: zero communication for user rows).  The item table is either
@@ -37,7 +38,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from .dist_utils import all_gather_into, all_reduce_sum_, all_to_all_rows, reduce_scatter_sum
-from .two_tower import TwoTowerModel
+from .two_tower import TwoTowerModel, _check_hard_args
 
 _MLP_KEYS = ["user_tower.mlp.0.weight", "user_tower.mlp.0.bias", "user_tower.mlp.3.weight", "user_tower.mlp.3.bias",
              "item_tower.mlp.0.weight", "item_tower.mlp.0.bias", "item_tower.mlp.3.weight", "item_tower.mlp.3.bias"]
@@ -116,7 +117,8 @@ class HipBPRTrainer:
                  inbatch_precision: int = 0, use_graph: bool = False, inbatch_store_g=None,
                  distributed: bool = False, item_shard: str = "replicate", exchange_cap: Optional[int] = None,
                  persistent: Optional[bool] = None, temperature: float = 0.05,
-                 item_logq: Optional[torch.Tensor] = None, mask_duplicates: bool = True):
+                 item_logq: Optional[torch.Tensor] = None, mask_duplicates: bool = True, n_hard: int = 8,
+                 hard_skip: int = 0):
         """distributed=True (or a process_group): this trainer is one rank of a collective job -- EVERY rank of the
         group must construct it and call step() in lock-step.  Default False even when torch.distributed is
         initialised, so that a single-rank trainer inside a distributed program never issues collectives.
@@ -135,8 +137,21 @@ class HipBPRTrainer:
         value, not a measured optimum); item_logq: f32 tensor over the item table's rows, log of each item's sampling
         probability, gathered by the step's item ids on the device (the logQ correction; None = none);
         mask_duplicates: rows whose item equals another row's positive are dropped from that row's softmax.  Single GPU
-        for now."""
-        assert loss_mode in ("sampled", "inbatch", "softmax") and table_opt in ("dense", "sparse")
+        for now.
+        loss_mode="hard": in-batch hard-negative BPR (rihip_inbatch_hard_*): every row trains against its n_hard
+        highest-scoring other rows' items (ranks hard_skip .. hard_skip + n_hard - 1); step() takes the same [B] ids as
+        "inbatch".  n_hard = 8 is a customary starting value, not a measured optimum, and the mode trains on the hard
+        negatives ALONE, which collapsed to loss ln 2 in the short run of DESIGN.md §5b.  mask_duplicates: a row whose item
+        equals another row's positive is never that row's negative.  Single GPU for now."""
+        assert loss_mode in ("sampled", "inbatch", "softmax", "hard") and table_opt in ("dense", "sparse")
+        if loss_mode == "hard":
+            _check_hard_args(n_hard, hard_skip)
+            if distributed or process_group is not None:
+                raise ValueError("HipBPRTrainer: loss_mode='hard' is single-GPU for now (the rectangular "
+                                 "rihip_inbatch_hard_* entries are ready; the multi-GPU trainer wiring is not)")
+            if model.embed_dim % 16 != 0 or not (16 <= model.embed_dim <= 256):
+                raise ValueError(f"HipBPRTrainer: loss_mode='hard' needs an embedding width that is a multiple of 16 up "
+                                 f"to 256, got {model.embed_dim}")
         if loss_mode == "softmax":
             if not (temperature > 0):
                 raise ValueError(f"HipBPRTrainer: temperature must be > 0, got {temperature}")
@@ -269,6 +284,15 @@ class HipBPRTrainer:
                 self.logq_b = torch.empty((B,), **f32)
             self.lse = torch.empty((B,), **f32)
             self.n_lparts = self.lib.rihip_inbatch_softmax_loss_parts(B)
+        if loss_mode == "hard":
+            self.n_hard, self.hard_skip = int(n_hard), int(hard_skip)
+            self.mask_duplicates = bool(mask_duplicates)
+            self.neg_idx = torch.empty((B, self.n_hard), dtype=torch.int32, device=self.dev)
+            self.neg_score = torch.empty((B, self.n_hard), **f32)
+            self.pos_score = torch.empty((B,), **f32)
+            self.hard_ws = torch.empty((self.lib.rihip_inbatch_hard_workspace_bytes(B, B, self.n_hard),),
+                                       dtype=torch.uint8, device=self.dev)
+            self.n_lparts = self.lib.rihip_inbatch_hard_loss_parts(B)
         if loss_mode == "inbatch":
             self.pos = torch.empty((B,), **f32); self.r = torch.empty((B,), **f32)
             # stored-G form (exact f32 only): G^T of the local users x all items stays in HBM between the two passes
@@ -515,6 +539,8 @@ class HipBPRTrainer:
                 self.loss.div_(self.world)   # (summed over the ranks together with the squared norms below)
         elif self.loss_mode == "softmax":
             self._softmax(item_ids, st)
+        elif self.loss_mode == "hard":
+            self._hard(item_ids, st)
         else:
             self._inbatch(st)
 
@@ -751,6 +777,19 @@ class HipBPRTrainer:
                     self.lpart.data_ptr(), st)
         self._timed(lib.rihip_inbatch_softmax_item_sweep, "inbatch_softmax_item_sweep", self.I.data_ptr(), B, 0,
                     self.U.data_ptr(), B, 0, d, self.inv_temp, lq, ids, ids, self.lse.data_ptr(), B, self.dI.data_ptr(), st)
+        self._loss_fold = (self.lpart.data_ptr(), self.n_lparts, 1.0 / B)
+
+    def _hard(self, item_ids: torch.Tensor, st: int) -> None:
+        """in-batch hard-negative BPR: the select sweep, then the sparse gradient passes fill dU, dI and the loss partials
+        that the clip-coefficient launch sums"""
+        lib, B, d, m = self.lib, self.B, self.d, self.n_hard
+        ids = item_ids.data_ptr() if self.mask_duplicates else None
+        self._timed(lib.rihip_inbatch_hard_select, "inbatch_hard_select", self.U.data_ptr(), B, 0, self.I.data_ptr(), B, 0,
+                    d, m, self.hard_skip, ids, ids, self.neg_idx.data_ptr(), self.neg_score.data_ptr(),
+                    self.pos_score.data_ptr(), st)
+        self._timed(lib.rihip_inbatch_hard_grads, "inbatch_hard_grads", self.U.data_ptr(), B, 0, self.I.data_ptr(), B, 0,
+                    d, m, self.neg_idx.data_ptr(), self.neg_score.data_ptr(), self.pos_score.data_ptr(), B,
+                    self.dU.data_ptr(), self.dI.data_ptr(), self.lpart.data_ptr(), self.hard_ws.data_ptr(), st)
         self._loss_fold = (self.lpart.data_ptr(), self.n_lparts, 1.0 / B)
 
 

@@ -290,6 +290,84 @@ class _InBatchSoftmaxFn(torch.autograd.Function):
         return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None, None, None
 
 
+def _check_hard_args(m: int, skip: int, what: str = "n_hard") -> None:
+    if isinstance(m, bool) or isinstance(skip, bool) or int(m) != m or int(skip) != skip:
+        raise ValueError(f"{what} and skip must be integers, got {m!r} and {skip!r}")
+    if not (1 <= m <= 32) or skip < 0 or skip + m > 64:
+        raise ValueError(f"{what}={m}, skip={skip}: need 1 <= {what} <= 32, skip >= 0 and skip + {what} <= 64")
+
+
+def _hard_inputs(U: torch.Tensor, I: torch.Tensor, m: int, skip: int, item_ids: Optional[torch.Tensor]):
+    _check_hard_args(m, skip, "m")
+    if U.dim() != 2 or U.shape != I.shape or U.shape[0] < 1:
+        raise ValueError("hard negatives need U and I of the same shape [B >= 1, d]")
+    if U.shape[1] % 16 != 0 or not (16 <= U.shape[1] <= 256):
+        raise ValueError(f"hard negatives need an embedding width that is a multiple of 16 up to 256, got {U.shape[1]}")
+    if item_ids is not None and item_ids.numel() != U.shape[0]:
+        raise ValueError(f"item_ids must have one entry per row of the batch ({U.shape[0]})")
+    Uc, Ic = L.f32c(U), L.f32c(I)
+    ids = None if item_ids is None else L.i64c(item_ids).reshape(-1)
+    return Uc, Ic, ids
+
+
+def hard_negatives(U: torch.Tensor, I: torch.Tensor, m: int, skip: int = 0, item_ids: Optional[torch.Tensor] = None):
+    """The m hardest in-batch negatives of every row (include/recommendit_hip.h: rihip_inbatch_hard_select), square
+    form: U, I [B,d], row i of I is user i's positive, user_pos_ids = item_ids.  Returns (neg_idx int32 [B,m] with -1 in
+    empty slots, neg_score [B,m], pos_score [B]) on the device; one launch, no host synchronisation."""
+    Uc, Ic, ids = _hard_inputs(U, I, m, skip, item_ids)
+    lib, dev = L.lib(), L.device()
+    B, d = Uc.shape
+    neg_idx = torch.empty((B, m), dtype=torch.int32, device=dev)
+    neg_score = torch.empty((B, m), dtype=torch.float32, device=dev)
+    pos_score = torch.empty((B,), dtype=torch.float32, device=dev)
+    L.check(lib.rihip_inbatch_hard_select(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, int(m), int(skip), L.ptr(ids),
+                                          L.ptr(ids), neg_idx.data_ptr(), neg_score.data_ptr(), pos_score.data_ptr(),
+                                          L.stream_ptr()), "inbatch_hard_select")
+    return neg_idx, neg_score, pos_score
+
+
+def hard_loss_and_grads(U: torch.Tensor, I: torch.Tensor, m: int, skip: int = 0,
+                        item_ids: Optional[torch.Tensor] = None):
+    """Single-GPU in-batch hard-negative BPR (rihip_inbatch_hard_*), square form as in softmax_loss_and_grads with
+    n_global = B.  Returns (loss, dU, dI, neg_idx) on the device; no host synchronisation."""
+    Uc, Ic, ids = _hard_inputs(U, I, m, skip, item_ids)
+    lib, dev = L.lib(), L.device()
+    B, d = Uc.shape
+    m, skip = int(m), int(skip)
+    st = L.stream_ptr()
+    neg_idx = torch.empty((B, m), dtype=torch.int32, device=dev)
+    neg_score = torch.empty((B, m), dtype=torch.float32, device=dev)
+    pos_score = torch.empty((B,), dtype=torch.float32, device=dev)
+    dU, dI = torch.empty_like(Uc), torch.empty_like(Ic)
+    nparts = lib.rihip_inbatch_hard_loss_parts(B)
+    part = torch.empty((nparts,), dtype=torch.float64, device=dev)
+    ws = torch.empty((lib.rihip_inbatch_hard_workspace_bytes(B, B, m),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    L.check(lib.rihip_inbatch_hard_select(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, m, skip, L.ptr(ids), L.ptr(ids),
+                                          neg_idx.data_ptr(), neg_score.data_ptr(), pos_score.data_ptr(), st),
+            "inbatch_hard_select")
+    L.check(lib.rihip_inbatch_hard_grads(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, m, neg_idx.data_ptr(),
+                                         neg_score.data_ptr(), pos_score.data_ptr(), B, dU.data_ptr(), dI.data_ptr(),
+                                         part.data_ptr(), ws.data_ptr(), st), "inbatch_hard_grads")
+    L.check(lib.rihip_sum_partials(part.data_ptr(), nparts, 1.0 / B, loss.data_ptr(), st), "sum_partials")
+    return loss, dU, dI, neg_idx
+
+
+class _InBatchHardFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, I, m, skip, item_ids):
+        loss, dU, dI, _ = hard_loss_and_grads(U, I, m, skip, item_ids)
+        ctx.save_for_backward(dU, dI)
+        ctx.in_devs = (U.device, I.device)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dU, dI = ctx.saved_tensors
+        g = g.to(dU.device)
+        return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None, None, None
+
+
 class TwoTowerModel(nn.Module):
     """two_tower.py:75-251 with HIP towers / losses."""
 
@@ -337,6 +415,23 @@ class TwoTowerModel(nn.Module):
             raise ValueError("in_batch_softmax_loss needs user_emb and item_emb of the same shape [B >= 1, d]")
         in_dev = user_emb.device
         loss = _InBatchSoftmaxFn.apply(user_emb, item_emb, 1.0 / float(temperature), logq, item_ids)
+        return loss if in_dev.type == "cuda" else loss.to(in_dev)
+
+    def in_batch_hard_bpr_loss(self, user_emb, item_emb, n_hard: int = 8, skip: int = 0, item_ids=None) -> torch.Tensor:
+        """In-batch hard-negative BPR (not in the reference): every row's loss is the mean of softplus(s_ij - s_ii) over
+        its ``n_hard`` highest-scoring other rows' items (ranks ``skip`` .. ``skip + n_hard - 1``; ties go to the lower
+        row), averaged over the rows.  ``item_ids`` [B]: another row that carries the same item as row i's positive is
+        never one of row i's negatives (None = no masking); two rows that carry the same item still count as two
+        negatives.  n_hard = 8 is a customary starting value, not a measured optimum.  Trained on this loss ALONE a short
+        run collapsed to loss ln 2, as pure hardest-negative mining is known to: add it to
+        in_batch_bpr_loss with a weight."""
+        _check_hard_args(n_hard, skip)
+        if user_emb.dim() != 2 or user_emb.shape[0] < 1 or user_emb.shape != item_emb.shape:
+            raise ValueError("in_batch_hard_bpr_loss needs user_emb and item_emb of the same shape [B >= 1, d]")
+        if item_ids is not None and item_ids.numel() != user_emb.shape[0]:
+            raise ValueError(f"item_ids must have one entry per row of the batch ({user_emb.shape[0]})")
+        in_dev = user_emb.device
+        loss = _InBatchHardFn.apply(user_emb, item_emb, int(n_hard), int(skip), item_ids)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     # -- inference helpers (two_tower.py:166-210) ---------------------------------------------
