@@ -11,6 +11,9 @@ constexpr int GKC = 32;    // k-panel width
 constexpr int GLDP = GKC + 4;
 constexpr int GNT = 2;     // 32-column output tiles per wave (4 waves x 2 x 32 = 256 columns)
 
+// a dimension the runtime-shape kernels cover: a multiple of 16 up to the 256 columns of one workgroup
+__host__ __device__ inline bool gen_width_ok(int d) { return d >= 16 && d <= 256 && d % 16 == 0; }
+
 __host__ __device__ inline int up8(int x) { return (x + 7) & ~7; }
 __host__ __device__ inline int up32(int x) { return (x + 31) & ~31; }
 

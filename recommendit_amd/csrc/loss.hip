@@ -16,9 +16,6 @@
 
 void rihip_launch_sweep_bf16x3(int d, bool mode_user, const SweepArgs& a, dim3 grid, hipStream_t st);
 void rihip_launch_sweep_x6(int d, bool mode_user, const SweepArgs& a, dim3 grid, int nw, hipStream_t st);
-// loss_generic.hip: runtime-width sweep (any embed_dim multiple of 16 up to 256) behind the tuned instantiations
-bool rihip_inbatch_generic_ok(int d);
-void rihip_launch_sweep_generic(int d, bool mode_user, const SweepArgs& a, int nsplit_slots, hipStream_t st);
 void rihip_launch_gt_x6(int d, const SweepArgs& a, dim3 grid, int nw, hipStream_t st);
 
 namespace {

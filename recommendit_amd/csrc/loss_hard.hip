@@ -12,13 +12,11 @@
 //   w_ij = sigma(s_ij - s_ii) / (n_global c_i),  W_i = sum_j w_ij
 //   dU_i = sum_{j in N_i} w_ij y_j - W_i y_partner      dI_j = sum_{i: j in N_i} w_ij u_i - [j partner of i] W_i u_i
 //
-// Select sweep: the structure of inbatch_softmax_kernel<true> (loss_softmax.hip) with one product instead of two.  One
-// workgroup (4 waves) owns 128 users, 32 at a time in LDS; the items go by in tiles of 128 (one 32x32 score tile per
-// wave, wg_gemm of gen_gemm.h).  Every owner keeps its M = skip + m best candidates so far as a list of 64-bit keys
-// (score order word << 32 | ~row, search_keys.h) in LDS, sorted descending.  A score is first compared with the
-// owner's M-th key; the few that pass are queued per owner with an LDS integer atomic and merged into the list after
-// the tile by rank counting.  Keys are distinct and totally ordered, so the merged list does not depend on the order of
-// arrival: the result is bitwise reproducible.  No float atomics anywhere.
+// Select sweep (skeleton: gen_sweep.h, the score product only).  Every owner keeps its M = skip + m best candidates so
+// far as a list of 64-bit keys (score order word << 32 | ~row, search_keys.h) in LDS, sorted descending.  A score is
+// first compared with the owner's M-th key; the few that pass are queued per owner with an LDS integer atomic and
+// merged into the list after the tile by rank counting.  Keys are distinct and totally ordered, so the merged list does
+// not depend on the order of arrival: the result is bitwise reproducible.  No float atomics anywhere.
 //
 // Gradients: one wave per user gathers its <= m + 1 item rows in slot order (dU, the loss row, the pair weights); the
 // n_users (m + 1) (item, pair) entries are sorted stably by item (rocprim radix sort, the partner term is slot m, empty
@@ -31,7 +29,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
-#include "gen_gemm.h"
+#include "gen_sweep.h"
 #include "search_keys.h"
 
 using namespace rihip_gen;
@@ -40,8 +38,6 @@ using rihip_index::ord2f;
 
 namespace {
 
-constexpr int HOW = 128;    // owners per workgroup = one loss slot
-constexpr int HWT = 128;    // swept rows per tile = queue slots per owner
 constexpr int HMAXM = 64;   // skip + m at most
 constexpr int HMAXN = 32;   // m at most
 
@@ -61,11 +57,11 @@ struct SelectArgs {
 __global__ __launch_bounds__(256) void hard_select_kernel(SelectArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int D = a.D, M = a.skip + a.m;
-  const int ldo = D + 4;
+  const int ldo = gen_ldo(D);
   float* Os = smem;                                                  // [32][ldo] owners
-  float* Wp = Os + 32 * ldo;                                         // [256][GLDP] k-panel of the tile
+  float* Wp = Os + 32 * ldo;                                         // [256][GLDP] k-panel of the tile (no Gs, no red)
   uint64_t* list = reinterpret_cast<uint64_t*>(Wp + 256 * GLDP);     // [32][M] best keys so far, descending
-  uint64_t* queue = list + 32 * M;                                   // [32][HWT] survivors of the current tile
+  uint64_t* queue = list + 32 * M;                                   // [32][GSW] survivors of the current tile
   uint64_t* tmp = reinterpret_cast<uint64_t*>(Wp);                   // [32][HMAXM] merged list (the panel is idle then)
   __shared__ int64_t own_id[32];       // user_pos_ids of the 32 owners
   __shared__ uint64_t thr[32];         // the owner's M-th key, 0 while its list is not full (every key is > 0)
@@ -74,41 +70,33 @@ __global__ __launch_bounds__(256) void hard_select_kernel(SelectArgs a) {
   __shared__ float diag_s[32];         // s_ii, written by the one lane that meets the diagonal
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r31 = lane & 31;
   const bool ids = a.o_ids != nullptr;
-  for (int og = 0; og < 4; ++og) {
-    const int64_t o_base = (int64_t)blockIdx.x * HOW + og * 32;
+  for (int og = 0; og < GOG; ++og) {
+    const int64_t o_base = owner_base(og);
     if (o_base >= a.No) break;
-    __syncthreads();
-    for (int idx = tid; idx < 32 * D; idx += 256) {
-      const int r = idx / D, k = idx % D;
-      Os[r * ldo + k] = (o_base + r < a.No) ? a.Xo[(o_base + r) * D + k] : 0.f;
-    }
+    stage_owners(Os, ldo, a.Xo, o_base, a.No, D, tid);
     if (tid < 32) {
       own_id[tid] = (ids && o_base + tid < a.No) ? a.o_ids[o_base + tid] : 0;
       thr[tid] = 0ull; lcnt[tid] = 0; qcnt[tid] = 0; diag_s[tid] = 0.f;
     }
     const int64_t og0 = a.o_goff + o_base;
-    for (int64_t sb = 0; sb < a.Ns; sb += HWT) {
-      const int nsw = (a.Ns - sb < HWT) ? (int)(a.Ns - sb) : HWT;
+    for (int64_t sb = 0; sb < a.Ns; sb += GSW) {
+      const int nsw = (a.Ns - sb < GSW) ? (int)(a.Ns - sb) : GSW;
       f32x16 sacc[GNT];
-      // S[owner][swept] = O . Y^T : wave w holds the 32 swept rows sb + 32w .. (tile nt = w)
-      wg_gemm<false>(Os, ldo, D, a.Ys + sb * D, D, nsw, Wp, sacc, tid);
-      const int64_t srow = sb + w * 32 + r31;
-      const bool s_ok = srow < a.Ns;
-      const int64_t s_g = a.s_goff + srow;
-      const int64_t id_s = (ids && s_ok) ? a.s_ids[srow] : 0;
-      const uint32_t low = 0xFFFFFFFFu - (uint32_t)srow;   // local row: the same order as the global index
+      wg_gemm<false>(Os, ldo, D, a.Ys + sb * D, D, nsw, Wp, sacc, tid);                // S = O.Y^T
+      const TileLane tl = tile_lane(sb, w, r31, a.Ns, a.s_goff);
+      const int64_t id_s = swept_id(ids, a.s_ids, tl);
+      const uint32_t low = 0xFFFFFFFFu - (uint32_t)tl.srow;   // local row: the same order as the global index
       int pushed = 0;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ol = acc_row(r, lane);
-        const int64_t orow = o_base + ol;
+        const TileElem e = tile_elem(r, lane, o_base, a.No, a.o_goff, tl);
+        const int ol = e.ol;
         const float s = sacc[0][r] + 0.f;                  // -0 -> +0: one score, one order word
-        const bool diag = (a.o_goff + orow) == s_g;
-        const bool elig = s_ok && orow < a.No && !diag && !(ids && id_s == own_id[ol]);
+        const bool elig = e.valid && !e.diag && !masked(ids, e.diag, id_s, own_id[ol]);
         const uint64_t key = elig ? (((uint64_t)f2ord(s) << 32) | (uint64_t)low) : 0ull;
         if (key > thr[ol]) {                               // the only per-score branch: rare after the first tiles
-          const int slot = atomicAdd(&qcnt[ol], 1);        // < HWT: one candidate per swept row of the tile
-          queue[ol * HWT + slot] = key;
+          const int slot = atomicAdd(&qcnt[ol], 1);        // < GSW: one candidate per swept row of the tile
+          queue[ol * GSW + slot] = key;
           pushed = 1;
         }
       }
@@ -117,9 +105,8 @@ __global__ __launch_bounds__(256) void hard_select_kernel(SelectArgs a) {
       if (wg0 < og0 + 32 && og0 < wg0 + 32) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ol = acc_row(r, lane);
-          const int64_t orow = o_base + ol;
-          if (s_ok && orow < a.No && (a.o_goff + orow) == s_g) diag_s[ol] = sacc[0][r] + 0.f;
+          const TileElem e = tile_elem(r, lane, o_base, a.No, a.o_goff, tl);
+          if (e.valid && e.diag) diag_s[e.ol] = sacc[0][r] + 0.f;
         }
       }
       // ---- merge the survivors: 8 threads per owner, rank = number of greater keys (keys are distinct)
@@ -129,11 +116,11 @@ __global__ __launch_bounds__(256) void hard_select_kernel(SelectArgs a) {
         if (q > 0) {
           for (int e = sub; e < lc + q; e += 8) {
             const bool old = e < lc;
-            const uint64_t k = old ? list[mo * M + e] : queue[mo * HWT + e - lc];
+            const uint64_t k = old ? list[mo * M + e] : queue[mo * GSW + e - lc];
             int rank = old ? e : 0;                        // the list is sorted: e greater keys inside it
             if (!old)
               for (int f = 0; f < lc; ++f) rank += list[mo * M + f] > k ? 1 : 0;
-            for (int f = 0; f < q; ++f) rank += queue[mo * HWT + f] > k ? 1 : 0;
+            for (int f = 0; f < q; ++f) rank += queue[mo * GSW + f] > k ? 1 : 0;
             if (rank < M) tmp[mo * HMAXM + rank] = k;
           }
         }
@@ -171,10 +158,8 @@ __global__ __launch_bounds__(256) void hard_select_kernel(SelectArgs a) {
 }
 
 size_t select_lds(int D, int M) {
-  return sizeof(float) * ((size_t)32 * (D + 4) + 256 * GLDP) + sizeof(uint64_t) * ((size_t)32 * M + 32 * HWT);
+  return sizeof(float) * ((size_t)32 * gen_ldo(D) + 256 * GLDP) + sizeof(uint64_t) * ((size_t)32 * M + 32 * GSW);
 }
-
-bool width_ok(int d) { return d >= 16 && d <= 256 && d % 16 == 0; }
 
 // ---- gradients ---------------------------------------------------------------------------------------------------
 struct GradArgs {
@@ -189,12 +174,12 @@ struct GradArgs {
 
 // One wave per user, 128 users (one loss part) per workgroup.  Lane s < m holds slot s.
 __global__ __launch_bounds__(256) void hard_user_kernel(GradArgs a) {
-  __shared__ double row_loss[HOW];
+  __shared__ double row_loss[GOW];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int m = a.m, m1 = a.m + 1, d = a.d;
   for (int u = 0; u < 32; ++u) {
     const int li = w * 32 + u;
-    const int64_t i = (int64_t)blockIdx.x * HOW + li;
+    const int64_t i = (int64_t)blockIdx.x * GOW + li;
     if (i >= a.nu) {                                       // wave-uniform
       if (lane == 0) row_loss[li] = 0.0;
       continue;
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(256) void hard_user_kernel(GradArgs a) {
   __syncthreads();
   if (tid == 0) {
     double s = 0.0;
-    for (int r = 0; r < HOW; ++r) s += row_loss[r];
+    for (int r = 0; r < GOW; ++r) s += row_loss[r];
     a.loss_part[blockIdx.x] = s;
   }
 }
@@ -315,7 +300,7 @@ int hard_ws_layout(int64_t n_users, int64_t n_items, int m, void* base, HardWs* 
 
 int check_shape(const char* who, int d, int m, int skip, int64_t n_users, int64_t user_goff, int64_t n_items,
                 int64_t item_goff) {
-  RIHIP_REQUIRE(width_ok(d), RIHIP_ERR_SHAPE, "%s: unsupported embed_dim=%d (multiples of 16 up to 256)", who, d);
+  RIHIP_REQUIRE(gen_width_ok(d), RIHIP_ERR_SHAPE, "%s: unsupported embed_dim=%d (multiples of 16 up to 256)", who, d);
   RIHIP_REQUIRE(m >= 1 && m <= HMAXN && skip >= 0 && skip + m <= HMAXM, RIHIP_ERR_ARG,
                 "%s: m=%d skip=%d need 1 <= m <= %d, skip >= 0 and skip + m <= %d", who, m, skip, HMAXN, HMAXM);
   RIHIP_REQUIRE(n_users > 0 && n_items > 0 && n_items < (1ll << 31), RIHIP_ERR_ARG,
@@ -339,21 +324,20 @@ extern "C" int rihip_inbatch_hard_select(const float* users, int64_t n_users, in
   RIHIP_REQUIRE(users && items && neg_idx && neg_score && pos_score, RIHIP_ERR_ARG, "inbatch_hard_select: null pointer");
   static bool granted = false;
   if (!granted) {
-    RIHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hard_select_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds(256, HMAXM)));
+    RIHIP_CHECK_HIP(grant_dynamic_lds(reinterpret_cast<const void*>(hard_select_kernel), select_lds(256, HMAXM)));
     granted = true;
   }
   SelectArgs a;
   a.Xo = users; a.No = n_users; a.o_goff = user_goff; a.Ys = items; a.Ns = n_items; a.s_goff = item_goff;
   a.D = d; a.m = m; a.skip = skip; a.o_ids = user_pos_ids; a.s_ids = item_ids;
   a.neg_idx = neg_idx; a.neg_score = neg_score; a.pos_score = pos_score;
-  const dim3 grid((unsigned)((n_users + HOW - 1) / HOW));
+  const dim3 grid((unsigned)((n_users + GOW - 1) / GOW));
   hipLaunchKernelGGL(hard_select_kernel, grid, dim3(256), select_lds(d, skip + m), (hipStream_t)stream, a);
   RIHIP_CHECK_LAUNCH();
   return RIHIP_OK;
 }
 
-extern "C" int64_t rihip_inbatch_hard_loss_parts(int64_t n_users) { return (n_users + HOW - 1) / HOW; }
+extern "C" int64_t rihip_inbatch_hard_loss_parts(int64_t n_users) { return (n_users + GOW - 1) / GOW; }
 
 extern "C" int64_t rihip_inbatch_hard_workspace_bytes(int64_t n_users, int64_t n_items, int m) {
   HardWs ws;
@@ -383,7 +367,7 @@ extern "C" int rihip_inbatch_hard_grads(const float* users, int64_t n_users, int
   a.dU = d_users; a.dI = d_items; a.loss_part = loss_part;
   a.keys_in = ws.keys_in; a.keys_out = ws.keys_out; a.vals_in = ws.vals_in; a.vals_out = ws.vals_out; a.wbuf = ws.w;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(hard_user_kernel, dim3((unsigned)((n_users + HOW - 1) / HOW)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(hard_user_kernel, dim3((unsigned)((n_users + GOW - 1) / GOW)), dim3(256), 0, st, a);
   RIHIP_CHECK_LAUNCH();
   const size_t n_ent = (size_t)n_users * (m + 1);
   size_t tb = ws.temp_bytes;

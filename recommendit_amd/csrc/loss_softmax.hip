@@ -20,20 +20,15 @@
 // decision is taken before the tile's weights are exponentiated, so nothing is ever at a mixed scale), and finishes
 // dU, lse and the loss in the same launch.  The item sweep recomputes the scores and exponentiates against the stored
 // lse.  Every exponent is <= 0 in user mode whatever the logits are: no fixed shift, no assumption of unit rows.
-// Structure of loss_generic.hip: one workgroup (4 waves) owns 128 owners = one loss slot, 32 at a time in LDS; swept
-// rows go by in tiles of 128 (one 32x32 score tile per wave); the tile's weights go to LDS and are multiplied back
-// against the same swept rows; both products run through wg_gemm of gen_gemm.h.  No atomics, fixed summation order.
+// Skeleton: gen_sweep.h.
 #include <cmath>
 
 #include "common.h"
-#include "gen_gemm.h"
+#include "gen_sweep.h"
 
 using namespace rihip_gen;
 
 namespace {
-
-constexpr int SOW = 128;   // owners per workgroup = one loss slot
-constexpr int SWT = 128;   // swept rows per tile
 
 struct SoftmaxArgs {
   const float* Xo;           // owners [No,d]
@@ -55,10 +50,10 @@ template <bool MODE_USER>
 __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int D = a.D;
-  const int ldo = D + 4, ldg = SWT + 4;
+  const int ldo = gen_ldo(D);
   float* Os = smem;                    // [32][ldo] owners
-  float* Gs = Os + 32 * ldo;           // [32][ldg] weights of the current swept tile
-  float* Wp = Gs + 32 * ldg;           // [256][GLDP]
+  float* Gs = Os + 32 * ldo;           // [32][GLDG] weights of the current swept tile
+  float* Wp = Gs + 32 * GLDG;          // [256][GLDP]
   float* red = Wp + 256 * GLDP;        // [4][32] per-wave row maxima of a tile, then the per-wave row sums
   __shared__ float own_lq[32];         // item mode: logq of the 32 owners
   __shared__ int64_t own_id[32];       // ids of the 32 owners
@@ -68,14 +63,10 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
   const bool ids = a.o_ids != nullptr;
   const float NEG_INF = -INFINITY;
   double loss_wg = 0.0;
-  for (int og = 0; og < 4; ++og) {
-    const int64_t o_base = (int64_t)blockIdx.x * SOW + og * 32;
+  for (int og = 0; og < GOG; ++og) {
+    const int64_t o_base = owner_base(og);
     if (o_base >= a.No) break;
-    __syncthreads();
-    for (int idx = tid; idx < 32 * D; idx += 256) {
-      const int r = idx / D, k = idx % D;
-      Os[r * ldo + k] = (o_base + r < a.No) ? a.Xo[(o_base + r) * D + k] : 0.f;
-    }
+    stage_owners(Os, ldo, a.Xo, o_base, a.No, D, tid);
     if (tid < 32) {
       const bool ok = o_base + tid < a.No;
       own_id[tid] = (ids && ok) ? a.o_ids[o_base + tid] : 0;
@@ -87,32 +78,23 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
     float m_run[16], l_run[16];        // user mode: running maximum and this lane's share of the running row sum
 #pragma unroll
     for (int r = 0; r < 16; ++r) { m_run[r] = NEG_INF; l_run[r] = 0.f; }
-    for (int64_t sb = 0; sb < a.Ns; sb += SWT) {
-      const int nsw = (a.Ns - sb < SWT) ? (int)(a.Ns - sb) : SWT;
+    for (int64_t sb = 0; sb < a.Ns; sb += GSW) {
+      const int nsw = (a.Ns - sb < GSW) ? (int)(a.Ns - sb) : GSW;
       f32x16 sacc[GNT];
-      // S[owner][swept] = O . Y^T : wave w holds the 32 swept rows sb + 32w .. (tile nt = w)
-      wg_gemm<false>(Os, ldo, D, a.Ys + sb * D, D, nsw, Wp, sacc, tid);
-      const int64_t srow = sb + w * 32 + r31;
-      const bool s_ok = srow < a.Ns;
-      const int64_t s_g = a.s_goff + srow;
-      const int64_t id_s = (ids && s_ok) ? a.s_ids[srow] : 0;
+      wg_gemm<false>(Os, ldo, D, a.Ys + sb * D, D, nsw, Wp, sacc, tid);                // S = O.Y^T
+      const TileLane tl = tile_lane(sb, w, r31, a.Ns, a.s_goff);
+      const int64_t id_s = swept_id(ids, a.s_ids, tl);
       if (MODE_USER) {
-        const float lq_s = (a.logq && s_ok) ? a.logq[srow] : 0.f;
+        const float lq_s = (a.logq && tl.s_ok) ? a.logq[tl.srow] : 0.f;
         float lg[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ol = acc_row(r, lane);
-          const int64_t orow = o_base + ol;
-          const bool valid = s_ok && orow < a.No;
-          const bool diag = (a.o_goff + orow) == s_g;
-          const bool masked = ids && !diag && id_s == own_id[ol];
+          const TileElem e = tile_elem(r, lane, o_base, a.No, a.o_goff, tl);
           const float l = a.inv_temp * sacc[0][r] - lq_s;
-          lg[r] = (valid && !masked) ? l : NEG_INF;
-          if (valid && diag) diag_l[ol] = l;
-          float v = lg[r];
-          v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-          v = fmaxf(v, __shfl_xor(v, 8, 64)); v = fmaxf(v, __shfl_xor(v, 16, 64));
-          if (r31 == 0) red[w * 32 + ol] = v;
+          lg[r] = (e.valid && !masked(ids, e.diag, id_s, own_id[e.ol])) ? l : NEG_INF;
+          if (e.valid && e.diag) diag_l[e.ol] = l;
+          const float v = row32_max(lg[r]);
+          if (r31 == 0) red[w * 32 + e.ol] = v;
         }
         __syncthreads();
         // the new maximum is settled BEFORE anything of this tile is exponentiated: accumulators and row sums move to
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ol = acc_row(r, lane);
-          const float mt = fmaxf(fmaxf(red[ol], red[32 + ol]), fmaxf(red[64 + ol], red[96 + ol]));
+          const float mt = red4_max(red, ol);
           const float mn = fmaxf(m_run[r], mt);
           const float alpha = (m_run[r] == NEG_INF) ? 0.f : __expf(m_run[r] - mn);   // nothing accumulated yet: any factor
           const float p = (lg[r] == NEG_INF) ? 0.f : __expf(lg[r] - mn);            // masked / out of range: exactly 0
@@ -128,34 +110,27 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
           m_run[r] = mn;
 #pragma unroll
           for (int t = 0; t < GNT; ++t) out[t][r] *= alpha;
-          Gs[ol * ldg + w * 32 + r31] = p;
+          Gs[ol * GLDG + w * 32 + r31] = p;
         }
       } else {
-        const float lse_s = s_ok ? a.lse[srow] : 0.f;
+        const float lse_s = tl.s_ok ? a.lse[tl.srow] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ol = acc_row(r, lane);
-          const int64_t orow = o_base + ol;
-          const bool valid = s_ok && orow < a.No;
-          const bool diag = (a.o_goff + orow) == s_g;
-          const bool masked = ids && !diag && id_s == own_id[ol];
-          const float l = a.inv_temp * sacc[0][r] - own_lq[ol];
-          float p = (valid && !masked) ? __expf(l - lse_s) : 0.f;
-          if (valid && diag) p -= 1.f;           // the partner user is in this tile: its -u term rides in the product
-          Gs[ol * ldg + w * 32 + r31] = p;
+          const TileElem e = tile_elem(r, lane, o_base, a.No, a.o_goff, tl);
+          const float l = a.inv_temp * sacc[0][r] - own_lq[e.ol];
+          float p = (e.valid && !masked(ids, e.diag, id_s, own_id[e.ol])) ? __expf(l - lse_s) : 0.f;
+          if (e.valid && e.diag) p -= 1.f;       // the partner user is in this tile: its -u term rides in the product
+          Gs[e.ol * GLDG + w * 32 + r31] = p;
         }
       }
-      // dOwner[owner][c] += sum_s P[owner][s] Y[s][c]   (B[n = c][k = s] = Y[(sb + s)*D + c]: transposed panel)
-      wg_gemm<true, true>(Gs, ldg, SWT, a.Ys + sb * D, D, D, Wp, out, tid, nsw);
+      wg_gemm<true, true>(Gs, GLDG, GSW, a.Ys + sb * D, D, D, Wp, out, tid, nsw);     // dOwner += G.Y
     }
     // ---- epilogue of the owner group
     __syncthreads();
     if (MODE_USER) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float v = l_run[r];
-        v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-        v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64);
+        const float v = row32_sum(l_run[r]);
         if (r31 == 0) red[w * 32 + acc_row(r, lane)] = v;
       }
       __syncthreads();
@@ -166,7 +141,7 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
       const int64_t orow = o_base + ol;
       float inv_sum = 1.f;
       if (MODE_USER) {
-        const float sum = ((red[ol] + red[32 + ol]) + red[64 + ol]) + red[96 + ol];   // >= 1: the maximum's own term
+        const float sum = red4_sum(red, ol);   // >= 1: the maximum's own term
         inv_sum = 1.f / sum;
         if (w == 0 && r31 == 0) {
           float rl = 0.f;
@@ -180,7 +155,7 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
       }
 #pragma unroll
       for (int t = 0; t < GNT; ++t) {
-        const int col = (w + 4 * t) * 32 + r31;
+        const int col = out_col(t, w, r31);
         if (col < D && orow < a.No) {
           float v = out[t][r];
           if (MODE_USER) {
@@ -203,29 +178,23 @@ __global__ __launch_bounds__(256) void inbatch_softmax_kernel(SoftmaxArgs a) {
   if (MODE_USER && tid == 0) a.loss_part[blockIdx.x] = loss_wg;
 }
 
-size_t softmax_lds(int D) { return sizeof(float) * ((size_t)32 * (D + 4) + 32 * (SWT + 4) + 256 * GLDP + 128); }
-
-bool width_ok(int d) { return d >= 16 && d <= 256 && d % 16 == 0; }
-
 int launch(bool mode_user, const SoftmaxArgs& a, hipStream_t st) {
   static bool granted = false;
   if (!granted) {
-    RIHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(inbatch_softmax_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)softmax_lds(256)));
-    RIHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(inbatch_softmax_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)softmax_lds(256)));
+    RIHIP_CHECK_HIP(grant_dynamic_lds(reinterpret_cast<const void*>(inbatch_softmax_kernel<true>), gen_sweep_lds(256)));
+    RIHIP_CHECK_HIP(grant_dynamic_lds(reinterpret_cast<const void*>(inbatch_softmax_kernel<false>), gen_sweep_lds(256)));
     granted = true;
   }
-  const dim3 grid((unsigned)((a.No + SOW - 1) / SOW));
-  if (mode_user) hipLaunchKernelGGL(inbatch_softmax_kernel<true>, grid, dim3(256), softmax_lds(a.D), st, a);
-  else hipLaunchKernelGGL(inbatch_softmax_kernel<false>, grid, dim3(256), softmax_lds(a.D), st, a);
+  const dim3 grid((unsigned)((a.No + GOW - 1) / GOW));
+  if (mode_user) hipLaunchKernelGGL(inbatch_softmax_kernel<true>, grid, dim3(256), gen_sweep_lds(a.D), st, a);
+  else hipLaunchKernelGGL(inbatch_softmax_kernel<false>, grid, dim3(256), gen_sweep_lds(a.D), st, a);
   RIHIP_CHECK_LAUNCH();
   return RIHIP_OK;
 }
 
 int check_common(const char* who, int d, float inv_temp, const int64_t* user_pos_ids, const int64_t* item_ids,
                  int64_t n_users, int64_t n_items, int64_t n_global) {
-  RIHIP_REQUIRE(width_ok(d), RIHIP_ERR_SHAPE, "%s: unsupported embed_dim=%d (multiples of 16 up to 256)", who, d);
+  RIHIP_REQUIRE(gen_width_ok(d), RIHIP_ERR_SHAPE, "%s: unsupported embed_dim=%d (multiples of 16 up to 256)", who, d);
   RIHIP_REQUIRE(std::isfinite(inv_temp) && inv_temp > 0.f, RIHIP_ERR_ARG, "%s: inv_temp=%g must be finite and > 0", who,
                 (double)inv_temp);
   RIHIP_REQUIRE((user_pos_ids == nullptr) == (item_ids == nullptr), RIHIP_ERR_ARG,
@@ -237,7 +206,7 @@ int check_common(const char* who, int d, float inv_temp, const int64_t* user_pos
 
 }  // namespace
 
-extern "C" int64_t rihip_inbatch_softmax_loss_parts(int64_t n_users) { return (n_users + SOW - 1) / SOW; }
+extern "C" int64_t rihip_inbatch_softmax_loss_parts(int64_t n_users) { return (n_users + GOW - 1) / GOW; }
 
 extern "C" int rihip_inbatch_softmax_user_sweep(const float* users, int64_t n_users, int64_t user_goff,
                                                 const float* items, int64_t n_items, int64_t item_goff, int d,

@@ -22,6 +22,10 @@ struct SweepArgs {
   int64_t g_ub;      //   element (item_local, user_local) at item_local*32 + user_local ; g_ub = user blocks per item block row
 };
 
+// loss_generic.hip: runtime-width sweep (any embed_dim multiple of 16 up to 256) behind the tuned instantiations
+bool rihip_inbatch_generic_ok(int d);
+void rihip_launch_sweep_generic(int d, bool mode_user, const SweepArgs& a, int nsplit_slots, hipStream_t st);
+
 constexpr int OW = 128;  // owners per workgroup (32 per wave)
 constexpr int TSW = 32;  // swept rows per LDS tile (shared by the 4 waves)
 // Instantiations of inbatch_gt_kernel and inbatch_sweep_kernel whose full interior tiles run in the unrolled steady-state loop (loss.hip); the

@@ -358,8 +358,7 @@ __global__ __launch_bounds__(STEP_WG) void bpr_step_persistent_kernel(StepArgs s
 }  // namespace
 
 extern "C" int rihip_bpr_step_persistent_supported(int64_t B, int d, int hidden) {
-  return (B >= 1 && 2 * B <= SCAT_LIST && d >= 16 && d <= 256 && hidden >= 16 && hidden <= 256 && d % 16 == 0 &&
-          hidden % 16 == 0) ? 1 : 0;
+  return (B >= 1 && 2 * B <= SCAT_LIST && gen_width_ok(d) && gen_width_ok(hidden)) ? 1 : 0;
 }
 
 extern "C" int64_t rihip_bpr_step_scratch_doubles(int64_t B) { return (B + 31) / 32 + RIHIP_NCU + 8; }

@@ -58,9 +58,7 @@ size_t bwd_lds(int D, int H) { return sizeof(float) * gen_bwd_lds_floats(D, H); 
 
 }  // namespace
 
-bool rihip_tower_generic_ok(int d, int hidden) {
-  return d >= 16 && d <= 256 && hidden >= 16 && hidden <= 256 && d % 16 == 0 && hidden % 16 == 0;
-}
+bool rihip_tower_generic_ok(int d, int hidden) { return gen_width_ok(d) && gen_width_ok(hidden); }
 
 void rihip_launch_tower_fwd_generic(int d, int hidden, bool item, const TowerFwdArgs& a, hipStream_t st) {
   GenFwd g;

@@ -227,23 +227,29 @@ def inbatch_loss_and_grads(U: torch.Tensor, I: torch.Tensor, precision: int = 0,
     return loss, dU, dI
 
 
-class _InBatchFn(torch.autograd.Function):
+class _ClosedFormLossFn(torch.autograd.Function):
+    """loss = fn(U, I, *args)[0] with the gradients fn returns beside it: fn is one of the *_loss_and_grads below."""
+
     @staticmethod
-    def forward(ctx, U, I):
-        if U.shape[0] < 2:  # reference: mean over an empty negative set -> nan (two_tower.py:156-158)
-            ctx.save_for_backward(torch.zeros_like(U), torch.zeros_like(I))
-            ctx.in_devs = (U.device, I.device)
-            return torch.full((), float("nan"), dtype=torch.float32, device=U.device)
-        loss, dU, dI = inbatch_loss_and_grads(U, I)
+    def forward(ctx, U, I, fn, *args):
+        loss, dU, dI = fn(U, I, *args)[:3]
         ctx.save_for_backward(dU, dI)
         ctx.in_devs = (U.device, I.device)
+        ctx.n_args = len(args)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         dU, dI = ctx.saved_tensors
         g = g.to(dU.device)
-        return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1])
+        return ((dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None) + (None,) * ctx.n_args
+
+
+def _inbatch_or_nan(U: torch.Tensor, I: torch.Tensor):
+    if U.shape[0] < 2:  # reference: mean over an empty negative set -> nan (two_tower.py:156-158)
+        return (torch.full((), float("nan"), dtype=torch.float32, device=U.device), torch.zeros_like(U),
+                torch.zeros_like(I))
+    return inbatch_loss_and_grads(U, I)
 
 
 def softmax_loss_and_grads(U: torch.Tensor, I: torch.Tensor, inv_temp: float, logq: Optional[torch.Tensor] = None,
@@ -275,21 +281,6 @@ def softmax_loss_and_grads(U: torch.Tensor, I: torch.Tensor, inv_temp: float, lo
     return loss, dU, dI, lse
 
 
-class _InBatchSoftmaxFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, U, I, inv_temp, logq, item_ids):
-        loss, dU, dI, _ = softmax_loss_and_grads(U, I, inv_temp, logq, item_ids)
-        ctx.save_for_backward(dU, dI)
-        ctx.in_devs = (U.device, I.device)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        dU, dI = ctx.saved_tensors
-        g = g.to(dU.device)
-        return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None, None, None
-
-
 def _check_hard_args(m: int, skip: int, what: str = "n_hard") -> None:
     if isinstance(m, bool) or isinstance(skip, bool) or int(m) != m or int(skip) != skip:
         raise ValueError(f"{what} and skip must be integers, got {m!r} and {skip!r}")
@@ -317,11 +308,12 @@ def hard_negatives(U: torch.Tensor, I: torch.Tensor, m: int, skip: int = 0, item
     Uc, Ic, ids = _hard_inputs(U, I, m, skip, item_ids)
     lib, dev = L.lib(), L.device()
     B, d = Uc.shape
+    m, skip = int(m), int(skip)
     neg_idx = torch.empty((B, m), dtype=torch.int32, device=dev)
     neg_score = torch.empty((B, m), dtype=torch.float32, device=dev)
     pos_score = torch.empty((B,), dtype=torch.float32, device=dev)
-    L.check(lib.rihip_inbatch_hard_select(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, int(m), int(skip), L.ptr(ids),
-                                          L.ptr(ids), neg_idx.data_ptr(), neg_score.data_ptr(), pos_score.data_ptr(),
+    L.check(lib.rihip_inbatch_hard_select(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, m, skip, L.ptr(ids), L.ptr(ids),
+                                          neg_idx.data_ptr(), neg_score.data_ptr(), pos_score.data_ptr(),
                                           L.stream_ptr()), "inbatch_hard_select")
     return neg_idx, neg_score, pos_score
 
@@ -330,42 +322,22 @@ def hard_loss_and_grads(U: torch.Tensor, I: torch.Tensor, m: int, skip: int = 0,
                         item_ids: Optional[torch.Tensor] = None):
     """Single-GPU in-batch hard-negative BPR (rihip_inbatch_hard_*), square form as in softmax_loss_and_grads with
     n_global = B.  Returns (loss, dU, dI, neg_idx) on the device; no host synchronisation."""
-    Uc, Ic, ids = _hard_inputs(U, I, m, skip, item_ids)
+    neg_idx, neg_score, pos_score = hard_negatives(U, I, m, skip, item_ids)
     lib, dev = L.lib(), L.device()
+    Uc, Ic = L.f32c(U), L.f32c(I)      # as hard_negatives converted them: no copy for f32 rows already on the device
     B, d = Uc.shape
-    m, skip = int(m), int(skip)
+    m = int(m)
     st = L.stream_ptr()
-    neg_idx = torch.empty((B, m), dtype=torch.int32, device=dev)
-    neg_score = torch.empty((B, m), dtype=torch.float32, device=dev)
-    pos_score = torch.empty((B,), dtype=torch.float32, device=dev)
     dU, dI = torch.empty_like(Uc), torch.empty_like(Ic)
     nparts = lib.rihip_inbatch_hard_loss_parts(B)
     part = torch.empty((nparts,), dtype=torch.float64, device=dev)
     ws = torch.empty((lib.rihip_inbatch_hard_workspace_bytes(B, B, m),), dtype=torch.uint8, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    L.check(lib.rihip_inbatch_hard_select(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, m, skip, L.ptr(ids), L.ptr(ids),
-                                          neg_idx.data_ptr(), neg_score.data_ptr(), pos_score.data_ptr(), st),
-            "inbatch_hard_select")
     L.check(lib.rihip_inbatch_hard_grads(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, m, neg_idx.data_ptr(),
                                          neg_score.data_ptr(), pos_score.data_ptr(), B, dU.data_ptr(), dI.data_ptr(),
                                          part.data_ptr(), ws.data_ptr(), st), "inbatch_hard_grads")
     L.check(lib.rihip_sum_partials(part.data_ptr(), nparts, 1.0 / B, loss.data_ptr(), st), "sum_partials")
     return loss, dU, dI, neg_idx
-
-
-class _InBatchHardFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, U, I, m, skip, item_ids):
-        loss, dU, dI, _ = hard_loss_and_grads(U, I, m, skip, item_ids)
-        ctx.save_for_backward(dU, dI)
-        ctx.in_devs = (U.device, I.device)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        dU, dI = ctx.saved_tensors
-        g = g.to(dU.device)
-        return (dU * g).to(ctx.in_devs[0]), (dI * g).to(ctx.in_devs[1]), None, None, None
 
 
 class TwoTowerModel(nn.Module):
@@ -399,7 +371,7 @@ class TwoTowerModel(nn.Module):
     def in_batch_bpr_loss(self, user_emb, item_emb) -> torch.Tensor:
         """two_tower.py:132-160 (closed form of the per-row python loop)."""
         in_dev = user_emb.device
-        loss = _InBatchFn.apply(user_emb, item_emb)
+        loss = _ClosedFormLossFn.apply(user_emb, item_emb, _inbatch_or_nan)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     def in_batch_softmax_loss(self, user_emb, item_emb, temperature: float = 0.05, logq=None, item_ids=None
@@ -414,7 +386,8 @@ class TwoTowerModel(nn.Module):
         if user_emb.shape[0] < 1 or user_emb.shape != item_emb.shape:
             raise ValueError("in_batch_softmax_loss needs user_emb and item_emb of the same shape [B >= 1, d]")
         in_dev = user_emb.device
-        loss = _InBatchSoftmaxFn.apply(user_emb, item_emb, 1.0 / float(temperature), logq, item_ids)
+        loss = _ClosedFormLossFn.apply(user_emb, item_emb, softmax_loss_and_grads, 1.0 / float(temperature), logq,
+                                       item_ids)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     def in_batch_hard_bpr_loss(self, user_emb, item_emb, n_hard: int = 8, skip: int = 0, item_ids=None) -> torch.Tensor:
@@ -431,7 +404,7 @@ class TwoTowerModel(nn.Module):
         if item_ids is not None and item_ids.numel() != user_emb.shape[0]:
             raise ValueError(f"item_ids must have one entry per row of the batch ({user_emb.shape[0]})")
         in_dev = user_emb.device
-        loss = _InBatchHardFn.apply(user_emb, item_emb, int(n_hard), int(skip), item_ids)
+        loss = _ClosedFormLossFn.apply(user_emb, item_emb, hard_loss_and_grads, int(n_hard), int(skip), item_ids)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     # -- inference helpers (two_tower.py:166-210) ---------------------------------------------
