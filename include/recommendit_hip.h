@@ -282,6 +282,60 @@ int rihip_inbatch_item_pass(const float* gmat, const float* users, int64_t n_use
                             int64_t n_items, int64_t item_goff, int d, const float* r, int64_t n_global,
                             float* d_items, float* workspace, int precision, void* stream);
 
+/* Mixed in-batch objective L = L_inbatch + hard_weight * L_hard on the stored-G passes (not in the reference): the hard
+ * negatives are mined from the weights the user pass left in `gmat`, no second score sweep.  Call order:
+ *   rihip_rowdot, rihip_inbatch_user_pass (gmat), rihip_inbatch_gmat_mine, rihip_inbatch_mixed_apply,
+ *   rihip_inbatch_item_pass (unchanged, on the boosted gmat and the corrected r), then ONE sum with scale c over the
+ *   user pass's loss parts and the rihip_inbatch_mixed_loss_parts(n_users) parts of apply.
+ * Indices are global as above: user i has gu = user_goff + i, item j has gi = item_goff + j, user i's positive partner is
+ * the item with gi == gu.  Every user's partner must lie inside the given items (item_goff <= user_goff and user_goff +
+ * n_users <= item_goff + n_items), else RIHIP_ERR_ARG.
+ *   sigma_ij  the f32 stored in gmat for (item j, user i), at ((j/32) g_ub + i/32) 1024 + (j%32) 32 + i%32 with
+ *             g_ub = 8 ceil(n_users/256);  n = n_global >= 2;  c = 1/(n(n-1))
+ *   eligible  item j for user i iff j is not i's partner and, when the id arrays are given, item_ids[j] !=
+ *             user_pos_ids[i] (both int64, NULL together).  By index, never by value: ragged slots and the 0 on the
+ *             diagonal are never candidates, an eligible weight of 0 is one.  Only the 32x32 blocks that hold an in-range
+ *             (item, user) pair are read (the blocks the user pass writes).
+ *   order     eligible items by (sigma_ij descending, global item index ascending), on the orderable key of the f32
+ *             bits of sigma_ij + 0.f: a total order, so the result depends neither on arrival order nor on nsplit.  NaN
+ *             weights are undefined behaviour (an unspecified selection; never an index outside [0, n_items) or -1).
+ *   N_i       the items at ranks skip .. skip+m-1 (fewer may exist); c_i = |N_i|, 0 <= c_i <= m
+ *   boost     for c_i > 0: f_i = (float)(1.0 + (double)hard_weight (double)(n-1) / (double)c_i);  sigma'_ij = sigma_ij f_i,
+ *             one round-to-nearest f32 multiply, written back to gmat in place for j in N_i; nothing else in gmat changes
+ *   corrections, with D_ij = sigma'_ij - sigma_ij in f32 and S_i = sum_j D_ij, slots in rank order, fused multiply-adds:
+ *             r_i += c S_i          d_users[i] += c (sum_j D_ij y_j - S_i y_partner)
+ *   loss      z_ij = <u_i, y_j> - pos_i in f32 for the selected pairs only (pos: the array given to the user pass);
+ *             loss_part[b] = hard_weight (n-1) sum_{i in 128-user block b} [c_i > 0] (1/c_i) sum_{j in N_i} softplus(z_ij)
+ *             in double, so that c * (user-pass parts + these parts) = L_inbatch + hard_weight * L_hard
+ *   A row with c_i = 0 changes nothing and contributes nothing; hard_weight = 0 writes nothing but zero loss parts.
+ * Since sigma is non-decreasing in the score, N_i is rihip_inbatch_hard_select's selection except where two distinct
+ * scores round to one f32 weight (saturated weights tie by index).
+ * Limits: 1 <= m <= 32, skip >= 0, skip + m <= 64, n_items < 2^31, n_users < 2^31 / 33; apply: d in {32, 64, 128},
+ * hard_weight finite and >= 0.
+ * rihip_inbatch_gmat_mine: the bandwidth-bound pass, two launches.  neg_idx int32[n_users, m] = LOCAL item indices in
+ *   rank order, -1 in empty slots (empties come last); neg_w f32[n_users, m] = the stored weight BEFORE the boost, 0 in
+ *   empty slots.  nsplit: item-range splits whose partial lists are merged by key, 0 = the library's choice, at most
+ *   rihip_inbatch_gmat_mine_max_nsplit(n_items); the result does not depend on it.  workspace:
+ *   rihip_inbatch_gmat_mine_workspace_bytes(n_users, n_items, m, skip, nsplit) bytes for the same nsplit (-1 for
+ *   arguments outside the limits), 8-byte aligned.
+ * rihip_inbatch_mixed_apply: one launch; a wave handles one user at a time and 32 users in sequence (128 users = one
+ *   loss part per workgroup).  Reads neg_idx / neg_w as mine wrote them (sigma_ij is
+ *   taken from neg_w; a slot whose index is outside [0, n_items) counts as empty).  Mining and applying twice on one
+ *   gmat boosts twice: the second mine sees the boosted weights.  Applying one selection twice rewrites the same
+ *   sigma' but corrects r and d_users twice.
+ * No float atomics, fixed summation order, no allocation, no host synchronisation: two calls on equal inputs are
+ * bitwise equal, and the step is capturable in a graph. */
+int rihip_inbatch_gmat_mine_max_nsplit(int64_t n_items);
+int64_t rihip_inbatch_gmat_mine_workspace_bytes(int64_t n_users, int64_t n_items, int m, int skip, int nsplit);
+int rihip_inbatch_gmat_mine(const float* gmat, int64_t n_users, int64_t user_goff, int64_t n_items, int64_t item_goff,
+                            int m, int skip, const int64_t* user_pos_ids, const int64_t* item_ids, int nsplit,
+                            int* neg_idx, float* neg_w, void* workspace, void* stream);
+int64_t rihip_inbatch_mixed_loss_parts(int64_t n_users);
+int rihip_inbatch_mixed_apply(float* gmat, const float* users, int64_t n_users, int64_t user_goff, const float* items,
+                              int64_t n_items, int64_t item_goff, int d, const float* pos, int m, const int* neg_idx,
+                              const float* neg_w, float hard_weight, int64_t n_global, float* d_users, float* r,
+                              double* loss_part, void* stream);
+
 /* ---- optimiser -----------------------------------------------------------------------------
  * clip_grad_norm_(max_norm) (train_embeddings.py:191): rihip_sumsq writes rihip_sumsq_nparts()
  * partial sums of x^2 per call; rihip_clip_coef reduces any number of partials to

@@ -64,6 +64,13 @@ SIGNATURES = {
                                           C.c_int, vp]),
     "rihip_inbatch_item_pass": (C.c_int, [vp, vp, c_i64, c_i64, c_i64, c_i64, C.c_int, vp, c_i64, vp, vp, C.c_int,
                                           vp]),
+    "rihip_inbatch_gmat_mine_max_nsplit": (C.c_int, [c_i64]),
+    "rihip_inbatch_gmat_mine_workspace_bytes": (c_i64, [c_i64, c_i64, C.c_int, C.c_int, C.c_int]),
+    "rihip_inbatch_gmat_mine": (C.c_int, [vp, c_i64, c_i64, c_i64, c_i64, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                          vp]),
+    "rihip_inbatch_mixed_loss_parts": (c_i64, [c_i64]),
+    "rihip_inbatch_mixed_apply": (C.c_int, [vp, vp, c_i64, c_i64, vp, c_i64, c_i64, C.c_int, vp, C.c_int, vp, vp,
+                                            C.c_float, c_i64, vp, vp, vp, vp]),
     "rihip_sumsq_nparts": (C.c_int, []),
     "rihip_sumsq_multi": (C.c_int, [C.c_int, vp, vp, vp, vp]),
     "rihip_adam_dense_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_float,

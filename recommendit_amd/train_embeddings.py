@@ -185,17 +185,20 @@ class EmbeddingTrainer:
                  embed_dim: int = 64, epochs: int = 10, batch_size: int = 1024, learning_rate: float = 1e-3,
                  device: Optional[str] = None, loss_mode: str = "sampled", table_opt: str = "dense",
                  dropout: float = 0.1, seed: int = 0, temperature: float = 0.05, logq_correction: bool = True,
-                 mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0):
+                 mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0, hard_weight: float = 0.1):
         """Defaults = the reference's settings (src/config.py:13,:24-26); `device` is accepted for
         signature compatibility -- training always runs on the HIP device.
         loss_mode="softmax" (not in the reference): in-batch sampled softmax with `temperature` (0.05 is a customary
         starting value, not a measured optimum), the logQ correction from the training pairs' item counts
         (item_log_q) and masking of duplicate items in a batch.
         loss_mode="hard" (not in the reference): in-batch BPR against each row's `n_hard` highest-scoring other items
-        (ranks hard_skip .. hard_skip + n_hard - 1); 8 is a customary starting value, not a measured optimum."""
-        if loss_mode == "hard":
+        (ranks hard_skip .. hard_skip + n_hard - 1); 8 is a customary starting value, not a measured optimum.
+        loss_mode="mixed" (not in the reference): in-batch BPR plus `hard_weight` times that hard-negative term, mined
+        from the stored in-batch weights; 0.1 is a starting value, not a measured optimum (it collapsed in
+        the one short run made, 0.01 did not)."""
+        if loss_mode in ("hard", "mixed"):
             _check_hard_args(n_hard, hard_skip)
-        self.n_hard, self.hard_skip = n_hard, hard_skip
+        self.n_hard, self.hard_skip, self.hard_weight = n_hard, hard_skip, hard_weight
         self.data_dir, self.model_output_path = data_dir, model_output_path
         self.embed_dim, self.epochs, self.batch_size, self.learning_rate = embed_dim, epochs, batch_size, learning_rate
         self.loss_mode, self.table_opt, self.dropout, self.seed = loss_mode, table_opt, dropout, seed
@@ -223,6 +226,9 @@ class EmbeddingTrainer:
             extra = dict(temperature=self.temperature, item_logq=logq, mask_duplicates=self.mask_duplicates)
         if self.loss_mode == "hard":
             extra = dict(n_hard=self.n_hard, hard_skip=self.hard_skip, mask_duplicates=self.mask_duplicates)
+        if self.loss_mode == "mixed":
+            extra = dict(n_hard=self.n_hard, hard_skip=self.hard_skip, mask_duplicates=self.mask_duplicates,
+                         hard_weight=self.hard_weight)
         trainer = HipBPRTrainer(model, self.batch_size, lr=self.learning_rate, weight_decay=1e-5, max_norm=1.0,
                                 loss_mode=self.loss_mode, table_opt=self.table_opt, seed=self.seed, **extra)
         gen = torch.Generator(device=self.device)

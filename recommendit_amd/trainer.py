@@ -118,7 +118,7 @@ class HipBPRTrainer:
                  distributed: bool = False, item_shard: str = "replicate", exchange_cap: Optional[int] = None,
                  persistent: Optional[bool] = None, temperature: float = 0.05,
                  item_logq: Optional[torch.Tensor] = None, mask_duplicates: bool = True, n_hard: int = 8,
-                 hard_skip: int = 0):
+                 hard_skip: int = 0, hard_weight: float = 0.1):
         """distributed=True (or a process_group): this trainer is one rank of a collective job -- EVERY rank of the
         group must construct it and call step() in lock-step.  Default False even when torch.distributed is
         initialised, so that a single-rank trainer inside a distributed program never issues collectives.
@@ -142,8 +142,28 @@ class HipBPRTrainer:
         highest-scoring other rows' items (ranks hard_skip .. hard_skip + n_hard - 1); step() takes the same [B] ids as
         "inbatch".  n_hard = 8 is a customary starting value, not a measured optimum, and the mode trains on the hard
         negatives ALONE, which collapsed to loss ln 2 in the short run of DESIGN.md §5b.  mask_duplicates: a row whose item
-        equals another row's positive is never that row's negative.  Single GPU for now."""
-        assert loss_mode in ("sampled", "inbatch", "softmax", "hard") and table_opt in ("dense", "sparse")
+        equals another row's positive is never that row's negative.  Single GPU for now.
+        loss_mode="mixed": in-batch BPR plus hard_weight times the hard-negative term (rihip_inbatch_gmat_mine /
+        rihip_inbatch_mixed_apply between the two stored-G passes of "inbatch"): the n_hard negatives of a row are its
+        largest stored weights, ranks hard_skip .. hard_skip + n_hard - 1, mask_duplicates as in "hard".  hard_weight = 0.1
+        is a starting value, not a measured optimum (in the short run of DESIGN.md §5b 0.1 collapsed like "hard", 0.01
+        trained like "inbatch"); 0 reproduces "inbatch" bit for bit.  Needs the stored-G form
+        (embed_dim 32 / 64 / 128, inbatch_precision 0 or 2, inbatch_store_g not False, memory for the B x B weights:
+        half of the free device memory when inbatch_store_g is None, all of it when True; ValueError otherwise);
+        single GPU for now."""
+        assert loss_mode in ("sampled", "inbatch", "softmax", "hard", "mixed") and table_opt in ("dense", "sparse")
+        if loss_mode == "mixed":
+            _check_hard_args(n_hard, hard_skip)
+            if not (math.isfinite(float(hard_weight)) and float(hard_weight) >= 0.0):
+                raise ValueError(f"HipBPRTrainer: hard_weight must be finite and >= 0, got {hard_weight!r}")
+            if distributed or process_group is not None:
+                raise ValueError("HipBPRTrainer: loss_mode='mixed' is single-GPU for now (the rectangular "
+                                 "rihip_inbatch_gmat_mine / rihip_inbatch_mixed_apply entries are ready; the multi-GPU "
+                                 "trainer wiring is not)")
+            if model.embed_dim not in (32, 64, 128) or int(inbatch_precision) not in (0, 2) or inbatch_store_g is False:
+                raise ValueError("HipBPRTrainer: loss_mode='mixed' runs on the stored-G passes only: it needs embed_dim "
+                                 f"32, 64 or 128 (got {model.embed_dim}), inbatch_precision 0 or 2 (got "
+                                 f"{inbatch_precision}) and inbatch_store_g not False")
         if loss_mode == "hard":
             _check_hard_args(n_hard, hard_skip)
             if distributed or process_group is not None:
@@ -293,7 +313,7 @@ class HipBPRTrainer:
             self.hard_ws = torch.empty((self.lib.rihip_inbatch_hard_workspace_bytes(B, B, self.n_hard),),
                                        dtype=torch.uint8, device=self.dev)
             self.n_lparts = self.lib.rihip_inbatch_hard_loss_parts(B)
-        if loss_mode == "inbatch":
+        if loss_mode in ("inbatch", "mixed"):
             self.pos = torch.empty((B,), **f32); self.r = torch.empty((B,), **f32)
             # stored-G form (exact f32 only): G^T of the local users x all items stays in HBM between the two passes
             # (17 GB at B = 65536 on one GPU, 2 GB per rank on eight) and removes the second score sweep
@@ -304,8 +324,26 @@ class HipBPRTrainer:
                 store = self.inbatch_precision in (0, 2) and 4 * ng <= 0.5 * free_b
             # (the stored-G passes exist for embed_dim 32/64/128; other widths run the runtime-width two-sweep kernel)
             self.inbatch_store_g = bool(store) and self.inbatch_precision in (0, 2) and d in (32, 64, 128)
+            if loss_mode == "mixed":   # no two-sweep form to fall back to: say so before the allocation fails
+                free_b = torch.cuda.mem_get_info(self.dev)[0]
+                if not self.inbatch_store_g or 4 * ng > free_b:
+                    raise ValueError(f"HipBPRTrainer: loss_mode='mixed' needs the {4 * ng / 2 ** 20:.1f} MiB of stored "
+                                     f"weights of batch {B} to fit in half of the free device memory (in all of it with "
+                                     f"inbatch_store_g=True); {free_b / 2 ** 20:.1f} MiB are free")
             if self.inbatch_store_g:
                 self.gmat = torch.empty((ng,), **f32)
+            if loss_mode == "mixed":
+                self.hard_weight = float(hard_weight)
+                self.n_hard, self.hard_skip = int(n_hard), int(hard_skip)
+                self.mask_duplicates = bool(mask_duplicates)
+                self.neg_idx = torch.empty((B, self.n_hard), dtype=torch.int32, device=self.dev)
+                self.neg_w = torch.empty((B, self.n_hard), **f32)
+                self.mine_ws = torch.empty((self.lib.rihip_inbatch_gmat_mine_workspace_bytes(
+                    B, B, self.n_hard, self.hard_skip, 0),), dtype=torch.uint8, device=self.dev)
+                # the hard term's loss parts go behind the user pass's: one fold under the scale c covers both
+                self.n_mixparts = self.lib.rihip_inbatch_mixed_loss_parts(B)
+                if self.lpart.numel() < self.n_lparts + self.n_mixparts:
+                    self.lpart = torch.zeros((self.n_lparts + self.n_mixparts,), dtype=torch.float64, device=self.dev)
             if self.dist:
                 W = self.world
                 self.I_all = torch.empty((W * B, d), **f32)
@@ -542,7 +580,7 @@ class HipBPRTrainer:
         elif self.loss_mode == "hard":
             self._hard(item_ids, st)
         else:
-            self._inbatch(st)
+            self._inbatch(st, item_ids)
 
         pp = self.part.data_ptr()
         o1 = self.np_mlp
@@ -711,7 +749,7 @@ class HipBPRTrainer:
     def _sweep(self, *args) -> None:
         self._timed(self.lib.rihip_inbatch_sweep, "inbatch_sweep", *args)
 
-    def _inbatch(self, st: int) -> None:
+    def _inbatch(self, st: int, item_ids: Optional[torch.Tensor] = None) -> None:
         lib, B, d, W = self.lib, self.B, self.d, self.world
         G, off = W * B, self.rank * B
         L.check(lib.rihip_rowdot(self.U.data_ptr(), self.I.data_ptr(), B, 0, d, self.pos.data_ptr(), st), "rowdot")
@@ -727,6 +765,17 @@ class HipBPRTrainer:
             self._timed(lib.rihip_inbatch_user_pass, "inbatch_user_pass", self.U.data_ptr(), B, off, I_all.data_ptr(),
                         G, 0, d, self.pos.data_ptr(), G, self.dU.data_ptr(), self.r.data_ptr(), self.lpart.data_ptr(),
                         self.sws.data_ptr(), self.gmat.data_ptr(), self.inbatch_precision, st)
+            if self.loss_mode == "mixed":
+                # the row's largest stored weights are its hardest negatives: mine them from G, boost them in place and
+                # correct dU and r; the item pass below then yields the mixed dI unchanged
+                ids = item_ids.data_ptr() if self.mask_duplicates else None
+                self._timed(lib.rihip_inbatch_gmat_mine, "inbatch_gmat_mine", self.gmat.data_ptr(), B, 0, B, 0,
+                            self.n_hard, self.hard_skip, ids, ids, 0, self.neg_idx.data_ptr(), self.neg_w.data_ptr(),
+                            self.mine_ws.data_ptr(), st)
+                self._timed(lib.rihip_inbatch_mixed_apply, "inbatch_mixed_apply", self.gmat.data_ptr(), self.U.data_ptr(),
+                            B, 0, self.I.data_ptr(), B, 0, d, self.pos.data_ptr(), self.n_hard, self.neg_idx.data_ptr(),
+                            self.neg_w.data_ptr(), self.hard_weight, B, self.dU.data_ptr(), self.r.data_ptr(),
+                            self.lpart[self.n_lparts:].data_ptr(), st)
             dI_all = self.dI if not self.dist else self.dI_all
             self._timed(lib.rihip_inbatch_item_pass, "inbatch_item_pass", self.gmat.data_ptr(), self.U.data_ptr(), B,
                         off, G, 0, d, self.r.data_ptr(), G, dI_all.data_ptr(), self.sws.data_ptr(), self.inbatch_precision, st)
@@ -761,7 +810,8 @@ class HipBPRTrainer:
                                            self.loss.data_ptr(), st), "sum_partials")
             self._loss_fold = None   # (summed over the ranks together with the squared norms in step())
         else:   # summed by the clip-coefficient launch
-            self._loss_fold = (self.lpart.data_ptr(), self.n_lparts, 1.0 / (G * (G - 1.0)))
+            n_parts = self.n_lparts + (self.n_mixparts if self.loss_mode == "mixed" else 0)
+            self._loss_fold = (self.lpart.data_ptr(), n_parts, 1.0 / (G * (G - 1.0)))
 
 
     def _softmax(self, item_ids: torch.Tensor, st: int) -> None:

@@ -14,6 +14,7 @@ every forward raises RuntimeError.
 from __future__ import annotations
 
 import logging
+import math
 import os
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
@@ -340,6 +341,77 @@ def hard_loss_and_grads(U: torch.Tensor, I: torch.Tensor, m: int, skip: int = 0,
     return loss, dU, dI, neg_idx
 
 
+_MIXED_FALLBACK = "use in_batch_bpr_loss + hard_weight * in_batch_hard_bpr_loss through autograd instead"
+
+
+def _check_hard_weight(hard_weight: float, who: str) -> float:
+    hw = float(hard_weight)
+    if not (math.isfinite(hw) and hw >= 0.0):
+        raise ValueError(f"{who}: hard_weight must be finite and >= 0, got {hard_weight!r}")
+    return hw
+
+
+def mixed_loss_and_grads(U: torch.Tensor, I: torch.Tensor, hard_weight: float, m: int, skip: int = 0,
+                         item_ids: Optional[torch.Tensor] = None, precision: int = 0):
+    """Single-GPU mixed objective L_inbatch + hard_weight * L_hard on the stored-G passes (include/recommendit_hip.h:
+    rihip_inbatch_gmat_mine / rihip_inbatch_mixed_apply), square form: U, I [B >= 2, d], row i of I is user i's
+    positive, n_global = B, user_pos_ids = item_ids.  The hard negatives are the largest stored weights of each row, so
+    the whole hard term is one read of G, a sparse correction and the item pass that runs anyway.  Returns (loss, dU,
+    dI, neg_idx) on the device; no host synchronisation."""
+    hw = _check_hard_weight(hard_weight, "mixed_loss_and_grads")
+    if U.dim() == 2 and U.shape[1] not in (32, 64, 128):
+        raise ValueError(f"mixed_loss_and_grads: the stored-G passes exist for embedding widths 32, 64 and 128, got "
+                         f"{U.shape[1]}; " + _MIXED_FALLBACK)
+    if precision not in (0, 2):
+        raise ValueError(f"mixed_loss_and_grads: the stored-G passes take precision 0 or 2, got {precision}; "
+                         + _MIXED_FALLBACK)
+    Uc, Ic, ids = _hard_inputs(U, I, m, skip, item_ids)
+    lib, dev = L.lib(), L.device()
+    B, d = Uc.shape
+    m, skip = int(m), int(skip)
+    if B < 2:
+        raise ValueError("mixed_loss_and_grads needs B >= 2 rows")
+    ng = lib.rihip_inbatch_gmat_floats(B, B)
+    if 4 * ng > (4 << 30):
+        raise ValueError(f"mixed_loss_and_grads: the stored weights of B = {B} rows take {4 * ng / 2 ** 30:.1f} GiB, over "
+                         "the 4 GiB this function allocates per call; " + _MIXED_FALLBACK
+                         + ", or train with HipBPRTrainer(loss_mode='mixed'), which keeps the buffer")
+    st = L.stream_ptr()
+    f32 = dict(dtype=torch.float32, device=dev)
+    posv = torch.empty((B,), **f32)
+    L.check(lib.rihip_rowdot(Uc.data_ptr(), Ic.data_ptr(), B, 0, d, posv.data_ptr(), st), "rowdot")
+    dU, dI = torch.empty_like(Uc), torch.empty_like(Ic)
+    rv = torch.empty((B,), **f32)
+    n_in, n_mx = lib.rihip_inbatch_loss_parts(B, B), lib.rihip_inbatch_mixed_loss_parts(B)
+    part = torch.zeros((max(lib.rihip_inbatch_workspace_doubles(B), n_in) + n_mx,), dtype=torch.float64, device=dev)
+    ws = torch.empty((lib.rihip_inbatch_workspace_floats(B, B, d),), **f32)
+    gm = torch.empty((ng,), **f32)
+    neg_idx = torch.empty((B, m), dtype=torch.int32, device=dev)
+    neg_w = torch.empty((B, m), **f32)
+    mws = torch.empty((lib.rihip_inbatch_gmat_mine_workspace_bytes(B, B, m, skip, 0),), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), **f32)
+    L.check(lib.rihip_inbatch_user_pass(Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, posv.data_ptr(), B, dU.data_ptr(),
+                                        rv.data_ptr(), part.data_ptr(), ws.data_ptr(), gm.data_ptr(), precision, st),
+            "inbatch_user_pass")
+    L.check(lib.rihip_inbatch_gmat_mine(gm.data_ptr(), B, 0, B, 0, m, skip, L.ptr(ids), L.ptr(ids), 0, neg_idx.data_ptr(),
+                                        neg_w.data_ptr(), mws.data_ptr(), st), "inbatch_gmat_mine")
+    L.check(lib.rihip_inbatch_mixed_apply(gm.data_ptr(), Uc.data_ptr(), B, 0, Ic.data_ptr(), B, 0, d, posv.data_ptr(), m,
+                                          neg_idx.data_ptr(), neg_w.data_ptr(), hw, B, dU.data_ptr(), rv.data_ptr(),
+                                          part[n_in:].data_ptr(), st), "inbatch_mixed_apply")
+    L.check(lib.rihip_inbatch_item_pass(gm.data_ptr(), Uc.data_ptr(), B, 0, B, 0, d, rv.data_ptr(), B, dI.data_ptr(),
+                                        ws.data_ptr(), precision, st), "inbatch_item_pass")
+    L.check(lib.rihip_sum_partials(part.data_ptr(), n_in + n_mx, 1.0 / (B * (B - 1.0)), loss.data_ptr(), st),
+            "sum_partials")
+    return loss, dU, dI, neg_idx
+
+
+def _mixed_or_nan(U: torch.Tensor, I: torch.Tensor, hard_weight: float, m: int, skip: int, item_ids):
+    if U.shape[0] < 2:  # as in_batch_bpr_loss: a mean over an empty negative set
+        return (torch.full((), float("nan"), dtype=torch.float32, device=U.device), torch.zeros_like(U),
+                torch.zeros_like(I))
+    return mixed_loss_and_grads(U, I, hard_weight, m, skip, item_ids)
+
+
 class TwoTowerModel(nn.Module):
     """two_tower.py:75-251 with HIP towers / losses."""
 
@@ -405,6 +477,25 @@ class TwoTowerModel(nn.Module):
             raise ValueError(f"item_ids must have one entry per row of the batch ({user_emb.shape[0]})")
         in_dev = user_emb.device
         loss = _ClosedFormLossFn.apply(user_emb, item_emb, hard_loss_and_grads, int(n_hard), int(skip), item_ids)
+        return loss if in_dev.type == "cuda" else loss.to(in_dev)
+
+    def in_batch_mixed_loss(self, user_emb, item_emb, hard_weight: float = 0.1, n_hard: int = 8, skip: int = 0,
+                            item_ids=None) -> torch.Tensor:
+        """Mixed in-batch objective (not in the reference): in_batch_bpr_loss + ``hard_weight`` * in_batch_hard_bpr_loss
+        in one pass over the stored weights: every row's ``n_hard`` hardest negatives are its largest
+        weights sigma(s_ij - s_ii) (ranks ``skip`` .. ``skip + n_hard - 1``; ties, saturated weights among them, go to
+        the lower row).  ``item_ids`` as in in_batch_hard_bpr_loss.  hard_weight = 0.1 and n_hard = 8 are starting
+        values, not measured optima: in the one short run of DESIGN.md §5b the weights 0.1, 0.5 and 1.0 collapsed to
+        (1 + hard_weight) ln 2 as the hard term alone does, 0.01 trained like in-batch BPR.  Needs an embedding width of
+        32, 64 or 128 and a batch whose B x B weights fit in 4 GiB; otherwise add the two losses through autograd."""
+        _check_hard_args(n_hard, skip)
+        hw = _check_hard_weight(hard_weight, "in_batch_mixed_loss")
+        if user_emb.dim() != 2 or user_emb.shape[0] < 1 or user_emb.shape != item_emb.shape:
+            raise ValueError("in_batch_mixed_loss needs user_emb and item_emb of the same shape [B >= 1, d]")
+        if item_ids is not None and item_ids.numel() != user_emb.shape[0]:
+            raise ValueError(f"item_ids must have one entry per row of the batch ({user_emb.shape[0]})")
+        in_dev = user_emb.device
+        loss = _ClosedFormLossFn.apply(user_emb, item_emb, _mixed_or_nan, hw, int(n_hard), int(skip), item_ids)
         return loss if in_dev.type == "cuda" else loss.to(in_dev)
 
     # -- inference helpers (two_tower.py:166-210) ---------------------------------------------

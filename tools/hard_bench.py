@@ -4,13 +4,17 @@ retrieves (HIP events, mean of --reps after --warmup).  Nothing here is a gate.
 --launch   rihip_inbatch_hard_select and rihip_inbatch_hard_grads (ids given, m = 8) and a whole
            HipBPRTrainer(loss_mode="hard") step at B in {8192, 65536}, d in {64, 128}.  Beside them, same run and same
            shape: rihip_inbatch_softmax_user_sweep (the yardstick: the select sweep performs one of its two products and
-           no exponentials) and a whole loss_mode="inbatch" step.
+           no exponentials) and a whole loss_mode="inbatch" step.  The mixed objective: rihip_inbatch_gmat_mine on the
+           weights a user pass left (its rate = the bytes of the blocks it must read, 4 B^2, over its time),
+           rihip_inbatch_mixed_apply, and a whole loss_mode="mixed" step, to be held against inbatch step + select sweep
+           + gradient entry, which is what the autograd sum of the two losses costs.
 --quality  hold-out recall@50 on ml1m_like() after --epochs epochs, the protocol of tools/coldstart_bench.py (80 / 20
            split of every user's liked items, top 50 of the trained row with the training items excluded, exact index):
-           in-batch BPR, in-batch softmax, hard negatives, and the popularity list.  One run each, unpinned.
+           in-batch BPR, in-batch softmax, hard negatives, the mixed objective at hard_weight 0.1 / 0.5 / 1.0, and the
+           popularity list.  One run each, unpinned.
 
 python tools/hard_bench.py [--launch] [--quality] [--reps 20] [--warmup 3] [--epochs 3] [--users 2000] [--n-hard 8]
-                          [--arms inbatch,softmax,hard]
+                          [--arms inbatch,softmax,hard,mixed0.1,mixed0.5,mixed1.0] [--hard-weight 0.1]
 """
 import argparse
 import json
@@ -33,7 +37,8 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--users", type=int, default=2000)
 ap.add_argument("--n-hard", type=int, default=8)
-ap.add_argument("--arms", default="inbatch,softmax,hard", help="--quality: which losses to train")
+ap.add_argument("--hard-weight", type=float, default=0.1, help="--launch: weight of the mixed step and of apply")
+ap.add_argument("--arms", default="inbatch,softmax,hard,mixed0.1,mixed0.5,mixed1.0", help="--quality: which losses to train")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
@@ -66,7 +71,9 @@ def step_ms(mode, B, d, n_rows=200000):
     torch.manual_seed(1)
     model = TwoTowerModel(n_rows, n_rows, embed_dim=d, hidden_dim=128, dropout=0.1)
     model.train()
-    kw = dict(n_hard=args.n_hard) if mode == "hard" else {}
+    kw = dict(n_hard=args.n_hard) if mode in ("hard", "mixed") else {}
+    if mode == "mixed":
+        kw["hard_weight"] = args.hard_weight
     tr = HipBPRTrainer(model, B, lr=1e-3, weight_decay=1e-5, loss_mode=mode, table_opt="sparse", seed=0, **kw)
     batches = []
     for _ in range(4):
@@ -116,9 +123,35 @@ if args.launch:
             row = {"hard_select_ms": timed(select), "hard_grads_ms": timed(grads), "softmax_user_ms": timed(sm_user)}
             row["select_over_softmax_user"] = row["hard_select_ms"] / row["softmax_user_ms"]
             row["select_tflops"] = 2.0 * B * B * d / (row["hard_select_ms"] * 1e-3) / 1e12
-            del U, Y, dU, dI, ws
+            # the whole steps before the 4 B^2 bytes of weights of the mine launch are allocated: measured after them, in
+            # one process, the "hard" step read 6 % slower at B = 65536, d = 128 than alone (profiles/r22_mixed.md)
             row["hard_step_ms"] = step_ms("hard", B, d)
             row["inbatch_step_ms"] = step_ms("inbatch", B, d)
+            row["mixed_step_ms"] = step_ms("mixed", B, d)
+            # the mixed objective's two launches, on the weights of a real user pass
+            pos, r = torch.empty((B,), **f32), torch.empty((B,), **f32)
+            sws = torch.empty((lib.rihip_inbatch_workspace_floats(B, B, d),), **f32)
+            gm = torch.empty((lib.rihip_inbatch_gmat_floats(B, B),), **f32)
+            neg_w = torch.empty((B, m), **f32)
+            mws = torch.empty((lib.rihip_inbatch_gmat_mine_workspace_bytes(B, B, m, 0, 0),), dtype=torch.uint8, device=dev)
+            mpart = torch.zeros((lib.rihip_inbatch_mixed_loss_parts(B),), dtype=torch.float64, device=dev)
+            L.check(lib.rihip_rowdot(U.data_ptr(), Y.data_ptr(), B, 0, d, pos.data_ptr(), st))
+            L.check(lib.rihip_inbatch_user_pass(U.data_ptr(), B, 0, Y.data_ptr(), B, 0, d, pos.data_ptr(), B, dU.data_ptr(),
+                                                r.data_ptr(), part.data_ptr(), sws.data_ptr(), gm.data_ptr(), 0, st))
+
+            def mine():
+                L.check(lib.rihip_inbatch_gmat_mine(gm.data_ptr(), B, 0, B, 0, m, 0, ids.data_ptr(), ids.data_ptr(), 0,
+                                                    neg_idx.data_ptr(), neg_w.data_ptr(), mws.data_ptr(), st))
+
+            def apply():   # boosts in place every time: the values grow from call to call, the work does not
+                L.check(lib.rihip_inbatch_mixed_apply(gm.data_ptr(), U.data_ptr(), B, 0, Y.data_ptr(), B, 0, d,
+                                                      pos.data_ptr(), m, neg_idx.data_ptr(), neg_w.data_ptr(),
+                                                      args.hard_weight, B, dU.data_ptr(), r.data_ptr(), mpart.data_ptr(), st))
+            row["mine_ms"] = timed(mine)
+            row["mine_TBps"] = 4.0 * B * B / (row["mine_ms"] * 1e-3) / 1e12
+            row["apply_ms"] = timed(apply)
+            del U, Y, dU, dI, ws, gm, sws, mws
+            row["autograd_sum_ms"] = row["inbatch_step_ms"] + row["hard_select_ms"] + row["hard_grads_ms"]
             out[f"launch B={B} d={d} m={m}"] = row
             print(f"[hard] B={B} d={d} m={m}: " + ", ".join(f"{k} {v:.3f}" for k, v in row.items()), flush=True)
 
@@ -153,6 +186,9 @@ if args.quality:
     arms = {"inbatch": dict(loss_mode="inbatch"),
             "softmax": dict(loss_mode="softmax"),
             "hard": dict(loss_mode="hard", n_hard=args.n_hard)}
+    for name in args.arms.split(","):       # "mixed<w>": the mixed objective at hard_weight w (the default runs three)
+        if name.startswith("mixed"):
+            arms[name] = dict(loss_mode="mixed", n_hard=args.n_hard, hard_weight=float(name[len("mixed"):]))
     for name, kw in arms.items():
         if name not in args.arms.split(","):
             continue
