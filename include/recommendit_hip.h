@@ -173,6 +173,33 @@ int rihip_bpr_pair_loss(const float* U, const float* P, const float* N, int64_t 
                         float* dP, float* dN, double* workspace, void* stream);
 int64_t rihip_bpr_pair_nparts(int64_t B);
 
+/* rihip_bpr_multi_loss (not in the reference): sampled-negative BPR with K negatives per positive.
+ *   z_ik = u_i.p_i - u_i.n_ik      L = 1/(B K) sum_i sum_k softplus(-z_ik)      g_ik = sigma(-z_ik) / (B K)
+ *   dN_ik = g_ik u_i               dP_i = -(sum_k g_ik) u_i                     dU_i = -sum_k g_ik (p_i - n_ik)
+ * U, P, dU, dP: [B, d].  N, dN: [K, B, d], k-major: negative k of sample i is row k B + i, so K = 1 is the pos || neg
+ * layout of rihip_bpr_pair_loss.  The loss is the MEAN over the B K pairs, not a sum over k: the loss scale and the
+ * gradient norm that the clip sees then mean the same thing at every K.  The K negatives of a sample are independent
+ * terms (a repeated negative counts twice).  The outputs must not overlap the inputs or each other.
+ * Operation order (float32 throughout, a product may be fused into the addition that consumes it):
+ *   u_i.x is a sum of d products in a fixed tree: with 16-byte accesses (d a multiple of 4 up to 256, all six pointers
+ *     16-byte aligned; tuned for d = 32 / 64 / 128) each lane forms (x0 y0 + x1 y1) + (x2 y2 + x3 y3) of its four
+ *     columns and the lanes of a row are combined by a butterfly; otherwise (any d >= 1, any alignment) lane l adds the
+ *     products of columns l, l + 64, ... in order and the 64 lanes are combined by a butterfly.  Either way the result
+ *     is within d u S of the exact dot product (u = 2^-24, S = the sum of the absolute products).
+ *   z_ik = fl(u_i.p_i - u_i.n_ik): u_i.p_i is formed once per sample, one rounding on the difference.
+ *   e = expf(-|z|); softplus(-z) = max(-z, 0) + log1pf(e); sigma(-z) = e / (1 + e) for z >= 0, 1 / (1 + e) for z < 0.
+ *   g_ik = sigma(-z_ik) * inv, inv = 1.0f / (float)(B K).
+ *   k runs ascending.  dN_ik = g_ik * u_i.  The sums over k are sequential float32 additions from 0:
+ *     s_k = s_(k-1) + g_ik,  a_k = a_(k-1) + g_ik * (p_i - n_ik) per column;  dP_i = (-s_K) * u_i,  dU_i = -a_K.
+ *   Loss: every softplus value is added, as a double, into one partial per workgroup in a fixed order.
+ * workspace: >= 1024 doubles; it receives rihip_bpr_multi_nparts(B, K) partials.  loss may be NULL: the value is then
+ * 1/(B K) * sum(workspace[0 .. nparts)), summed later by the caller (rihip_sum_partials / rihip_clip_coef_step), exactly
+ * as with the pair loss.  No float atomics: two calls are bitwise equal.  K = 1 IS rihip_bpr_pair_loss (same launches,
+ * same bits).  RIHIP_ERR_ARG: a null pointer (loss excepted), B < 1, d < 1, K < 1, (1 + K) B > 2^31 - 1. */
+int rihip_bpr_multi_loss(const float* U, const float* P, const float* N, int64_t B, int K, int d, float* loss, float* dU,
+                         float* dP, float* dN, double* workspace, void* stream);
+int64_t rihip_bpr_multi_nparts(int64_t B, int K);
+
 /* In-batch-negative BPR (TwoTowerModel.in_batch_bpr_loss, two_tower.py:132-160, closed form
  *   L = 1/(B(B-1)) sum_i sum_{j!=i} softplus(s_ij - s_ii)) is three calls:
  *   rihip_rowdot        pos[i] = U[i].I[i+i_offset]
@@ -757,6 +784,24 @@ int rihip_feature_log_rewind(int64_t* cursor, void* stream);
 int rihip_sample_negatives(const int64_t* users, int64_t n, const int64_t* catalog, int64_t n_catalog,
                            const int64_t* rated_keys, int64_t n_rated, int64_t key_stride, uint64_t seed,
                            int max_attempts, int64_t* neg_out, int* gave_up, void* stream);
+/* rihip_sample_negatives_multi (not in the reference): K negatives per sample, uniform or proportional to item weights.
+ * neg_out: [K n], k-major (negative k of sample i at k n + i).  One thread per output slot s = k n + i; attempt a draws
+ *   r = splitmix64(splitmix64(seed ^ splitmix64(s)) + a),  column j = ((r >> 32) * n_catalog) >> 32,
+ *   pick = j                                                      (alias_prob = alias_idx = NULL: uniform)
+ *   pick = ((uint32_t)r < alias_prob[j]) ? j : alias_idx[j]       (Walker's alias method: two dependent reads per
+ *                                                                  attempt where a search of the CDF would take twenty)
+ * and the negative is catalog[pick], re-drawn while users[i] * key_stride + catalog[pick] is in rated_keys; after
+ * max_attempts the slot keeps its last pick and adds one to *gave_up.  alias_prob u32 [n_catalog] (the probability of
+ * keeping the column, in units of 2^-32: a column that is always kept holds any value with alias_idx[j] = j),
+ * alias_idx i32 [n_catalog]; an alias_idx[j] outside [0, n_catalog) is read as j, so no table content makes the kernel
+ * read out of bounds.  The K draws of a sample are independent (WITH replacement: a sample may hold the same negative
+ * twice).  At K = 1 the slot is the sample, so K = 1 with a NULL table equals rihip_sample_negatives bit for bit.
+ * RIHIP_ERR_ARG: as rihip_sample_negatives, plus K < 1, exactly one of the two table pointers NULL, a table with
+ * n_catalog > 2^31 - 1, K n beyond one launch (256 (2^31 - 1) slots). */
+int rihip_sample_negatives_multi(const int64_t* users, int64_t n, int K, const int64_t* catalog, int64_t n_catalog,
+                                 const uint32_t* alias_prob, const int32_t* alias_idx, const int64_t* rated_keys,
+                                 int64_t n_rated, int64_t key_stride, uint64_t seed, int max_attempts, int64_t* neg_out,
+                                 int* gave_up, void* stream);
 
 /* ---- LambdaMART training set from raw ratings ---------------------------------------------------
  * Replaces the pandas stages of FeatureEngineer (src/features/feature_engineering.py): build_user_features :91-166,

@@ -83,6 +83,8 @@ SIGNATURES = {
     "rihip_clip_coef_step": (C.c_int, [vp, c_i64, C.c_float, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, c_i64,
                                        C.c_double, vp, vp]),
     "rihip_bpr_pair_nparts": (c_i64, [c_i64]),
+    "rihip_bpr_multi_loss": (C.c_int, [vp, vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "rihip_bpr_multi_nparts": (c_i64, [c_i64, C.c_int]),
     "rihip_tower_backward_partial": (C.c_int, [vp, c_i64, vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
                                                C.c_float, vp, vp, vp, vp, vp]),
     "rihip_backward_reduce2_scatter2": (C.c_int, [C.c_int, C.c_int, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, c_i64,
@@ -152,6 +154,8 @@ SIGNATURES = {
                                              vp, vp]),
     "rihip_free": (None, [vp]),
     "rihip_sample_negatives": (C.c_int, [vp, c_i64, vp, c_i64, vp, c_i64, c_i64, C.c_uint64, C.c_int, vp, vp, vp]),
+    "rihip_sample_negatives_multi": (C.c_int, [vp, c_i64, C.c_int, vp, c_i64, vp, vp, vp, c_i64, c_i64, C.c_uint64,
+                                               C.c_int, vp, vp, vp]),
     "rihip_bpr_step_persistent_supported": (C.c_int, [c_i64, C.c_int, C.c_int]),
     "rihip_bpr_step_scratch_doubles": (c_i64, [c_i64]),
     "rihip_bpr_step_persistent": (C.c_int, [vp, vp]),

@@ -4,7 +4,8 @@
 adds a device-side batch sampler (positives shuffled on the GPU, one rejection-sampled negative per
 positive drawn by a HIP kernel from the catalogue and rejected while in the user's *rated* set
 -- :58-63 --, genre rows gathered from a device table), because the reference's own DataLoader tops out at ~21 k
-samples/s and would starve the kernels.
+samples/s and would starve the kernels.  Not in the reference: ``n_negatives=K`` negatives per positive
+(``sample_negatives`` / ``epoch_batches``) and draws proportional to ``(count + 1)^alpha`` (``set_negative_sampling``).
 
 ``EmbeddingTrainer`` keeps the reference's constructor arguments and ``train()`` flow (:131-223:
 Adam(lr, wd=1e-5) + clip 1.0 + CosineAnnealingLR stepped per epoch, best-loss checkpoint, final
@@ -22,6 +23,7 @@ import pandas as pd
 import torch
 
 from . import _lib as L
+from .negative_sampling import alias_table, popularity_weights
 from .synthetic import GENRES, N_GENRES
 from .trainer import HipBPRTrainer, cosine_lr
 from .two_tower import TwoTowerModel, _check_hard_args
@@ -62,6 +64,9 @@ def build_item_genre_dict(movies_df: pd.DataFrame) -> Dict[int, np.ndarray]:
 class UserItemDataset:
     def __init__(self, ratings_df: pd.DataFrame, item_genre_dict: Dict[int, np.ndarray], all_item_ids: List[int],
                  n_negatives: int = 4, min_rating: float = 4.0, device_tables: bool = True):
+        """n_negatives is accepted and unused, like the reference's (:35,:40): it is the reference's quirk, and making
+        its default of 4 live would silently change every existing run.  The number of negatives per positive is the
+        n_negatives argument of sample_negatives / epoch_batches (default 1)."""
         self.item_genre_dict = item_genre_dict
         self.all_item_ids = all_item_ids
         self.n_negatives = n_negatives  # accepted and unused, like the reference (:35,:40)
@@ -73,6 +78,9 @@ class UserItemDataset:
         self._ratings_i = ratings_df["item_id"].values.astype(np.int64)
         self._user_rated: Optional[Dict[int, set]] = None
         self._dev_ready = False
+        self._neg_weights: Optional[np.ndarray] = None     # None = uniform draws
+        self._alias_host: Optional[Tuple[np.ndarray, np.ndarray]] = None
+        self._alias_dev: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         logger.info("Dataset: %d positive pairs", len(self.user_ids))
 
     def __len__(self) -> int:
@@ -122,15 +130,72 @@ class UserItemDataset:
         self.d_gave_up = torch.zeros(1, dtype=torch.int32, device=dev)   # samples whose attempts ran out (never read per call)
         self._dev_ready = True
 
-    def sample_negatives(self, users: torch.Tensor, gen: torch.Generator, max_attempts: int = 1000) -> torch.Tensor:
+    def catalog_counts(self) -> np.ndarray:
+        """count_j: the dataset's positives on catalogue position j (int64 [len(all_item_ids)]); positives on items
+        outside the catalogue count nowhere"""
+        order = np.argsort(self.all_items_array, kind="stable")
+        sorted_items = self.all_items_array[order]
+        at = np.searchsorted(sorted_items, self.item_ids)
+        hit = (at < sorted_items.shape[0]) & (sorted_items[np.minimum(at, sorted_items.shape[0] - 1)] == self.item_ids)
+        cnt = np.zeros(self.all_items_array.shape[0], dtype=np.int64)
+        np.add.at(cnt, order[at[hit]], 1)
+        return cnt
+
+    def set_negative_sampling(self, alpha: float = 0.0, weights=None) -> None:
+        """Popularity-weighted negatives (not in the reference, which draws uniformly): negatives are drawn from the
+        catalogue with probability proportional to `weights` (one per catalogue position, finite, >= 0, positive sum;
+        a weight of zero is never drawn), by default (count_j + 1)^alpha with count_j = catalog_counts().  The + 1 is a
+        choice: it keeps items nobody liked drawable.  alpha = 0.75 is word2vec's customary value, not a measured
+        optimum.  The weights become a Walker alias table (negative_sampling.alias_table, probabilities quantised to
+        2^-32) that is uploaded on first use.  alpha == 0 with no weights clears the table: uniform draws, as before."""
+        if weights is None:
+            alpha = float(alpha)
+            if not np.isfinite(alpha):
+                raise ValueError(f"set_negative_sampling: alpha must be finite, got {alpha!r}")
+            w = None if alpha == 0.0 else popularity_weights(self.catalog_counts(), alpha)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != self.all_items_array.shape:
+                raise ValueError(f"set_negative_sampling: weights must have one entry per catalogue item "
+                                 f"({self.all_items_array.shape[0]}), got shape {w.shape}")
+        self._alias_host = None if w is None else alias_table(w)    # raises ValueError on bad weights
+        self._neg_weights = w
+        self._alias_dev = None
+
+    def _alias_ptrs(self):
+        if self._alias_host is None:
+            return None, None
+        if self._alias_dev is None:
+            dev = L.device()
+            prob, alias = self._alias_host
+            # (torch has no uint32 arithmetic: the words travel as int32 bit patterns)
+            self._alias_dev = (torch.from_numpy(prob.view(np.int32).copy()).to(dev), torch.from_numpy(alias.copy()).to(dev))
+        return self._alias_dev[0].data_ptr(), self._alias_dev[1].data_ptr()
+
+    def sample_negatives(self, users: torch.Tensor, gen: torch.Generator, max_attempts: int = 1000,
+                         n_negatives: int = 1) -> torch.Tensor:
         """One HIP launch for the whole batch (rihip_sample_negatives): uniform catalogue draws, re-drawn while the
         item is in the user's rated set -- the reference's rejection loop (:58-63), bounded at `max_attempts`.  A sample
-        that exhausts them keeps its last draw, a RATED item, and is counted on the device (negatives_given_up)."""
+        that exhausts them keeps its last draw, a RATED item, and is counted on the device (negatives_given_up).
+        n_negatives = K > 1 or a table set by set_negative_sampling (rihip_sample_negatives_multi): [K n] negatives,
+        k-major (negative k of sample i at k n + i), the K draws of a sample independent (with replacement)."""
+        if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or int(n_negatives) < 1:
+            raise ValueError(f"sample_negatives: n_negatives must be an integer >= 1, got {n_negatives!r}")
+        K = int(n_negatives)
         self._prepare_device()
         u = users.contiguous()
-        neg = torch.empty_like(u)
         self._neg_calls = getattr(self, "_neg_calls", 0) + 1     # host-side counter: no device sync for the seed
         seed = (gen.initial_seed() * 0x9E3779B97F4A7C15 + self._neg_calls) & ((1 << 63) - 1)
+        prob, alias = self._alias_ptrs()
+        if K > 1 or prob is not None:
+            neg = torch.empty((K * u.numel(),), dtype=u.dtype, device=u.device)
+            L.check(L.lib().rihip_sample_negatives_multi(u.data_ptr(), u.numel(), K, self.d_catalog.data_ptr(),
+                                                         self.d_catalog.numel(), prob, alias, self.d_rated.data_ptr(),
+                                                         self.d_rated.numel(), self.M, seed, max_attempts,
+                                                         neg.data_ptr(), self.d_gave_up.data_ptr(), L.stream_ptr()),
+                    "sample_negatives_multi")
+            return neg
+        neg = torch.empty_like(u)
         L.check(L.lib().rihip_sample_negatives(u.data_ptr(), u.numel(), self.d_catalog.data_ptr(),
                                                self.d_catalog.numel(), self.d_rated.data_ptr(), self.d_rated.numel(),
                                                self.M, seed, max_attempts, neg.data_ptr(), self.d_gave_up.data_ptr(),
@@ -147,10 +212,13 @@ class UserItemDataset:
             self.d_gave_up.zero_()
         return n
 
-    def epoch_batches(self, batch_size: int, gen: torch.Generator, with_negatives: bool = True
+    def epoch_batches(self, batch_size: int, gen: torch.Generator, with_negatives: bool = True, n_negatives: int = 1
                       ) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """Shuffled, drop_last batches (DataLoader(shuffle=True, drop_last=True), :144-151) as device
-        tensors: (user_ids [B], item_ids [2B]=pos||neg or [B], item_genres)."""
+        tensors: (user_ids [B], item_ids [2B]=pos||neg or [B], item_genres).  n_negatives = K: item_ids
+        [(1+K)B] = pos || neg_0 || ... || neg_(K-1), the layout HipBPRTrainer(n_negatives=K).step takes."""
+        if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or int(n_negatives) < 1:
+            raise ValueError(f"epoch_batches: n_negatives must be an integer >= 1, got {n_negatives!r}")
         self._prepare_device()
         n = len(self)
         perm = torch.randperm(n, device=self.d_pos_u.device, generator=gen)
@@ -158,7 +226,7 @@ class UserItemDataset:
             idx = perm[s:s + batch_size]
             u, p = self.d_pos_u[idx], self.d_pos_i[idx]
             if with_negatives:
-                items = torch.cat([p, self.sample_negatives(u, gen)])
+                items = torch.cat([p, self.sample_negatives(u, gen, n_negatives=int(n_negatives))])
             else:
                 items = p
             yield u, items, self.d_genres[items]
@@ -185,7 +253,8 @@ class EmbeddingTrainer:
                  embed_dim: int = 64, epochs: int = 10, batch_size: int = 1024, learning_rate: float = 1e-3,
                  device: Optional[str] = None, loss_mode: str = "sampled", table_opt: str = "dense",
                  dropout: float = 0.1, seed: int = 0, temperature: float = 0.05, logq_correction: bool = True,
-                 mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0, hard_weight: float = 0.1):
+                 mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0, hard_weight: float = 0.1,
+                 n_negatives: int = 1, negative_alpha: float = 0.0):
         """Defaults = the reference's settings (src/config.py:13,:24-26); `device` is accepted for
         signature compatibility -- training always runs on the HIP device.
         loss_mode="softmax" (not in the reference): in-batch sampled softmax with `temperature` (0.05 is a customary
@@ -195,7 +264,18 @@ class EmbeddingTrainer:
         (ranks hard_skip .. hard_skip + n_hard - 1); 8 is a customary starting value, not a measured optimum.
         loss_mode="mixed" (not in the reference): in-batch BPR plus `hard_weight` times that hard-negative term, mined
         from the stored in-batch weights; 0.1 is a starting value, not a measured optimum (it collapsed in
-        the one short run made, 0.01 did not)."""
+        the one short run made, 0.01 did not).
+        n_negatives, negative_alpha (loss_mode="sampled" only; not in the reference): K sampled negatives per positive,
+        drawn with probability proportional to (count + 1)^negative_alpha (UserItemDataset.set_negative_sampling);
+        the defaults 1 and 0.0 are the reference's one uniform negative."""
+        if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or int(n_negatives) < 1:
+            raise ValueError(f"EmbeddingTrainer: n_negatives must be an integer >= 1, got {n_negatives!r}")
+        if not np.isfinite(float(negative_alpha)):
+            raise ValueError(f"EmbeddingTrainer: negative_alpha must be finite, got {negative_alpha!r}")
+        if loss_mode != "sampled" and (int(n_negatives) != 1 or float(negative_alpha) != 0.0):
+            raise ValueError(f"EmbeddingTrainer: n_negatives / negative_alpha need loss_mode='sampled' (the in-batch modes "
+                             f"take their negatives from the batch), got loss_mode={loss_mode!r}")
+        self.n_negatives, self.negative_alpha = int(n_negatives), float(negative_alpha)
         if loss_mode in ("hard", "mixed"):
             _check_hard_args(n_hard, hard_skip)
         self.n_hard, self.hard_skip, self.hard_weight = n_hard, hard_skip, hard_weight
@@ -218,6 +298,8 @@ class EmbeddingTrainer:
         all_item_ids = sorted(movies_df["item_id"].unique().tolist())
         item_genre_dict = build_item_genre_dict(movies_df)
         dataset = UserItemDataset(ratings_df, item_genre_dict, all_item_ids)
+        if self.negative_alpha != 0.0:
+            dataset.set_negative_sampling(alpha=self.negative_alpha)
         torch.manual_seed(self.seed)
         model = TwoTowerModel(n_users, n_items, embed_dim=self.embed_dim, hidden_dim=128, dropout=self.dropout)
         extra = {}
@@ -229,6 +311,8 @@ class EmbeddingTrainer:
         if self.loss_mode == "mixed":
             extra = dict(n_hard=self.n_hard, hard_skip=self.hard_skip, mask_duplicates=self.mask_duplicates,
                          hard_weight=self.hard_weight)
+        if self.n_negatives != 1:
+            extra = dict(n_negatives=self.n_negatives)
         trainer = HipBPRTrainer(model, self.batch_size, lr=self.learning_rate, weight_decay=1e-5, max_norm=1.0,
                                 loss_mode=self.loss_mode, table_opt=self.table_opt, seed=self.seed, **extra)
         gen = torch.Generator(device=self.device)
@@ -241,7 +325,8 @@ class EmbeddingTrainer:
             t0 = time.time()
             tot = torch.zeros((), dtype=torch.float64, device=self.device)
             nb = 0
-            for u, items, genres in dataset.epoch_batches(self.batch_size, gen, self.loss_mode == "sampled"):
+            for u, items, genres in dataset.epoch_batches(self.batch_size, gen, self.loss_mode == "sampled",
+                                                          n_negatives=self.n_negatives):
                 tot += trainer.step(u, items, genres, lr=lr).double()
                 nb += 1
             avg = float(tot.item()) / max(nb, 1)   # one host sync per epoch (the reference syncs every step, :194)

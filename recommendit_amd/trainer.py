@@ -14,6 +14,7 @@ Two loss modes: ``sampled`` (one explicit negative per positive -- what the refe
 with) and ``inbatch`` (TwoTowerModel.in_batch_bpr_loss, never called by the reference trainer).  ``softmax`` (not in the
 reference): the in-batch sampled softmax with temperature, logQ correction and duplicate masking.  ``hard`` (not in the
 reference): in-batch BPR against every row's n_hard highest-scoring other items (online hard-negative mining).
+``sampled`` with ``n_negatives=K`` (not in the reference): K explicit negatives per positive, the mean over the B K pairs.
 
 Multi-GPU (one process per GPU, torch.distributed/RCCL; opt-in with ``distributed=True``): user rows are sharded
 (each rank trains pairs whose user row it owns: zero communication for user rows).  The item table is either
@@ -118,7 +119,7 @@ class HipBPRTrainer:
                  distributed: bool = False, item_shard: str = "replicate", exchange_cap: Optional[int] = None,
                  persistent: Optional[bool] = None, temperature: float = 0.05,
                  item_logq: Optional[torch.Tensor] = None, mask_duplicates: bool = True, n_hard: int = 8,
-                 hard_skip: int = 0, hard_weight: float = 0.1):
+                 hard_skip: int = 0, hard_weight: float = 0.1, n_negatives: int = 1):
         """distributed=True (or a process_group): this trainer is one rank of a collective job -- EVERY rank of the
         group must construct it and call step() in lock-step.  Default False even when torch.distributed is
         initialised, so that a single-rank trainer inside a distributed program never issues collectives.
@@ -150,7 +151,11 @@ class HipBPRTrainer:
         trained like "inbatch"); 0 reproduces "inbatch" bit for bit.  Needs the stored-G form
         (embed_dim 32 / 64 / 128, inbatch_precision 0 or 2, inbatch_store_g not False, memory for the B x B weights:
         half of the free device memory when inbatch_store_g is None, all of it when True; ValueError otherwise);
-        single GPU for now."""
+        single GPU for now.
+        n_negatives (loss_mode="sampled" only; not in the reference, which trains one negative per positive): K explicit
+        negatives per positive through rihip_bpr_multi_loss, the mean over the B K pairs.  step() then takes
+        (1 + K) B item ids, pos || neg_0 || ... || neg_(K-1).  1 keeps the launches and the bits of rihip_bpr_pair_loss.
+        K > 1 is single-GPU for now and has no one-launch (persistent) form."""
         assert loss_mode in ("sampled", "inbatch", "softmax", "hard", "mixed") and table_opt in ("dense", "sparse")
         if loss_mode == "mixed":
             _check_hard_args(n_hard, hard_skip)
@@ -178,6 +183,20 @@ class HipBPRTrainer:
             if distributed or process_group is not None:
                 raise ValueError("HipBPRTrainer: loss_mode='softmax' is single-GPU for now (the rectangular "
                                  "rihip_inbatch_softmax_* entries are ready; the multi-GPU trainer wiring is not)")
+        if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or int(n_negatives) < 1:
+            raise ValueError(f"HipBPRTrainer: n_negatives must be an integer >= 1, got {n_negatives!r}")
+        n_negatives = int(n_negatives)
+        if n_negatives != 1:
+            if loss_mode != "sampled":
+                raise ValueError(f"HipBPRTrainer: n_negatives={n_negatives} needs loss_mode='sampled' (the in-batch modes "
+                                 f"take their negatives from the batch), got loss_mode={loss_mode!r}")
+            if distributed or process_group is not None:
+                raise ValueError("HipBPRTrainer: n_negatives > 1 is single-GPU for now (rihip_bpr_multi_loss is ready; "
+                                 "the multi-GPU trainer wiring is not)")
+            if persistent:
+                raise ValueError("HipBPRTrainer: persistent=True needs n_negatives=1 (the one-launch step's contract is "
+                                 "item.B = 2 * user.B)")
+        self.n_negatives = n_negatives
         assert item_shard in ("replicate", "rows")
         self.lib = L.lib()
         self.model = model
@@ -231,7 +250,7 @@ class HipBPRTrainer:
             self.gv[k] = self.flat_g[o:o + s].view_as(prm)
         self.utab = model.user_tower.embedding.weight.data
         self.itab = model.item_tower.embedding.weight.data
-        nI = self.B * (2 if loss_mode == "sampled" else 1)
+        nI = self.B * (1 + n_negatives if loss_mode == "sampled" else 1)
         self.nI = nI
         # replicated item table: applies every rank's rows; row-sharded: up to every rank's requests can hit one owner
         cap = self.exchange_cap = (int(exchange_cap) if exchange_cap else nI) if self.item_rows else 0
@@ -253,7 +272,7 @@ class HipBPRTrainer:
             self._mt_m = PA(*[x[2].data_ptr() for x in ts]); self._mt_v = PA(*[x[3].data_ptr() for x in ts])
             self._mt_n = NA(*[x[0].numel() for x in ts])
 
-        can_persist = (loss_mode == "sampled" and table_opt == "dense" and not self.dist
+        can_persist = (loss_mode == "sampled" and n_negatives == 1 and table_opt == "dense" and not self.dist
                        and bool(self.lib.rihip_bpr_step_persistent_supported(self.B, d, H)))
         if persistent and not can_persist:
             raise ValueError("persistent=True needs loss_mode='sampled', table_opt='dense', one GPU and B <= 2048")
@@ -433,12 +452,16 @@ class HipBPRTrainer:
     def step(self, user_ids: torch.Tensor, item_ids: torch.Tensor, item_genres: torch.Tensor,
              lr: Optional[float] = None) -> torch.Tensor:
         """One optimisation step.  user_ids int64 [B] (LOCAL row ids when tables are sharded);
-        sampled mode: item_ids [2B] = pos || neg, item_genres [2B,18]; inbatch: [B] / [B,18].
+        sampled mode: item_ids [2B] = pos || neg, item_genres [2B,18] (n_negatives = K: [(1+K)B] = pos || neg_0 || ... ||
+        neg_(K-1), any other length is a ValueError); inbatch: [B] / [B,18].
         Returns the loss as a 0-dim device tensor (no host sync).
 
         use_graph=True (single GPU): the second call captures the whole step (~45 launches) into a hipGraph;
         later calls copy the ids into static buffers and replay it.  The Adam step clock and the dropout seed
         offset live in device memory (rihip_adam_hyper_step), so replays advance them."""
+        if self.n_negatives != 1 and item_ids.numel() != self.nI:
+            raise ValueError(f"HipBPRTrainer.step: n_negatives={self.n_negatives} takes {self.nI} item ids "
+                             f"((1 + n_negatives) * batch_size, pos || neg_0 || ...), got {item_ids.numel()}")
         assert user_ids.numel() == self.B and item_ids.numel() == self.I.shape[0]
         lr = self.lr if lr is None else float(lr)
         if lr != self._lr_host:
@@ -565,7 +588,14 @@ class HipBPRTrainer:
                     self._I_work = all_gather_into(self.I_all, self.I, self.pg, async_op=True)
                 self._fwd(self.utab, user_ids, None, ukeys, self.U, self.hidU, self.denU, s0)
 
-        if self.loss_mode == "sampled":
+        if self.loss_mode == "sampled" and self.n_negatives > 1:
+            # K negatives per positive (single GPU): I = pos || neg_0 || ... is the k-major layout of the entry
+            K = self.n_negatives
+            L.check(lib.rihip_bpr_multi_loss(self.U.data_ptr(), self.I.data_ptr(), self.I[B:].data_ptr(), B, K, d, None,
+                                             self.dU.data_ptr(), self.dI.data_ptr(), self.dI[B:].data_ptr(),
+                                             self.lpart.data_ptr(), st), "bpr_multi_loss")
+            self._loss_fold = (self.lpart.data_ptr(), lib.rihip_bpr_multi_nparts(B, K), 1.0 / (B * K))
+        elif self.loss_mode == "sampled":
             # single GPU: the loss partials are summed by the clip-coefficient launch (one dependent launch less)
             L.check(lib.rihip_bpr_pair_loss(self.U.data_ptr(), self.I.data_ptr(), self.I[B:].data_ptr(), B, d,
                                             self.loss.data_ptr() if self.dist else None, self.dU.data_ptr(),
