@@ -742,6 +742,51 @@ int rihip_eval_reduce(int64_t n, int n_k, const double* vals, const double* rr, 
                       const uint8_t* scored, const uint8_t* flags, int64_t n_id_space, int64_t catalog_size,
                       const int* err, double* partials, int64_t* cov_partials, double* out, void* stream);
 
+/* ---- validation by exact full-catalogue ranks ---------------------------------------------------
+ * Not in the reference, which evaluates once, after training, from top-k lists.  For held-out (user, item) pairs: the
+ * position each item would have in its user's exact list over the whole catalogue, without building a list.
+ * U f32 [n_users, d], Y f32 [n_items, d]: tower outputs, any finite values (nothing relies on unit rows).  Pairs as a
+ * CSR by user: pair_offsets i64 [n_users + 1] into pair_item i32 [n_pairs] = the target ROW of Y; a user may have no
+ * pairs.  Optional exclusion CSR by the same user index: excl_offsets i64 [n_users + 1] (NULL: nothing excluded) into
+ * excl_items i32 [n_excl], rows of Y, ascending and unique inside a row (the convention of rihip_exclude_topk).
+ * For pair p = (u, t):
+ *   s_uj = the f32 score of user u against item j from the owner sweep's product code (exact-f32 MFMA, fixed k order,
+ *          s + 0.f: -0 and +0 are one score).  Every score that enters a comparison -- the target's, the swept ones,
+ *          the excluded items' -- comes from that code, whose result for an element depends only on its two rows: a
+ *          row compared with a bytewise equal row ties exactly.
+ *   item j OUTRANKS t iff s_uj > s_ut, or s_uj == s_ut and j < t (score descending, row ascending: the tie rule of the
+ *          exact index search)
+ *   rank[p] = #{ j in [0, n_items) : j != t, j not in excl(u), j outranks t }: the 0-based position of t in u's exact
+ *          top-n_items list with excl(u) removed.  An exclusion entry equal to t is ignored; other targets of the same
+ *          user are ordinary competitors.
+ *   target_score[p] = s_ut.
+ * err (device int, zeroed here, OR-ed): bit 0 = an exclusion entry outside [0, n_items): ignored, never used as an
+ * address; bit 1 = a target outside [0, n_items): rank[p] = -1, target_score[p] = 0.  Non-finite scores give
+ * unspecified ranks inside [-1, n_items).
+ * grid_splits: workgroups the item range is divided over, by whole 128-row tiles (0 = the library's choice, which fills
+ * the chip at small n_pairs).  Counts are integers added with integer atomics: the result does not depend on the
+ * split, and two calls agree bit for bit.
+ * Limits: n_items < 2^31, n_pairs < 2^31, d a multiple of 16 up to 256.  workspace: device memory of
+ * rihip_rank_targets_workspace_bytes(n_pairs, n_excl, d) bytes (-1 for sizes out of range), bounded in n_excl * d.
+ * Argument errors return RIHIP_ERR_ARG with a reason and launch nothing; n_pairs == 0 zeroes err and launches nothing.
+ * No host synchronisation, no allocation; capturable in a hipGraph. */
+int64_t rihip_rank_targets_workspace_bytes(int64_t n_pairs, int64_t n_excl, int d);
+int rihip_rank_targets(const float* U, int64_t n_users, const float* Y, int64_t n_items, int d,
+                       const int64_t* pair_offsets, const int32_t* pair_item, int64_t n_pairs,
+                       const int64_t* excl_offsets, const int32_t* excl_items, int64_t n_excl, int grid_splits,
+                       int32_t* rank, float* target_score, int* err, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+/* Ranks -> the per-user outputs of rihip_eval_topk: vals f64 [n_users, n_k, 3] (ndcg, recall, precision), rr f64
+ * [n_users], scored u8 [n_users], from rank i32 [n_pairs] and the pairs' CSR.  Same k_values (HOST array, 1..64
+ * values), disc / idcg tables (n_tab > max k) and per-k formulas; user u's hits are its pairs with 0 <= rank < k, its
+ * DCG the sum of disc[rank] in ascending rank order (what the list kernel adds walking its row), recall = hits / its
+ * pairs, rr = 1 / (1 + its smallest rank >= 0) over the whole catalogue.  gt_raw i64 [n_users] as in rihip_eval_topk
+ * (NULL: the user's number of pairs).  rank -1 is a miss; a user without pairs or with gt_raw <= 0 is not scored.
+ * rihip_eval_reduce then produces the means unchanged. */
+int rihip_eval_ranks(const int32_t* rank, const int64_t* pair_offsets, int64_t n_users, int64_t n_pairs,
+                     const int64_t* gt_raw, const int* k_values, int n_k, const double* disc, const double* idcg,
+                     int n_tab, double* vals, double* rr, uint8_t* scored, void* stream);
+
 /* ---- training-serving skew ------------------------------------------------------------------
  * Replaces the per-column loop of detect_training_serving_skew and the histograms of kl_divergence_bins
  * (src/evaluation/metrics.py:197-294) for two row-major device samples A [na, lda] and B [nb, ldb] (f32, or f64 when

@@ -9,7 +9,8 @@ from .ranker import LightGBMRanker  # noqa: F401
 from .seen import SeenItems  # noqa: F401  (not in the reference: per-user exclusion of seen items, seen.py)
 from .coldstart import UserHistories  # noqa: F401  (not in the reference: cold-start users from rating histories, coldstart.py)
 from .rerank import mmr_rerank_device  # noqa: F401  (not in the reference: diversified top-k, rerank.py)
+from .validation import RankValidator  # noqa: F401  (not in the reference: validation while training, validation.py)
 from ._lib import have_gpu  # noqa: F401  (the switch a caller guards the swap with: INTEGRATION.md §1)
 
-__all__ = ["TwoTowerModel", "UserTower", "ItemTower", "FAISSIndex", "LightGBMRanker", "SeenItems", "UserHistories", "mmr_rerank_device", "N_GENRES",
+__all__ = ["TwoTowerModel", "UserTower", "ItemTower", "FAISSIndex", "LightGBMRanker", "SeenItems", "UserHistories", "mmr_rerank_device", "RankValidator", "N_GENRES",
            "have_gpu"]

@@ -171,6 +171,10 @@ SIGNATURES = {
                                   vp, vp]),
     "rihip_eval_diversity": (C.c_int, [vp, c_i64, C.c_int, vp, C.c_int, vp, c_i64, C.c_int, vp, vp, vp]),
     "rihip_eval_reduce": (C.c_int, [c_i64, C.c_int, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp, vp, vp, vp]),
+    "rihip_rank_targets_workspace_bytes": (c_i64, [c_i64, c_i64, C.c_int]),
+    "rihip_rank_targets": (C.c_int, [vp, c_i64, vp, c_i64, C.c_int, vp, vp, c_i64, vp, vp, c_i64, C.c_int, vp, vp, vp, vp,
+                                     c_i64, vp]),
+    "rihip_eval_ranks": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "rihip_skew_workspace_bytes": (c_i64, [C.c_int]),
     "rihip_skew_compute": (C.c_int, [vp, C.c_int, c_i64, c_i64, vp, vp, vp, C.c_int, c_i64, c_i64, vp, vp, C.c_int,
                                      C.c_int, C.c_double, c_i64, C.c_int, vp, c_i64, vp, vp, vp, vp, vp, vp]),

@@ -254,7 +254,8 @@ class EmbeddingTrainer:
                  device: Optional[str] = None, loss_mode: str = "sampled", table_opt: str = "dense",
                  dropout: float = 0.1, seed: int = 0, temperature: float = 0.05, logq_correction: bool = True,
                  mask_duplicates: bool = True, n_hard: int = 8, hard_skip: int = 0, hard_weight: float = 0.1,
-                 n_negatives: int = 1, negative_alpha: float = 0.0):
+                 n_negatives: int = 1, negative_alpha: float = 0.0, validation=None, val_k=(10, 50), val_every: int = 1,
+                 select_by: Optional[str] = None, patience: Optional[int] = None):
         """Defaults = the reference's settings (src/config.py:13,:24-26); `device` is accepted for
         signature compatibility -- training always runs on the HIP device.
         loss_mode="softmax" (not in the reference): in-batch sampled softmax with `temperature` (0.05 is a customary
@@ -267,7 +268,33 @@ class EmbeddingTrainer:
         the one short run made, 0.01 did not).
         n_negatives, negative_alpha (loss_mode="sampled" only; not in the reference): K sampled negatives per positive,
         drawn with probability proportional to (count + 1)^negative_alpha (UserItemDataset.set_negative_sampling);
-        the defaults 1 and 0.0 are the reference's one uniform negative."""
+        the defaults 1 and 0.0 are the reference's one uniform negative.
+        validation (not in the reference; validation.py): None = the reference's flow, nothing constructed.  "last":
+        train() holds out every user's last rating >= 4 (validation.leave_last_out) and trains on the rest; or a ready
+        (GroundTruth, users, SeenItems) triple.  Every `val_every` epochs the history row gains val_recall@k,
+        val_ndcg@k, val_precision@k (k in `val_k`), val_mrr, val_median_rank and val_seconds: exact full-catalogue
+        ranks of the held-out items with the seen items removed, for every loss_mode (the validator only reads the
+        model).  select_by="recall@50" (any reported key) replaces "lowest training loss" as the checkpoint rule: the
+        model train() returns and saves is the one of the best validation, ties to the earlier epoch.  patience=n
+        stops after n validations without improvement of `select_by`."""
+        if validation is None and (select_by is not None or patience is not None):
+            raise ValueError("EmbeddingTrainer: select_by / patience need validation")
+        if validation is not None:
+            from .validation import report_keys, select_epoch
+            if not (isinstance(validation, str) and validation == "last") and not (
+                    isinstance(validation, (tuple, list)) and len(validation) == 3):
+                raise ValueError(f"EmbeddingTrainer: validation must be None, 'last' or a (GroundTruth, users, SeenItems) "
+                                 f"triple, got {validation!r}")
+            if isinstance(val_every, bool) or int(val_every) != val_every or int(val_every) < 1:
+                raise ValueError(f"EmbeddingTrainer: val_every must be an integer >= 1, got {val_every!r}")
+            if select_by is not None and select_by not in report_keys(val_k):
+                raise ValueError(f"EmbeddingTrainer: select_by={select_by!r} is not reported; one of {report_keys(val_k)}")
+            if patience is not None:
+                if select_by is None:
+                    raise ValueError("EmbeddingTrainer: patience needs select_by (the value that has to improve)")
+                select_epoch([], "max", patience)   # validates the value
+        self.validation, self.val_k, self.val_every = validation, tuple(int(k) for k in val_k), int(val_every)
+        self.select_by, self.patience = select_by, patience
         if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or int(n_negatives) < 1:
             raise ValueError(f"EmbeddingTrainer: n_negatives must be an integer >= 1, got {n_negatives!r}")
         if not np.isfinite(float(negative_alpha)):
@@ -297,6 +324,14 @@ class EmbeddingTrainer:
         n_items = int(ratings_df["item_id"].max())
         all_item_ids = sorted(movies_df["item_id"].unique().tolist())
         item_genre_dict = build_item_genre_dict(movies_df)
+        held_out = None
+        if self.validation is not None:
+            from . import validation as V
+            if isinstance(self.validation, str):
+                ratings_df, truth, val_users, seen = V.leave_last_out(ratings_df)
+                held_out = (truth, val_users, seen)
+            else:
+                held_out = tuple(self.validation)
         dataset = UserItemDataset(ratings_df, item_genre_dict, all_item_ids)
         if self.negative_alpha != 0.0:
             dataset.set_negative_sampling(alpha=self.negative_alpha)
@@ -319,6 +354,12 @@ class EmbeddingTrainer:
         gen.manual_seed(self.seed)
         Path(self.model_output_path).parent.mkdir(parents=True, exist_ok=True)
         best = float("inf")
+        validator, val_values, best_state = None, [], None
+        if held_out is not None:
+            genre_rows = np.stack([item_genre_dict.get(i, np.zeros(N_GENRES, np.float32)) for i in all_item_ids])
+            validator = V.RankValidator(model, all_item_ids, genre_rows, held_out[0], held_out[1], held_out[2],
+                                        k_values=self.val_k)
+            val_mode = "min" if self.select_by in V.LOWER_IS_BETTER else "max"
         for epoch in range(1, self.epochs + 1):
             model.train()
             lr = cosine_lr(self.learning_rate, epoch - 1, self.epochs)
@@ -333,9 +374,31 @@ class EmbeddingTrainer:
             dt = time.time() - t0
             self.history.append({"epoch": epoch, "loss": avg, "seconds": dt, "pairs_per_sec": nb * self.batch_size / dt})
             logger.info("Epoch %d/%d - loss %.4f - %.1fs - lr %.6f", epoch, self.epochs, avg, dt, lr)
-            if avg < best:
+            stop = None
+            if validator is not None and epoch % self.val_every == 0:
+                t0 = time.time()
+                rep = validator.evaluate()     # one host read
+                row = self.history[-1]
+                row.update({f"val_{k}": v for k, v in rep.items() if k in V.report_keys(self.val_k)})
+                row["val_seconds"] = time.time() - t0
+                logger.info("Epoch %d/%d - validation %s", epoch, self.epochs,
+                            {k: round(v, 4) for k, v in row.items() if k.startswith("val_")})
+                if self.select_by is not None:
+                    val_values.append(rep[self.select_by])
+                    best_val, stop = V.select_epoch(val_values, val_mode, self.patience)
+                    if best_val == len(val_values) - 1:
+                        row["val_best"] = True
+                        best_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+                        model.save(self.model_output_path)
+            if self.select_by is None and avg < best:
                 best = avg
                 model.save(self.model_output_path)
+            if stop is not None:
+                logger.info("Early stop after epoch %d: %d validations without a better %s", epoch, self.patience,
+                            self.select_by)
+                break
+        if best_state is not None:
+            model.load_state_dict(best_state)
         genre_matrix = np.stack([item_genre_dict.get(i, np.zeros(N_GENRES, np.float32)) for i in all_item_ids])
         model.precompute_item_embeddings(all_item_ids, genre_matrix, self.device)
         model.save(self.model_output_path)
