@@ -578,6 +578,44 @@ int rihip_ip_index_search_filtered(void* handle, const float* Q, int64_t nq, int
                                    int64_t pred_stride, float* out_scores, int64_t* out_rows, void* stream);
 int rihip_ip_index_filtered_stats(void* handle, int64_t* out);
 
+/* ---- 8-bit scalar-quantised index (faiss IndexScalarQuantizer / IndexIVFScalarQuantizer at 8 bits; the reference's
+ * FAISSIndex has none) ----------------------------------------------------------------------
+ * A second handle type, built from the f32 rows of a built ip_index (which may be destroyed afterwards): one int8 code
+ * per dimension, rows of 64 or 128 bytes, in the source's physical order (IVF: its lists and centroids; flat: one list).
+ * Quantiser, per dimension j over all rows, in f32:  m_j = 0.5f * (lo_j + hi_j),  s_j = (hi_j - lo_j) / 254.0f  (1 where
+ * hi_j == lo_j),  c_ij = clamp(rintf((x_ij - m_j) / s_j), -127, 127)  (one subtraction, one correctly rounded division),
+ * decoded x^_ij = m_j + s_j * c_ij.  from_ip_index: centre / scale host f32 [d] inject (m, s) instead (both or neither;
+ * scale > 0).  This is not faiss's QT_8bit (codes 0..255 over [lo, hi]); faiss SQ files are not read or written.
+ * Query side (asymmetric, 16 bits):  w_j = q_j * s_j,  A = max_j |w_j|,  t = A / 32512.0f  (t = 0, n = 0 when A == 0),
+ * n_j = clamp(rintf(w_j / t), -32512, 32512).  Integer score S_i = sum_j n_j * c_ij  (|S| < 2^31); ranking is by S, ties
+ * to the lower row; reported score (float)(b + (double)t * S) with b = sum_j (double)q_j * (double)m_j in ascending j.
+ * encode_queries: the search's first stage exposed -- device outputs n int16 [nq,d], t f32 [nq], b f64 [nq].
+ * search: Q device f32 [nq,d]; outputs device scores f32 [nq,k] (-inf pad), rows i64 [nq,k] (-1 pad; set_id_map as for
+ * ip_index), out_iscores i32 [nq,k] or NULL (INT32_MIN pad).  mode 0 = auto, 1 = dense slots per (query, probed list)
+ * and the two-level select, queries chunked to a fixed scratch budget (auto takes it for small batches and small probed
+ * populations), 2 = sampled threshold, survivors S >= threshold,
+ * exact completeness check (integers: no epsilon), failed queries re-done dense; every mode returns the same bytes.
+ * The thresholded pass synchronises the stream.  k <= rihip_ip_index_max_k().
+ * get_codes: host int8 [N,d], reconstruct: host f32 [N,d], both in original row order; get_quantizer: host f32 [d] each.
+ * stats: out[0] = queries searched thresholded, out[1] = of those re-done, out[2] = device bytes the index holds.
+ * save / load: own format ("RIHIPSQ8", version word; header fields are range-checked on load). */
+int rihip_sq8_index_from_ip_index(void* ip_handle, const float* centre, const float* scale, void** handle, void* stream);
+int rihip_sq8_index_destroy(void* handle);
+int64_t rihip_sq8_index_ntotal(void* handle);
+int rihip_sq8_index_nlist(void* handle);
+int rihip_sq8_index_set_nprobe(void* handle, int nprobe);
+int rihip_sq8_index_set_id_map(void* handle, const int64_t* item_ids_dev);
+int rihip_sq8_index_get_quantizer(void* handle, float* centre, float* scale);   /* synchronous */
+int rihip_sq8_index_get_codes(void* handle, int8_t* out);                        /* synchronous */
+int rihip_sq8_index_reconstruct(void* handle, float* out);                       /* synchronous */
+int rihip_sq8_index_encode_queries(void* handle, const float* Q, int64_t nq, int16_t* out_n, float* out_t, double* out_b,
+                                   void* stream);
+int rihip_sq8_index_search(void* handle, const float* Q, int64_t nq, int k, int mode, float* out_scores, int64_t* out_rows,
+                           int32_t* out_iscores, void* stream);
+int rihip_sq8_index_stats(void* handle, int64_t* out);
+int rihip_sq8_index_save(void* handle, const char* path);          /* host path; synchronous */
+int rihip_sq8_index_load(const char* path, void** handle);         /* host path; synchronous */
+
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict
  * (ranker.py:174): raw score = sum over trees of the reached leaf value, float64.

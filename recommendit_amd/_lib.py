@@ -137,6 +137,20 @@ SIGNATURES = {
     "rihip_ip_index_has_tags": (C.c_int, [vp]),
     "rihip_ip_index_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, vp, c_i64, vp, vp, vp]),
     "rihip_ip_index_filtered_stats": (C.c_int, [vp, vp]),
+    "rihip_sq8_index_from_ip_index": (C.c_int, [vp, vp, vp, C.POINTER(vp), vp]),
+    "rihip_sq8_index_destroy": (C.c_int, [vp]),
+    "rihip_sq8_index_ntotal": (c_i64, [vp]),
+    "rihip_sq8_index_nlist": (C.c_int, [vp]),
+    "rihip_sq8_index_set_nprobe": (C.c_int, [vp, C.c_int]),
+    "rihip_sq8_index_set_id_map": (C.c_int, [vp, vp]),
+    "rihip_sq8_index_get_quantizer": (C.c_int, [vp, vp, vp]),
+    "rihip_sq8_index_get_codes": (C.c_int, [vp, vp]),
+    "rihip_sq8_index_reconstruct": (C.c_int, [vp, vp]),
+    "rihip_sq8_index_encode_queries": (C.c_int, [vp, vp, c_i64, vp, vp, vp, vp]),
+    "rihip_sq8_index_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "rihip_sq8_index_stats": (C.c_int, [vp, vp]),
+    "rihip_sq8_index_save": (C.c_int, [vp, C.c_char_p]),
+    "rihip_sq8_index_load": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

@@ -1,0 +1,809 @@
+// 8-bit scalar-quantised inner-product index (flat and IVF): the handle, its kernels and its C ABI.
+//
+// A second handle type next to IpIndex.  It is built from the f32 rows of a built IpIndex, in that index's physical order
+// (lists padded to 64-row granules; a flat source becomes one list), and stores one int8 code per dimension:
+//   m_j = 0.5f (lo_j + hi_j), s_j = (hi_j - lo_j) / 254.0f (1 where hi_j == lo_j), c_ij = clamp(rint((x_ij - m_j) / s_j), +-127)
+// The query side keeps 16 bits: w_j = q_j s_j, t = max|w| / 32512, n_j = rint(w_j / t) split into two int8 limbs
+// n = 256 hi + lo.  The scan scores S_i = sum_j n_j c_ij on the i8 MFMA (two chains into two i32 accumulators,
+// S = 256 S_hi + S_lo, |S| <= 32512 * 127 * 128 < 2^31): integers, so ranking, ties and the completeness check of the
+// thresholded pass are exact.  The reported score is (float)(b + t S) with b = sum_j q_j m_j in f64.
+//
+// The search reuses what does not depend on the corpus representation: the coarse quantizer, probe selection, work plan
+// and scatter of ivf_search.hip and finalize_kernel of select.hip.  Candidate keys are make_key's with the integer score
+// in the high word ((uint32)S ^ 0x80000000: unsigned order = signed order; never 0, the empty-slot key).  finalize emits a
+// key's high word through ord2f, a bijection of the 32 bits, so sq8_decode_kernel recovers S from the float it wrote.
+#pragma clang fp contract(off)   // the quantiser is specified operation by operation: no fused multiply-add
+#include "common.h"
+#include "recommendit_hip.h"
+
+#include <algorithm>
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+#include "search_kernels.h"
+#include "search_keys.h"
+
+using namespace rihip_index;
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr float SQ8_QMAX = 32512.0f;            // largest |n_j|: 127 * 256, so both limbs fit int8
+constexpr int64_t SQ8_DENSE_BUDGET = 1ll << 26;  // dense candidate slots (8 B each) of one query chunk: 512 MiB
+constexpr int64_t SQ8_DENSE_AUTO = 1ll << 23;    // auto: dense while the batch's slots stay under 64 MiB (the f32 index's rule;
+                                                 // at 256 queries x IVF 100/10 of 1 M rows dense measured 0.46 ms, thresholded 0.23)
+constexpr int SQ8_TARGET = 16 * RIHIP_NCU;      // wave work items aimed at (as the f32 list-major scan)
+constexpr int SQ8_SS = 16;                      // threshold sample: every 16th probed tile
+constexpr int64_t SQ8_CH = 4096;                // queries per internal pass at most
+
+struct Sq8Index {
+  int du = 0;        // caller's width (1 .. 128)
+  int dk = 0;        // width of the f32 side (centroids, coarse queries): 32 / 64 / 128, as the source index
+  int dpad = 0;      // bytes per code row: 64 / 128
+  int64_t N = 0, Np = 0;
+  int nlist = 0, nprobe = 1;
+  int8_t* codes = nullptr;        // [Np, dpad] physical order, padding rows and columns 0
+  float* centre = nullptr;        // [dpad] (columns >= du: 0)
+  float* scale = nullptr;         // [dpad] (columns >= du: 1)
+  float* C = nullptr;             // [nlist, dk]
+  int64_t* list_poff = nullptr;   // [nlist+1]
+  int* list_len_dev = nullptr;    // [nlist]
+  int64_t* row_ids = nullptr;     // [Np] original row, -1 = padding
+  std::vector<int64_t> list_len;
+  const int64_t* id_map = nullptr;   // not owned
+  int64_t stats[2] = {0, 0};         // queries searched thresholded, of those re-done dense
+  // scratch
+  DevBuf<int8_t> qhi, qlo, fhi, flo;
+  DevBuf<float> qt, qpad, fQ, coarse, thr;
+  DevBuf<double> qb;
+  DevBuf<uint64_t> cand, scand, fcand;
+  DevBuf<int> count, probe_list, list_q, list_cnt, list_qoff, list_cur, work_off, plan, fail_flags, fail_list, n_fail;
+  int* h_nfail = nullptr;   // pinned
+};
+
+int64_t held_bytes(const Sq8Index* h) {
+  return (int64_t)h->Np * h->dpad + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
+         4 * (int64_t)h->nlist + 8 * h->Np;
+}
+
+void free_sq8(Sq8Index* h) {
+  rihip_bump_generation();
+  hipFree(h->codes); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
+  hipFree(h->row_ids);
+  h->qhi.release(); h->qlo.release(); h->fhi.release(); h->flo.release(); h->qt.release(); h->qpad.release(); h->fQ.release();
+  h->coarse.release(); h->thr.release(); h->qb.release(); h->cand.release(); h->scand.release(); h->fcand.release();
+  h->count.release(); h->probe_list.release(); h->list_q.release(); h->list_cnt.release(); h->list_qoff.release();
+  h->list_cur.release(); h->work_off.release(); h->plan.release(); h->fail_flags.release(); h->fail_list.release();
+  h->n_fail.release();
+  if (h->h_nfail) hipHostFree(h->h_nfail);
+  delete h;
+}
+
+// ------------------------------------------------ quantiser ----------------------------------------------------------
+// column min / max of the real rows, fixed order: block b takes a contiguous row range, thread (rr, c) every rpp-th row of
+// column c, the rpp partial results of a column are combined in rr order, the blocks' results in block order (no atomics)
+__global__ __launch_bounds__(256) void sq8_colrange_part_kernel(const float* __restrict__ X, const int64_t* __restrict__ row_ids,
+                                                                int64_t n_rows, int dk, float* part) {
+  __shared__ float slo[256], shi[256];
+  const int tid = threadIdx.x, rpp = 256 / dk, rr = tid / dk, c = tid % dk;
+  const int64_t per = (n_rows + gridDim.x - 1) / gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * per, r1 = (r0 + per < n_rows) ? r0 + per : n_rows;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int64_t r = r0 + rr; r < r1; r += rpp) {
+    if (row_ids && row_ids[r] < 0) continue;
+    const float v = X[(size_t)r * dk + c];
+    lo = fminf(lo, v); hi = fmaxf(hi, v);
+  }
+  slo[tid] = lo; shi[tid] = hi;
+  __syncthreads();
+  if (rr == 0) {
+    for (int k = 1; k < rpp; ++k) { lo = fminf(lo, slo[k * dk + c]); hi = fmaxf(hi, shi[k * dk + c]); }
+    part[((size_t)blockIdx.x * 2 + 0) * dk + c] = lo;
+    part[((size_t)blockIdx.x * 2 + 1) * dk + c] = hi;
+  }
+}
+__global__ void sq8_colrange_final_kernel(const float* __restrict__ part, int nb, int dk, int dpad, float* centre, float* scale) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= dpad) return;
+  float m = 0.f, s = 1.f;
+  if (j < dk) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (int b = 0; b < nb; ++b) { lo = fminf(lo, part[((size_t)b * 2 + 0) * dk + j]); hi = fmaxf(hi, part[((size_t)b * 2 + 1) * dk + j]); }
+    if (lo <= hi) {
+      m = 0.5f * (lo + hi);
+      s = (hi == lo) ? 1.f : (hi - lo) / 254.0f;
+    }
+  }
+  centre[j] = m; scale[j] = s;
+}
+
+__device__ __forceinline__ int sq8_code(float x, float m, float s) {
+  float v = rintf((x - m) / s);            // one f32 subtraction, one correctly rounded f32 division, round to nearest even
+  v = fminf(fmaxf(v, -127.f), 127.f);
+  return (int)v;
+}
+// four codes per thread; rows beyond n_src, padding rows (row_ids < 0) and columns >= dk are 0
+__global__ void sq8_encode_kernel(const float* __restrict__ X, const int64_t* __restrict__ row_ids, int64_t n_src, int64_t Np,
+                                  int dk, int dpad, const float* __restrict__ centre, const float* __restrict__ scale,
+                                  int8_t* codes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per_row = dpad / 4;
+  if (i >= Np * per_row) return;
+  const int64_t r = i / per_row;
+  const int j = (int)(i % per_row) * 4;
+  uint32_t packed = 0;
+  if (r < n_src && j < dk && row_ids[r] >= 0) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(X + (size_t)r * dk + j);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) packed |= ((uint32_t)sq8_code(x[u], centre[j + u], scale[j + u]) & 0xFFu) << (8 * u);
+  }
+  *reinterpret_cast<uint32_t*>(codes + (size_t)r * dpad + j) = packed;
+}
+
+__global__ void sq8_identity_rows_kernel(int64_t* row_ids, int64_t N, int64_t Np) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Np) row_ids[i] = i < N ? i : -1;
+}
+
+// decoded rows in original row order: out[row, j] = m_j + s_j c (two roundings)
+__global__ void sq8_reconstruct_kernel(const int8_t* __restrict__ codes, const int64_t* __restrict__ row_ids, int64_t Np, int du,
+                                       int dpad, const float* __restrict__ centre, const float* __restrict__ scale, float* out,
+                                       int8_t* out_codes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Np * du) return;
+  const int64_t p = i / du;
+  const int j = (int)(i % du);
+  const int64_t row = row_ids[p];
+  if (row < 0) return;
+  const int8_t c = codes[(size_t)p * dpad + j];
+  if (out_codes) out_codes[(size_t)row * du + j] = c;
+  if (out) {
+    const float prod = scale[j] * (float)c;
+    out[(size_t)row * du + j] = centre[j] + prod;
+  }
+}
+
+// ------------------------------------------------ query transform ----------------------------------------------------
+// one workgroup of 128 threads per query: limb rows (zero beyond du), t, b, and optionally n as int16 [nq, du]
+__global__ __launch_bounds__(128) void sq8_query_kernel(const float* __restrict__ Q, int64_t nq, int du, int dpad,
+                                                        const float* __restrict__ centre, const float* __restrict__ scale,
+                                                        int8_t* qhi, int8_t* qlo, float* qt, double* qb, int16_t* n16) {
+  __shared__ float smax[2];
+  __shared__ double sprod[128];
+  const int64_t q = blockIdx.x;
+  const int j = threadIdx.x;
+  float w = 0.f;
+  double pm = 0.0;
+  if (j < du) {
+    const float x = Q[q * du + j];
+    w = x * scale[j];
+    pm = (double)x * (double)centre[j];   // exact in f64
+  }
+  sprod[j] = pm;
+  float a = fabsf(w);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+  if ((j & 63) == 0) smax[j >> 6] = a;
+  __syncthreads();
+  const float A = fmaxf(smax[0], smax[1]);
+  const float t = A / SQ8_QMAX;
+  int n = 0;
+  if (A != 0.f) {
+    float v = rintf(w / t);
+    v = fminf(fmaxf(v, -SQ8_QMAX), SQ8_QMAX);
+    n = (int)v;
+  }
+  const int hi = (n + 128) >> 8, lo = n - 256 * hi;
+  if (j < dpad) { qhi[q * dpad + j] = (int8_t)hi; qlo[q * dpad + j] = (int8_t)lo; }
+  if (n16 && j < du) n16[q * du + j] = (int16_t)n;
+  if (j == 0) {
+    double b = 0.0;
+    for (int i = 0; i < du; ++i) b += sprod[i];   // ascending j
+    qb[q] = b;
+    qt[q] = (A != 0.f) ? t : 0.f;
+  }
+}
+
+// ------------------------------------------------ list-major scan ----------------------------------------------------
+struct Sq8LmArgs {
+  const int8_t* codes;       // [Np, DP]
+  const int8_t* qhi;         // [nq, DP]
+  const int8_t* qlo;
+  const float* thr;          // [nq] threshold as finalize (mode 1) wrote it, or null: every probed row is a candidate
+  uint64_t* cand; int64_t cap; int* count;
+  const int64_t* row_ids; const int64_t* list_poff; const int* list_len;
+  const int* list_qoff; const int* list_q; const int* work_off; const int* plan;
+  int nlist, tile_step, nprobe, count_stride;
+  int64_t dense_cap;         // > 0: dense slots, cand = [nq*nprobe, dense_cap]
+  int dense_ids;             // dense slots carry the original row id instead of 0 (threshold sample)
+};
+
+__device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
+  return ((uint64_t)((uint32_t)S ^ 0x80000000u) << 32) | (uint64_t)(0xFFFFFFFFu - row);
+}
+__device__ __forceinline__ int sq8_score_of_word(uint32_t hw) { return (int)(hw ^ 0x80000000u); }
+
+// The work plan is ivf_scan_lm_kernel's: a wave takes (one list, 32 of the queries that probe it, a range of the list's
+// 32-row tiles).  The 32 queries' limb rows are the B operands and stay in registers; a code tile is loaded straight into
+// the A-operand registers (lane (r, h) holds bytes 32 ks + 16 h .. + 15 of row r for k-step ks -- the same bytes of its
+// query on the B side, so whatever order the instruction gives the 16 bytes of a lane, both operands agree on it), the
+// next tile's loads are in flight under the chain.  No LDS, no barrier, no float arithmetic.
+template <int DP>
+__global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
+  constexpr int KS = DP / 32;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r31 = lane & 31, hh = lane >> 5;
+  const int wi = blockIdx.x * 4 + w;
+  if (wi >= a.plan[0]) return;  // wave-uniform
+  int lo = 0, hi = a.nlist;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.work_off[mid] <= wi) lo = mid; else hi = mid;
+  }
+  const int c = lo;
+  const int rem = wi - a.work_off[c];
+  const int64_t p0 = a.list_poff[c];
+  const int64_t tiles = (a.list_poff[c + 1] - p0) / TRS;
+  const int tstep = a.tile_step > 1 ? a.tile_step : 1;
+  const int64_t n_seq = (tiles + tstep - 1) / tstep;
+  const int tpi = a.plan[1];
+  const int s_c = (int)((n_seq + tpi - 1) / tpi);
+  if (s_c <= 0) return;
+  const int grp = rem / s_c, split = rem % s_c;
+  const int q0 = a.list_qoff[c], m = a.list_qoff[c + 1] - q0;
+  if (grp * 32 >= m) return;
+  const int slot = grp * 32 + r31;
+  const bool q_ok = slot < m;
+  const int pair = a.list_q[q0 + (q_ok ? slot : grp * 32)];
+  const int64_t q = pair / a.nprobe;
+  const int len = a.list_len[c];
+  i32x4 bh[KS], bl[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    bh[ks] = *reinterpret_cast<const i32x4*>(a.qhi + (size_t)q * DP + ks * 32 + 16 * hh);
+    bl[ks] = *reinterpret_cast<const i32x4*>(a.qlo + (size_t)q * DP + ks * 32 + 16 * hh);
+  }
+  const int thr = a.thr ? sq8_score_of_word(f2ord(a.thr[q])) : (int)0x80000000;
+  uint64_t* my_cand = a.cand + (size_t)q * a.cap;
+  uint64_t* my_dense = a.dense_cap > 0 ? a.cand + (size_t)pair * a.dense_cap : nullptr;
+  const int64_t i0 = (int64_t)split * tpi;
+  const int64_t i1 = (i0 + tpi < n_seq) ? i0 + tpi : n_seq;
+  if (i0 >= i1) return;
+
+  i32x4 av[KS], nx[KS];
+  auto load_tile = [&](int64_t i, i32x4* dst) {
+    const i32x4* src = reinterpret_cast<const i32x4*>(a.codes + (size_t)(p0 + i * tstep * TRS + r31) * DP + 16 * hh);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) dst[ks] = src[ks * 2];
+  };
+  load_tile(i0, av);
+#pragma unroll 1
+  for (int64_t i = i0; i < i1; ++i) {
+    const bool more = i + 1 < i1;
+    if (more) load_tile(i + 1, nx);
+    i32x16 ah, al;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { ah[r] = 0; al[r] = 0; }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[ks], bh[ks], ah, 0, 0, 0);
+      al = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[ks], bl[ks], al, 0, 0, 0);
+    }
+    if (q_ok) {
+      const int64_t t_row0 = i * tstep * TRS;
+      const int64_t left = (int64_t)len - t_row0;
+      const int n_ok = left >= TRS ? TRS : (left > 0 ? (int)left : 0);
+      if (my_dense) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int rr = acc_row(r, lane);
+          const int64_t sl = i * TRS + rr;
+          if (sl < a.dense_cap)
+            my_dense[sl] = rr < n_ok ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
+        }
+      } else {
+        unsigned hits = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr) hits |= (1u << r);
+        if (hits) {
+          int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            if (hits & (1u << r)) {
+              const int64_t v = p0 + t_row0 + acc_row(r, lane);
+              if (pos < a.cap) my_cand[pos] = sq8_key(ah[r] * 256 + al[r], (uint32_t)a.row_ids[v]);
+              ++pos;
+            }
+          }
+        }
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) av[ks] = nx[ks];
+    }
+  }
+}
+
+// ------------------------------------------------ decode -------------------------------------------------------------
+// finalize wrote, per result, the key's high word as ord2f(word) and the original row (-1 = padding): recover S, report
+// (float)(b + t S), the optional i32 score and the row or mapped id
+__global__ void sq8_decode_kernel(float* scores, int64_t* rows, int* iscores, int64_t nq, int k, const float* __restrict__ qt,
+                                  const double* __restrict__ qb, const int64_t* __restrict__ id_map) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq * k) return;
+  const int64_t q = i / k;
+  const int64_t row = rows[i];
+  if (row < 0) {
+    scores[i] = -INFINITY; rows[i] = -1;
+    if (iscores) iscores[i] = (int)0x80000000;
+    return;
+  }
+  const int S = sq8_score_of_word(f2ord(scores[i]));
+  scores[i] = (float)(qb[q] + (double)qt[q] * (double)S);
+  if (iscores) iscores[i] = S;
+  if (id_map) rows[i] = id_map[row];
+}
+
+__global__ void sq8_gather_kernel(const int8_t* __restrict__ hi, const int8_t* __restrict__ lo, const float* __restrict__ Qf,
+                                  const int* __restrict__ idx, int n, int dpad, int dk, int8_t* ohi, int8_t* olo, float* oQ) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n * dpad) return;
+  const int64_t r = i / dpad;
+  const int j = (int)(i % dpad);
+  const size_t src = (size_t)idx[r];
+  ohi[i] = hi[src * dpad + j]; olo[i] = lo[src * dpad + j];
+  if (j < dk) oQ[r * dk + j] = Qf[src * dk + j];
+}
+
+// ------------------------------------------------ search driver ------------------------------------------------------
+// one internal pass: the queries [0, nq) of the pointers below
+struct Sq8Search {
+  Sq8Index* h;
+  const float* Qf;      // [nq, dk] f32 (coarse quantizer)
+  const int8_t* qhi;    // [nq, dpad]
+  const int8_t* qlo;
+  int64_t nq;
+  int k;
+  float* out_s; int64_t* out_r;   // [nq, k]: finalize's raw output, decoded by the caller
+  hipStream_t st;
+};
+
+struct Sq8Geom {
+  int nlist, nprobe;
+  int64_t cap_full, max_tiles, cap_lf, cap_df;
+};
+Sq8Geom sq8_geom(const Sq8Index* h) {
+  Sq8Geom g;
+  std::vector<int64_t> ll = h->list_len;
+  std::sort(ll.begin(), ll.end(), [](int64_t x, int64_t y) { return x > y; });
+  g.nlist = h->nlist;
+  g.nprobe = h->nprobe < h->nlist ? h->nprobe : h->nlist;
+  g.cap_full = 0;
+  for (int i = 0; i < g.nprobe; ++i) g.cap_full += ll[i];
+  if (g.cap_full < 1) g.cap_full = 1;
+  g.max_tiles = ll.empty() ? 0 : (ll[0] + TR - 1) / TR * (TR / TRS);
+  g.cap_lf = std::max<int64_t>(g.max_tiles * TRS, TRS);
+  g.cap_df = g.cap_lf * g.nprobe;
+  return g;
+}
+
+int sq8_prepare(const Sq8Search& s, const Sq8Geom& g, int first_tile_step, uint64_t* zero_buf, int64_t zero_n) {
+  Sq8Index* h = s.h;
+  const int64_t n = s.nq;
+  RCCHK(h->coarse.reserve(n * g.nlist));
+  RCCHK(h->probe_list.reserve(n * g.nprobe));
+  RCCHK(h->list_q.reserve(n * g.nprobe));
+  RCCHK(h->list_cnt.reserve(g.nlist)); RCCHK(h->list_qoff.reserve(g.nlist + 1)); RCCHK(h->list_cur.reserve(g.nlist));
+  RCCHK(h->work_off.reserve(g.nlist + 1)); RCCHK(h->plan.reserve(2));
+  if (zero_buf) HIPCHK(hipMemsetAsync(zero_buf, 0, sizeof(uint64_t) * (size_t)zero_n, s.st));
+  HIPCHK(hipMemsetAsync(h->list_cnt.p, 0, sizeof(int) * g.nlist, s.st));
+  RCCHK(launch_ivf_coarse(h->dk, s.Qf, n, h->C, g.nlist, h->coarse.p, s.st));
+  launch_ivf_select(h->coarse.p, n, g.nlist, g.nprobe, h->probe_list.p, h->list_cnt.p, s.st);
+  launch_ivf_plan(h->list_cnt.p, h->list_poff, g.nlist, first_tile_step, SQ8_TARGET, h->list_qoff.p, h->list_cur.p, h->work_off.p,
+                  h->plan.p, h->count.p, n * CSTRIDE, s.st);
+  launch_ivf_scatter(h->probe_list.p, n * g.nprobe, g.nprobe, h->list_cur.p, h->list_q.p, s.st);
+  return check_launch("sq8 prepare");
+}
+
+int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* cand, int64_t cap, int tile_step,
+             int64_t dense_cap, bool planned, int dense_ids) {
+  Sq8Index* h = s.h;
+  if (!planned)
+    launch_ivf_plan(h->list_cnt.p, h->list_poff, g.nlist, tile_step, SQ8_TARGET, h->list_qoff.p, h->list_cur.p, h->work_off.p,
+                    h->plan.p, h->count.p, s.nq * CSTRIDE, s.st);
+  Sq8LmArgs x;
+  memset(&x, 0, sizeof(x));
+  x.codes = h->codes; x.qhi = s.qhi; x.qlo = s.qlo; x.thr = thr; x.cand = cand; x.cap = cap; x.count = h->count.p;
+  x.row_ids = h->row_ids; x.list_poff = h->list_poff; x.list_len = h->list_len_dev; x.list_qoff = h->list_qoff.p;
+  x.list_q = h->list_q.p; x.work_off = h->work_off.p; x.plan = h->plan.p; x.nlist = g.nlist; x.tile_step = tile_step;
+  x.nprobe = g.nprobe; x.count_stride = CSTRIDE; x.dense_cap = dense_cap; x.dense_ids = dense_ids;
+  // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
+  const int64_t bound = (int64_t)SQ8_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
+  const dim3 grid((unsigned)((bound + 3) / 4));
+  if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64>), grid, dim3(256), 0, s.st, x);
+  else hipLaunchKernelGGL((sq8_scan_lm_kernel<128>), grid, dim3(256), 0, s.st, x);
+  return check_launch("sq8 scan");
+}
+
+// dense emission: every (query, probed list) pair owns a slot per row of the longest list, then the two-level select
+int sq8_dense(const Sq8Search& s, const Sq8Geom& g, const int* out_slot) {
+  Sq8Index* h = s.h;
+  const int64_t n = s.nq;
+  RCCHK(h->fcand.reserve(n * g.cap_df));
+  RCCHK(sq8_prepare(s, g, 1, h->fcand.p, n * g.cap_df));
+  RCCHK(sq8_scan(s, g, nullptr, h->fcand.p, g.cap_df, 1, g.cap_lf, true, 1));
+  const int64_t np_ = n * g.nprobe;
+  RCCHK(h->scand.reserve(np_ * s.k));
+  FinArgs f1;
+  memset(&f1, 0, sizeof(f1));
+  f1.nq = np_; f1.k = s.k; f1.count = nullptr; f1.cand = h->fcand.p; f1.cap = g.cap_lf; f1.mode = 0; f1.out_keys = h->scand.p;
+  RCCHK(launch_finalize(f1, (unsigned)np_, s.st));
+  FinArgs f2;
+  memset(&f2, 0, sizeof(f2));
+  f2.nq = n; f2.k = s.k; f2.count = nullptr; f2.out_scores = s.out_s; f2.out_rows = s.out_r; f2.cand = h->scand.p;
+  f2.cap = (int64_t)g.nprobe * s.k; f2.mode = 0; f2.out_slot = out_slot;
+  return launch_finalize(f2, (unsigned)n, s.st);
+}
+
+// the `nf` failed queries of h->fail_list, dense, 64 at a time, into their own output rows
+int sq8_redo(const Sq8Search& s, const Sq8Geom& g, int nf) {
+  Sq8Index* h = s.h;
+  const int FCH = 64;
+  RCCHK(h->fQ.reserve((int64_t)FCH * h->dk));
+  RCCHK(h->fhi.reserve((int64_t)FCH * h->dpad));
+  RCCHK(h->flo.reserve((int64_t)FCH * h->dpad));
+  for (int f0 = 0; f0 < nf; f0 += FCH) {
+    const int nfc = (nf - f0 < FCH) ? nf - f0 : FCH;
+    hipLaunchKernelGGL(sq8_gather_kernel, dim3((unsigned)(((int64_t)nfc * h->dpad + 255) / 256)), dim3(256), 0, s.st, s.qhi, s.qlo,
+                       s.Qf, h->fail_list.p + f0, nfc, h->dpad, h->dk, h->fhi.p, h->flo.p, h->fQ.p);
+    Sq8Search r = s;
+    r.Qf = h->fQ.p; r.qhi = h->fhi.p; r.qlo = h->flo.p; r.nq = nfc;
+    RCCHK(sq8_dense(r, g, h->fail_list.p + f0));
+  }
+  return RIHIP_OK;
+}
+
+// Thresholded pass, built as the f32 index's: (A) every 16th tile of each probed list into dense slots, the rank-th best
+// sampled score is the query's threshold; (B) all probed tiles, S >= threshold appended; select; a query whose list
+// overflowed, or that holds fewer than k candidates under a real threshold, is re-done dense.  Integer scores: a query that
+// passes holds every probed row with S >= threshold and at least k of them, so its top k is complete -- no epsilon.
+int sq8_thresholded(const Sq8Search& s, const Sq8Geom& g) {
+  Sq8Index* h = s.h;
+  const int64_t nq = s.nq;
+  const int k = s.k;
+  const double m = (double)k / SQ8_SS;
+  const int rank = (int)ceil(m + 4.0 * sqrt(m) + 4.0);
+  int64_t cap = 4096;
+  while ((double)cap < 2.5 * rank * SQ8_SS) cap <<= 1;
+  if (cap > g.cap_full) cap = g.cap_full;
+  const int64_t cap_l = std::max<int64_t>((g.max_tiles + SQ8_SS - 1) / SQ8_SS * TRS, TRS);
+  const int64_t cap_s = cap_l * g.nprobe;
+  RCCHK(h->scand.reserve(nq * cap_s));
+  RCCHK(h->cand.reserve(nq * cap));
+  RCCHK(sq8_prepare(s, g, SQ8_SS, h->scand.p, nq * cap_s));
+  RCCHK(sq8_scan(s, g, nullptr, h->scand.p, cap_s, SQ8_SS, cap_l, true, 0));
+  FinArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.nq = nq; fa.k = k; fa.out_scores = s.out_s; fa.out_rows = s.out_r;
+  fa.cand = h->scand.p; fa.cap = cap_s; fa.mode = 1; fa.rank = rank; fa.thr_out = h->thr.p; fa.count = nullptr;
+  fa.zero_me = h->n_fail.p;
+  RCCHK(launch_finalize(fa, (unsigned)nq, s.st));
+  RCCHK(sq8_scan(s, g, h->thr.p, h->cand.p, cap, 1, 0, false, 0));
+  fa.cand = h->cand.p; fa.cap = cap; fa.mode = 0; fa.thr_out = nullptr; fa.fail_flags = h->fail_flags.p;
+  fa.count = h->count.p; fa.zero_me = nullptr; fa.fail_list = h->fail_list.p; fa.n_fail = h->n_fail.p;
+  fa.ivf_thr = h->thr.p; fa.count_stride = CSTRIDE;
+  RCCHK(launch_finalize(fa, (unsigned)nq, s.st));
+  HIPCHK(hipMemcpyAsync(h->h_nfail, h->n_fail.p, sizeof(int), hipMemcpyDeviceToHost, s.st));
+  HIPCHK(hipStreamSynchronize(s.st));
+  const int nf = *h->h_nfail;
+  h->stats[0] += nq; h->stats[1] += nf;
+  return nf > 0 ? sq8_redo(s, g, nf) : RIHIP_OK;
+}
+
+int sq8_transform_queries(Sq8Index* h, const float* Q, int64_t nq, int16_t* n16, float* t_out, double* b_out, hipStream_t st) {
+  RCCHK(h->qhi.reserve(nq * h->dpad));
+  RCCHK(h->qlo.reserve(nq * h->dpad));
+  if (!t_out) { RCCHK(h->qt.reserve(nq)); t_out = h->qt.p; }
+  if (!b_out) { RCCHK(h->qb.reserve(nq)); b_out = h->qb.p; }
+  hipLaunchKernelGGL(sq8_query_kernel, dim3((unsigned)nq), dim3(128), 0, st, Q, nq, h->du, h->dpad, h->centre, h->scale, h->qhi.p,
+                     h->qlo.p, t_out, b_out, n16);
+  return check_launch("sq8 query transform");
+}
+
+int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* out_s, int64_t* out_r, int* out_i,
+               hipStream_t st) {
+  RCCHK(sq8_transform_queries(h, Q, nq, nullptr, nullptr, nullptr, st));
+  const float* Qf = Q;
+  if (h->du != h->dk) {
+    RCCHK(h->qpad.reserve(nq * h->dk));
+    RCCHK(pad_rows(Q, nq, h->du, h->dk, h->qpad.p, st));
+    Qf = h->qpad.p;
+  }
+  RIHIP_REQUIRE((reinterpret_cast<uintptr_t>(Qf) & 15) == 0, RIHIP_ERR_ARG, "sq8_index_search: Q must be 16-byte aligned");
+  const Sq8Geom g = sq8_geom(h);
+  bool thresholded = mode == 2;
+  if (mode == 0)
+    thresholded = !(nq * g.cap_df <= SQ8_DENSE_AUTO || g.cap_full <= 16384 || (double)k * 4.0 > (double)g.cap_full / SQ8_SS);
+  int64_t ch = SQ8_CH;
+  if (!thresholded) ch = std::max<int64_t>(1, std::min<int64_t>(SQ8_CH, SQ8_DENSE_BUDGET / g.cap_df));
+  const int64_t nmax = std::min(nq, ch);
+  RCCHK(h->count.reserve(nmax * CSTRIDE));
+  RCCHK(h->fail_flags.reserve(nmax)); RCCHK(h->fail_list.reserve(nmax)); RCCHK(h->thr.reserve(nmax)); RCCHK(h->n_fail.reserve(1));
+  if (!h->h_nfail) HIPCHK(hipHostMalloc((void**)&h->h_nfail, sizeof(int)));
+  for (int64_t q0 = 0; q0 < nq; q0 += ch) {
+    const int64_t n = std::min(ch, nq - q0);
+    const Sq8Search s{h, Qf + q0 * h->dk, h->qhi.p + q0 * h->dpad, h->qlo.p + q0 * h->dpad, n, k, out_s + q0 * k, out_r + q0 * k, st};
+    RCCHK(thresholded ? sq8_thresholded(s, g) : sq8_dense(s, g, nullptr));
+  }
+  const int64_t tot = nq * k;
+  hipLaunchKernelGGL(sq8_decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, out_s, out_r, out_i, nq, k, h->qt.p,
+                     h->qb.p, h->id_map);
+  return check_launch("sq8 decode");
+}
+
+// ------------------------------------------------ build --------------------------------------------------------------
+// list offsets / lengths on the device from the host copy list_len (lists padded to 64-row granules)
+int sq8_upload_layout(Sq8Index* h, hipStream_t st) {
+  std::vector<int64_t> poff(h->nlist + 1, 0);
+  std::vector<int> len(h->nlist);
+  for (int c = 0; c < h->nlist; ++c) {
+    poff[c + 1] = poff[c] + (h->list_len[c] + TR - 1) / TR * TR;
+    len[c] = (int)h->list_len[c];
+  }
+  RIHIP_REQUIRE(poff[h->nlist] == h->Np, RIHIP_ERR_STATE, "sq8_index: list lengths give %lld padded rows, the index holds %lld",
+                (long long)poff[h->nlist], (long long)h->Np);
+  HIPCHK(hipMalloc((void**)&h->list_poff, sizeof(int64_t) * (h->nlist + 1)));
+  HIPCHK(hipMalloc((void**)&h->list_len_dev, sizeof(int) * h->nlist));
+  HIPCHK(hipMemcpyAsync(h->list_poff, poff.data(), sizeof(int64_t) * (h->nlist + 1), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(h->list_len_dev, len.data(), sizeof(int) * h->nlist, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the host vectors go away)
+  return RIHIP_OK;
+}
+
+int sq8_build(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, hipStream_t st) {
+  h->du = src->du; h->dk = src->d; h->dpad = src->d <= 64 ? 64 : 128;
+  h->N = src->N;
+  h->nprobe = src->ivf ? src->nprobe : 1;
+  const int64_t n_src = src->ivf ? src->Np : src->N;
+  if (src->ivf) {
+    RIHIP_REQUIRE(src->C && src->row_ids && (int)src->list_len.size() == src->nlist && src->nlist >= 1, RIHIP_ERR_STATE,
+                  "sq8_index_from_ip_index: the IVF source is incomplete");
+    h->nlist = src->nlist; h->Np = src->Np; h->list_len = src->list_len;
+  } else {
+    h->nlist = 1; h->Np = (src->N + TR - 1) / TR * TR; h->list_len.assign(1, src->N);
+  }
+  RCCHK(sq8_upload_layout(h, st));
+  HIPCHK(hipMalloc((void**)&h->row_ids, sizeof(int64_t) * (size_t)h->Np));
+  HIPCHK(hipMalloc((void**)&h->C, sizeof(float) * (size_t)h->nlist * h->dk));
+  HIPCHK(hipMalloc((void**)&h->codes, (size_t)h->Np * h->dpad));
+  HIPCHK(hipMalloc((void**)&h->centre, sizeof(float) * h->dpad));
+  HIPCHK(hipMalloc((void**)&h->scale, sizeof(float) * h->dpad));
+  if (src->ivf) {
+    HIPCHK(hipMemcpyAsync(h->row_ids, src->row_ids, sizeof(int64_t) * (size_t)h->Np, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->C, src->C, sizeof(float) * (size_t)h->nlist * h->dk, hipMemcpyDeviceToDevice, st));
+  } else {
+    hipLaunchKernelGGL(sq8_identity_rows_kernel, dim3((unsigned)((h->Np + 255) / 256)), dim3(256), 0, st, h->row_ids, h->N, h->Np);
+    HIPCHK(hipMemsetAsync(h->C, 0, sizeof(float) * (size_t)h->dk, st));
+  }
+  if (centre) {   // injected quantiser: [du] host arrays, columns beyond du are (0, 1)
+    std::vector<float> m(h->dpad, 0.f), s(h->dpad, 1.f);
+    for (int j = 0; j < h->du; ++j) {
+      RIHIP_REQUIRE(isfinite(centre[j]) && isfinite(scale[j]) && scale[j] > 0.f, RIHIP_ERR_ARG,
+                    "sq8_index_from_ip_index: column %d: centre %g, scale %g (finite, scale > 0)", j, (double)centre[j], (double)scale[j]);
+      m[j] = centre[j]; s[j] = scale[j];
+    }
+    HIPCHK(hipMemcpyAsync(h->centre, m.data(), sizeof(float) * h->dpad, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->scale, s.data(), sizeof(float) * h->dpad, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+  } else {
+    const int nb = (int)std::min<int64_t>(1024, (n_src + 255) / 256);
+    float* part = nullptr;
+    HIPCHK(hipMalloc((void**)&part, sizeof(float) * (size_t)nb * 2 * h->dk));
+    hipLaunchKernelGGL(sq8_colrange_part_kernel, dim3(nb), dim3(256), 0, st, src->X, src->ivf ? h->row_ids : nullptr, n_src, h->dk, part);
+    hipLaunchKernelGGL(sq8_colrange_final_kernel, dim3(1), dim3(128), 0, st, part, nb, h->dk, h->dpad, h->centre, h->scale);
+    const hipError_t e = hipStreamSynchronize(st);
+    hipFree(part);
+    HIPCHK(e);
+  }
+  const int64_t nthr = h->Np * (h->dpad / 4);
+  hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, src->X, h->row_ids, n_src, h->Np, h->dk,
+                     h->dpad, h->centre, h->scale, h->codes);
+  RCCHK(check_launch("sq8 encode"));
+  HIPCHK(hipStreamSynchronize(st));   // the source may be dropped as soon as the call returns
+  return RIHIP_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------ C ABI --------------------------------------------------------------
+extern "C" int rihip_sq8_index_from_ip_index(void* ip_handle, const float* centre, const float* scale, void** handle, void* stream) {
+  const IpIndex* src = (const IpIndex*)ip_handle;
+  RIHIP_REQUIRE(src && handle, RIHIP_ERR_ARG, "sq8_index_from_ip_index: null handle");
+  RIHIP_REQUIRE(src->X && src->N > 0, RIHIP_ERR_STATE, "sq8_index_from_ip_index: the source index is empty");
+  RIHIP_REQUIRE((centre == nullptr) == (scale == nullptr), RIHIP_ERR_ARG, "sq8_index_from_ip_index: give both centre and scale, or neither");
+  Sq8Index* h = new Sq8Index();
+  const int rc = sq8_build(h, src, centre, scale, (hipStream_t)stream);
+  if (rc) { free_sq8(h); return rc; }
+  *handle = h;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_index_destroy(void* handle) {
+  if (handle) free_sq8((Sq8Index*)handle);
+  return RIHIP_OK;
+}
+
+extern "C" int64_t rihip_sq8_index_ntotal(void* handle) { return handle ? ((Sq8Index*)handle)->N : 0; }
+extern "C" int rihip_sq8_index_nlist(void* handle) { return handle ? ((Sq8Index*)handle)->nlist : 0; }
+
+extern "C" int rihip_sq8_index_set_nprobe(void* handle, int nprobe) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && nprobe >= 1, RIHIP_ERR_ARG, "sq8_index_set_nprobe: bad arguments");
+  h->nprobe = nprobe;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_index_set_id_map(void* handle, const int64_t* item_ids_dev) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h, RIHIP_ERR_ARG, "sq8_index_set_id_map: null handle");
+  h->id_map = item_ids_dev;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_index_get_quantizer(void* handle, float* centre, float* scale) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && centre && scale, RIHIP_ERR_ARG, "sq8_index_get_quantizer: bad arguments");
+  HIPCHK(hipMemcpy(centre, h->centre, sizeof(float) * h->du, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(scale, h->scale, sizeof(float) * h->du, hipMemcpyDeviceToHost));
+  return RIHIP_OK;
+}
+
+namespace {
+int sq8_rows_out(Sq8Index* h, float* out_x, int8_t* out_c) {
+  float* dx = nullptr; int8_t* dc = nullptr;
+  const size_t n = (size_t)h->N * h->du;
+  if (out_x) HIPCHK(hipMalloc((void**)&dx, sizeof(float) * n));
+  if (out_c && hipMalloc((void**)&dc, n) != hipSuccess) { hipFree(dx); rihip_set_error("sq8_index: device allocation failed"); return RIHIP_ERR_HIP; }
+  const int64_t tot = h->Np * h->du;
+  hipLaunchKernelGGL(sq8_reconstruct_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, h->codes, h->row_ids, h->Np, h->du,
+                     h->dpad, h->centre, h->scale, dx, dc);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && out_x) e = hipMemcpy(out_x, dx, sizeof(float) * n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_c) e = hipMemcpy(out_c, dc, n, hipMemcpyDeviceToHost);
+  hipFree(dx); hipFree(dc);
+  HIPCHK(e);
+  return RIHIP_OK;
+}
+}  // namespace
+
+extern "C" int rihip_sq8_index_get_codes(void* handle, int8_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_index_get_codes: bad arguments");
+  return sq8_rows_out(h, nullptr, out);
+}
+
+extern "C" int rihip_sq8_index_reconstruct(void* handle, float* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_index_reconstruct: bad arguments");
+  return sq8_rows_out(h, out, nullptr);
+}
+
+extern "C" int rihip_sq8_index_encode_queries(void* handle, const float* Q, int64_t nq, int16_t* out_n, float* out_t, double* out_b,
+                                              void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && Q && out_n && out_t && out_b && nq > 0, RIHIP_ERR_ARG, "sq8_index_encode_queries: bad arguments");
+  return sq8_transform_queries(h, Q, nq, out_n, out_t, out_b, (hipStream_t)stream);
+}
+
+extern "C" int rihip_sq8_index_search(void* handle, const float* Q, int64_t nq, int k, int mode, float* out_scores, int64_t* out_rows,
+                                      int32_t* out_iscores, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_index_search: index is empty");
+  RIHIP_REQUIRE(Q && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "sq8_index_search: bad arguments");
+  RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "sq8_index_search: k=%d outside [1,%d]", k, K_MAX);
+  RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_index_search: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
+  return sq8_search(h, Q, nq, k, mode, out_scores, out_rows, out_iscores, (hipStream_t)stream);
+}
+
+extern "C" int rihip_sq8_index_stats(void* handle, int64_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_index_stats: bad arguments");
+  out[0] = h->stats[0]; out[1] = h->stats[1]; out[2] = held_bytes(h);
+  return RIHIP_OK;
+}
+
+// File: "RIHIPSQ8", int64 header {version 1, du, dk, dpad, N, Np, nlist, nprobe}, centre f32[dpad], scale f32[dpad],
+// centroids f32[nlist, dk], list lengths int64[nlist], row ids int64[Np], codes int8[Np, dpad]
+extern "C" int rihip_sq8_index_save(void* handle, const char* path) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && path, RIHIP_ERR_ARG, "sq8_index_save: bad arguments");
+  std::vector<float> m(h->dpad), s(h->dpad), C((size_t)h->nlist * h->dk);
+  std::vector<int64_t> rid((size_t)h->Np);
+  std::vector<int8_t> codes((size_t)h->Np * h->dpad);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(m.data(), h->centre, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(s.data(), h->scale, sizeof(float) * s.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(C.data(), h->C, sizeof(float) * C.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rid.data(), h->row_ids, sizeof(int64_t) * rid.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(codes.data(), h->codes, codes.size(), hipMemcpyDeviceToHost));
+  FILE* f = fopen(path, "wb");
+  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "sq8_index_save: cannot open %s", path);
+  const int64_t hdr[8] = {1, h->du, h->dk, h->dpad, h->N, h->Np, h->nlist, h->nprobe};
+  bool ok = fwrite("RIHIPSQ8", 1, 8, f) == 8 && fwrite(hdr, sizeof(int64_t), 8, f) == 8 &&
+            fwrite(m.data(), sizeof(float), m.size(), f) == m.size() && fwrite(s.data(), sizeof(float), s.size(), f) == s.size() &&
+            fwrite(C.data(), sizeof(float), C.size(), f) == C.size() &&
+            fwrite(h->list_len.data(), sizeof(int64_t), h->nlist, f) == (size_t)h->nlist &&
+            fwrite(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fwrite(codes.data(), 1, codes.size(), f) == codes.size();
+  ok = (fclose(f) == 0) && ok;
+  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "sq8_index_save: short write to %s", path);
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_index_load(const char* path, void** handle) {
+  RIHIP_REQUIRE(path && handle, RIHIP_ERR_ARG, "sq8_index_load: bad arguments");
+  FILE* f = fopen(path, "rb");
+  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "sq8_index_load: cannot open %s", path);
+  char magic[8]; int64_t hdr[8];
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "RIHIPSQ8", 8) != 0 || fread(hdr, sizeof(int64_t), 8, f) != 8 || hdr[0] != 1) {
+    fclose(f); rihip_set_error("sq8_index_load: %s is not an SQ8 index file (magic / version)", path); return RIHIP_ERR_IO;
+  }
+  const int64_t du = hdr[1], dk = hdr[2], dpad = hdr[3], N = hdr[4], Np = hdr[5], nlist = hdr[6], nprobe = hdr[7];
+  const bool hdr_ok = du >= 1 && du <= 128 && dk == (du <= 32 ? 32 : (du <= 64 ? 64 : 128)) && dpad == (dk <= 64 ? 64 : 128) &&
+                      N >= 1 && N < (1ll << 31) && nlist >= 1 && nlist <= NLIST_MAX && nprobe >= 1 && nprobe < (1ll << 31) &&
+                      Np >= N && Np % TR == 0 && Np <= N + (int64_t)TR * nlist;
+  int64_t expect = 0, have = -1;
+  if (hdr_ok) {
+    expect = 8 + 64 + 8 * dpad + 4 * nlist * dk + 8 * nlist + 8 * Np + Np * dpad;
+    if (fseek(f, 0, SEEK_END) == 0) have = (int64_t)ftell(f);
+    if (fseek(f, 72, SEEK_SET) != 0) have = -1;
+  }
+  if (!hdr_ok || have != expect) {
+    fclose(f);
+    rihip_set_error("sq8_index_load: %s: %s", path, hdr_ok ? "file size does not match its header (truncated?)" : "header field out of range");
+    return RIHIP_ERR_IO;
+  }
+  std::vector<float> m(dpad), s(dpad), C((size_t)nlist * dk);
+  std::vector<int64_t> ll(nlist), rid((size_t)Np);
+  std::vector<int8_t> codes((size_t)Np * dpad);
+  bool ok = fread(m.data(), sizeof(float), m.size(), f) == m.size() && fread(s.data(), sizeof(float), s.size(), f) == s.size() &&
+            fread(C.data(), sizeof(float), C.size(), f) == C.size() && fread(ll.data(), sizeof(int64_t), nlist, f) == (size_t)nlist &&
+            fread(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fread(codes.data(), 1, codes.size(), f) == codes.size();
+  fclose(f);
+  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "sq8_index_load: short read from %s", path);
+  int64_t tot = 0, ptot = 0;
+  for (int64_t c = 0; c < nlist; ++c) {
+    RIHIP_REQUIRE(ll[c] >= 0 && ll[c] <= N, RIHIP_ERR_IO, "sq8_index_load: %s: list %lld has length %lld", path, (long long)c, (long long)ll[c]);
+    tot += ll[c]; ptot += (ll[c] + TR - 1) / TR * TR;
+  }
+  RIHIP_REQUIRE(tot == N && ptot == Np, RIHIP_ERR_IO, "sq8_index_load: %s: list lengths do not add up to the header's row counts", path);
+  for (int64_t p = 0; p < Np; ++p)
+    RIHIP_REQUIRE(rid[p] >= -1 && rid[p] < N, RIHIP_ERR_IO, "sq8_index_load: %s: row id %lld out of range", path, (long long)rid[p]);
+  for (int64_t j = 0; j < dpad; ++j)
+    RIHIP_REQUIRE(isfinite(m[j]) && isfinite(s[j]) && s[j] > 0.f, RIHIP_ERR_IO, "sq8_index_load: %s: quantiser column %lld is not finite", path, (long long)j);
+  Sq8Index* h = new Sq8Index();
+  h->du = (int)du; h->dk = (int)dk; h->dpad = (int)dpad; h->N = N; h->Np = Np; h->nlist = (int)nlist; h->nprobe = (int)nprobe;
+  h->list_len = ll;
+  auto fill = [&]() -> int {
+    RCCHK(sq8_upload_layout(h, 0));
+    HIPCHK(hipMalloc((void**)&h->row_ids, sizeof(int64_t) * rid.size()));
+    HIPCHK(hipMalloc((void**)&h->C, sizeof(float) * C.size()));
+    HIPCHK(hipMalloc((void**)&h->codes, codes.size()));
+    HIPCHK(hipMalloc((void**)&h->centre, sizeof(float) * dpad));
+    HIPCHK(hipMalloc((void**)&h->scale, sizeof(float) * dpad));
+    HIPCHK(hipMemcpy(h->row_ids, rid.data(), sizeof(int64_t) * rid.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->C, C.data(), sizeof(float) * C.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->centre, m.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->scale, s.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
+    return RIHIP_OK;
+  };
+  const int rc = fill();
+  if (rc) { free_sq8(h); return rc; }
+  *handle = h;
+  return RIHIP_OK;
+}

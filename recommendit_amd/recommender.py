@@ -23,6 +23,7 @@ from .coldstart import UserHistories, fold_in_users_device
 from .faiss_index import FAISSIndex
 from .ranker import LightGBMRanker
 from .seen import SeenItems, overfetch_k, plan_overfetch
+from .sq8_index import SQ8Index
 from .two_tower import N_GENRES, TwoTowerModel
 
 USER_SCALARS = [("avg_rating", 3.5), ("log_rating_count", 0.0), ("recency_score", 0.5), ("gender_encoded", 0.0),
@@ -202,10 +203,18 @@ class GpuRecommendationPipeline:
         replaces the one behind seen-item exclusion and item_filter, so it composes with both, and it is one launch
         without synchronisation: graph=True works.
 
+        index may be an SQ8Index (the 8-bit scalar-quantised index, sq8_index.py) for the plain chain: tower -> SQ8
+        search -> features -> ranker -> top-k.  A seen store, item_filter, diversity, the cold-start calls and
+        graph=True are not built for it yet: each raises ValueError.
+
         feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
         device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
         serving_features(), detect_skew(), reset_feature_log().  0 leaves the chain as it is."""
         self.model, self.index, self.ranker, self.store = model, index, ranker, store
+        self._sq8 = isinstance(index, SQ8Index)
+        if self._sq8:
+            self._no_sq8("a seen store", seen is not None)
+            self._no_sq8("diversity", diversity is not None)
         self.top_k_candidates, self.top_k_results = top_k_candidates, top_k_results
         self._graphs: Dict[Tuple[int, int, Optional[int], Optional[float]], Any] = {}
         self.diversity = None if diversity is None else RR.check_diversity(diversity)
@@ -220,8 +229,13 @@ class GpuRecommendationPipeline:
         self._log: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None
         self.reset_feature_log(feature_log_rows)
 
+    def _no_sq8(self, what: str, asked: bool) -> None:
+        if self._sq8 and asked:
+            raise ValueError(f"{what} is not supported on an SQ8 index (SQ8Index serves the plain chain only)")
+
     def set_seen(self, seen: Optional[SeenItems]) -> None:
         """attach / replace / detach (None) the store of excluded items; captured graphs are re-captured"""
+        self._no_sq8("a seen store", seen is not None)
         self.seen = seen
 
     def exclusion_deficit(self) -> int:
@@ -267,6 +281,10 @@ class GpuRecommendationPipeline:
         diversity: overrides the constructor's value for this call (a number in [0, 1], or None for the plain top-k);
         the outputs are then in MMR selection order, not in score order."""
         k = k or self.top_k_results
+        self._no_sq8("graph=True", bool(graph))
+        self._no_sq8("item_filter", item_filter is not None)
+        self._no_sq8("exclude_seen", bool(exclude_seen))
+        self._no_sq8("diversity", diversity is not _DEFAULT and diversity is not None)
         div = self._diversity_stage(diversity, k)
         if exclude_seen and self.seen is None:
             raise ValueError("exclude_seen=True without a seen store (set_seen)")
@@ -566,6 +584,7 @@ class GpuRecommendationPipeline:
         popularity_order() that pass item_filter and (exclude_history) are not in its history, score 1 - rank / (k + 1),
         retrieval score 0, -1 padded; no diversity stage, nothing logged.  The chain runs eager with the search's
         synchronous exactness check, like the item_filter branch of recommend_batch: there is no graph= option."""
+        self._no_sq8("recommend_cold_batch (cold start)", True)
         if not isinstance(histories, UserHistories):
             raise ValueError("recommend_cold_batch: histories must be a coldstart.UserHistories")
         k = k or self.top_k_results

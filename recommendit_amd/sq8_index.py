@@ -1,0 +1,312 @@
+"""SQ8Index: an 8-bit scalar-quantised inner-product index (flat and IVF) next to FAISSIndex (not in the reference; faiss
+has it as IndexScalarQuantizer / IndexIVFScalarQuantizer at 8 bits per dimension).
+
+Built from a trained FAISSIndex (``SQ8Index.from_index``), which may be dropped afterwards: the catalogue then takes
+64 or 128 bytes per item instead of 512 (d = 128) and the scan runs on the int8 matrix pipe.  The quantiser, the 16-bit
+query transform and the integer score are specified at ``rihip_sq8_index_*`` in recommendit_hip.h; the quantiser is
+not faiss's QT_8bit and faiss SQ files are not read or written.  Search results have FAISSIndex's shapes,
+dtypes and -1 padding; scores are (float)(b + t * S) of the integer score S, i.e. the inner product of the query with
+the DECODED vectors up to the query's own 16-bit rounding.
+
+There is no NumPy or torch path for encode or search: everything runs in csrc/sq8.hip.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+import pickle
+from pathlib import Path
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .faiss_index import FAISSIndex
+
+logger = logging.getLogger(__name__)
+
+MODES = {"auto": 0, "dense": 1, "thresholded": 2}
+
+
+class _SQ8Handle:
+    """Owns one rihip sq8_index; exposes the two faiss attributes the callers touch."""
+
+    def __init__(self, handle: int, owner: "SQ8Index"):
+        self._h = C.c_void_p(handle)
+        self._owner = owner
+
+    @property
+    def ntotal(self) -> int:
+        return int(L.lib().rihip_sq8_index_ntotal(self._h))
+
+    @property
+    def nprobe(self) -> int:
+        return self._owner.n_probe
+
+    @nprobe.setter
+    def nprobe(self, v: int) -> None:
+        self._owner.n_probe = int(v)
+        L.check(L.lib().rihip_sq8_index_set_nprobe(self._h, int(v)), "sq8_index_set_nprobe")
+
+    @property
+    def nlist(self) -> int:
+        return int(L.lib().rihip_sq8_index_nlist(self._h))
+
+    def __del__(self):
+        try:
+            if self._h:
+                L.lib().rihip_sq8_index_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _mode(mode) -> int:
+    if mode not in MODES:
+        raise ValueError(f"SQ8Index: unknown search mode {mode!r} (one of {sorted(MODES)})")
+    return MODES[mode]
+
+
+class SQ8Index:
+    def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
+        if not 1 <= int(embed_dim) <= 128:
+            raise ValueError(f"SQ8Index: embed_dim={embed_dim} outside 1..128")
+        self.embed_dim = int(embed_dim)
+        self.n_lists = n_lists
+        self.n_probe = n_probe
+        self.exact = exact
+        self.index: Optional[_SQ8Handle] = None
+        self.item_ids: Optional[np.ndarray] = None
+        self._item_id_to_faiss_idx: Dict[int, int] = {}
+        self._item_ids_dev: Optional[torch.Tensor] = None
+
+    # -- build ----------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_index(cls, faiss_index: FAISSIndex, ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> "SQ8Index":
+        """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  ranges: (centre,
+        scale), two f32 [embed_dim] arrays that replace the trained per-dimension quantiser; scale > 0."""
+        if not isinstance(faiss_index, FAISSIndex):
+            raise ValueError(f"SQ8Index.from_index needs a FAISSIndex, got {type(faiss_index).__name__}")
+        if faiss_index.index is None:
+            raise RuntimeError("Index not built.")
+        if faiss_index.search_pending():
+            raise RuntimeError("a deferred search is pending: call finish_search() before encoding the index")
+        d = faiss_index.embed_dim
+        m = s = None
+        if ranges is not None:
+            if len(ranges) != 2:
+                raise ValueError("SQ8Index: ranges must be (centre, scale)")
+            m = np.ascontiguousarray(ranges[0], dtype=np.float32)
+            s = np.ascontiguousarray(ranges[1], dtype=np.float32)
+            if m.shape != (d,) or s.shape != (d,):
+                raise ValueError(f"SQ8Index: ranges must be two [{d}] arrays, got {m.shape} and {s.shape}")
+            if not (np.isfinite(m).all() and np.isfinite(s).all() and (s > 0).all()):
+                raise ValueError("SQ8Index: ranges must be finite with scale > 0")
+        obj = cls(embed_dim=d, n_lists=faiss_index.n_lists, n_probe=faiss_index.n_probe, exact=not faiss_index.index.is_ivf)
+        h = C.c_void_p()
+        L.check(L.lib().rihip_sq8_index_from_ip_index(faiss_index.index._h, None if m is None else m.ctypes.data,
+                                                      None if s is None else s.ctypes.data, C.byref(h), L.stream_ptr()),
+                "sq8_index_from_ip_index")
+        obj.index = _SQ8Handle(h.value, obj)
+        obj.item_ids = np.array(faiss_index.item_ids, dtype=np.int64)
+        obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())
+        obj._item_id_to_faiss_idx = dict(faiss_index._item_id_to_faiss_idx)
+        logger.info("SQ8 index built: %d vectors, %d lists, probe=%d", obj.index.ntotal, obj.index.nlist, obj.n_probe)
+        return obj
+
+    def _built(self) -> _SQ8Handle:
+        if self.index is None:
+            raise RuntimeError("Index not built. Call SQ8Index.from_index() first.")
+        return self.index
+
+    # -- trained state ----------------------------------------------------------------------------------------------
+    def quantizer(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(centre, scale): f32 [embed_dim] each"""
+        h = self._built()
+        m = np.empty(self.embed_dim, dtype=np.float32)
+        s = np.empty(self.embed_dim, dtype=np.float32)
+        L.check(L.lib().rihip_sq8_index_get_quantizer(h._h, m.ctypes.data, s.ctypes.data), "sq8_index_get_quantizer")
+        return m, s
+
+    def codes(self) -> np.ndarray:
+        """int8 [N, embed_dim]: the stored codes in insertion order"""
+        h = self._built()
+        c = np.empty((h.ntotal, self.embed_dim), dtype=np.int8)
+        L.check(L.lib().rihip_sq8_index_get_codes(h._h, c.ctypes.data), "sq8_index_get_codes")
+        return c
+
+    def reconstruct(self) -> np.ndarray:
+        """f32 [N, embed_dim]: the decoded vectors centre + scale * code in insertion order"""
+        h = self._built()
+        x = np.empty((h.ntotal, self.embed_dim), dtype=np.float32)
+        L.check(L.lib().rihip_sq8_index_reconstruct(h._h, x.ctypes.data), "sq8_index_reconstruct")
+        return x
+
+    def encode_queries(self, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """the search's first stage on f32 [nq, embed_dim] device queries (taken as they are): (n int16 [nq, embed_dim],
+        t f32 [nq], b f64 [nq]) on the device"""
+        h = self._built()
+        q = self._queries(queries)
+        nq = q.shape[0]
+        n = torch.empty((nq, self.embed_dim), dtype=torch.int16, device=q.device)
+        t = torch.empty((nq,), dtype=torch.float32, device=q.device)
+        b = torch.empty((nq,), dtype=torch.float64, device=q.device)
+        L.check(L.lib().rihip_sq8_index_encode_queries(h._h, q.data_ptr(), nq, n.data_ptr(), t.data_ptr(), b.data_ptr(),
+                                                       L.stream_ptr()), "sq8_index_encode_queries")
+        return n, t, b
+
+    # -- search -----------------------------------------------------------------------------------------------------
+    def _queries(self, queries: torch.Tensor) -> torch.Tensor:
+        if not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != self.embed_dim:
+            shape = tuple(queries.shape) if hasattr(queries, "shape") else type(queries).__name__
+            raise ValueError(f"SQ8Index: queries must be a tensor [nq, {self.embed_dim}], got {shape}")
+        if queries.shape[0] == 0:
+            raise ValueError("SQ8Index: no queries")
+        return queries.to(device=L.device(), dtype=torch.float32).contiguous()
+
+    def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool, mode: int, return_int: bool):
+        h = self._built()
+        lib = L.lib()
+        if k < 1:
+            raise ValueError(f"SQ8Index: k={k} must be at least 1")
+        if k > int(lib.rihip_ip_index_max_k()):
+            raise ValueError(f"k={k} exceeds the device select buffer ({int(lib.rihip_ip_index_max_k())})")
+        nq = q_dev.shape[0]
+        L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr() if item_ids else None),
+                "sq8_index_set_id_map")
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=q_dev.device)
+        ints = torch.empty((nq, k), dtype=torch.int32, device=q_dev.device) if return_int else None
+        L.check(lib.rihip_sq8_index_search(h._h, q_dev.data_ptr(), nq, k, mode, scores.data_ptr(), rows.data_ptr(),
+                                           L.ptr(ints), L.stream_ptr()), "sq8_index_search")
+        return (scores, rows, ints) if return_int else (scores, rows)
+
+    def search(self, query_vector: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+        h = self._built()
+        query = np.atleast_2d(query_vector).astype(np.float32)
+        if query.shape[1] != self.embed_dim:
+            raise ValueError(f"SQ8Index: query width {query.shape[1]}, index width {self.embed_dim}")
+        query = query / np.maximum(np.linalg.norm(query, axis=1, keepdims=True), 1e-8)
+        k = min(k, h.ntotal)
+        q_dev = torch.from_numpy(np.ascontiguousarray(query[:1])).to(L.device())
+        scores, rows = self._search_device(q_dev, k, False, 0, False)
+        distances, idx = scores[0].cpu().numpy(), rows[0].cpu().numpy()
+        valid = idx >= 0
+        return distances[valid], self.item_ids[idx[valid]]
+
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+        h = self._built()
+        queries = np.asarray(query_vectors).astype(np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.embed_dim:
+            raise ValueError(f"SQ8Index: queries must be [nq, {self.embed_dim}], got {queries.shape}")
+        queries = queries / np.maximum(np.linalg.norm(queries, axis=1, keepdims=True), 1e-8)
+        k = min(k, h.ntotal)
+        q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
+        scores, ids = self._search_device(self._queries(q_dev), k, True, 0, False)
+        return scores.cpu().numpy(), ids.cpu().numpy()
+
+    def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, mode: str = "auto",
+                            return_int: bool = False):
+        """queries f32 [nq, embed_dim] on the device -> (scores f32, item ids i64) [nq, k] on the device, -1 padded;
+        return_int=True appends the integer scores i32 [nq, k].  mode: "auto", "dense" or "thresholded" (the same bytes
+        from each; "thresholded" synchronises the stream for its completeness check)."""
+        h = self._built()
+        m = _mode(mode)
+        q = self._queries(queries)
+        if not normalized:
+            q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
+        return self._search_device(q, min(k, h.ntotal), True, m, return_int)
+
+    def search_rows_device(self, queries: torch.Tensor, k: int, mode: str = "auto", return_int: bool = False):
+        """batch_search_device on queries taken as they are, returning ROWS (insertion order) instead of item ids and k
+        as given (padded beyond ntotal)"""
+        return self._search_device(self._queries(queries), k, False, _mode(mode), return_int)
+
+    # -- the calls a serve chain makes on its index; an SQ8 search has no pending state -------------------------------
+    def set_deferred_check(self, enable: bool) -> None:
+        self._built()
+
+    def finish_search(self) -> int:
+        return 0
+
+    def search_pending(self) -> bool:
+        return False
+
+    def last_fail_count(self) -> int:
+        return 0
+
+    def exclusion_deficit(self) -> int:
+        return 0
+
+    # -- persistence ------------------------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        h = self._built()
+        save_path = Path(path)
+        save_path.parent.mkdir(parents=True, exist_ok=True)
+        L.check(L.lib().rihip_sq8_index_save(h._h, str(save_path).encode()), "sq8_index_save")
+        meta = {
+            "item_ids": self.item_ids,
+            "item_id_to_faiss_idx": self._item_id_to_faiss_idx,
+            "embed_dim": self.embed_dim,
+            "n_lists": self.n_lists,
+            "n_probe": self.n_probe,
+        }
+        with open(save_path.with_suffix(".meta.pkl"), "wb") as f:
+            pickle.dump(meta, f)
+        logger.info("Saved SQ8 index to %s", save_path)
+
+    @classmethod
+    def load(cls, path: str) -> "SQ8Index":
+        load_path = Path(path)
+        if not load_path.exists():
+            raise FileNotFoundError(f"SQ8 index not found at {load_path}")
+        with open(load_path.with_suffix(".meta.pkl"), "rb") as f:
+            meta = pickle.load(f)  # sidecar written by save() above
+        obj = cls(embed_dim=meta["embed_dim"], n_lists=meta["n_lists"], n_probe=meta["n_probe"])
+        h = C.c_void_p()
+        L.check(L.lib().rihip_sq8_index_load(str(load_path).encode(), C.byref(h)), "sq8_index_load")
+        obj.index = _SQ8Handle(h.value, obj)
+        obj.index.nprobe = meta["n_probe"]
+        obj.item_ids = np.asarray(meta["item_ids"], dtype=np.int64)
+        if obj.item_ids.shape[0] != obj.index.ntotal:
+            raise ValueError(f"{load_path}: {obj.index.ntotal} vectors, {obj.item_ids.shape[0]} item ids in the sidecar")
+        obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())
+        obj._item_id_to_faiss_idx = meta["item_id_to_faiss_idx"]
+        return obj
+
+    # -- utilities --------------------------------------------------------------------------------------------------
+    def search_stats(self) -> Tuple[int, int]:
+        """(queries searched by the thresholded pass, of those re-done dense) since the handle was made"""
+        out = (C.c_int64 * 3)()
+        L.check(L.lib().rihip_sq8_index_stats(self._built()._h, out), "sq8_index_stats")
+        return int(out[0]), int(out[1])
+
+    def stats(self) -> Dict:
+        if self.index is None:
+            return {"status": "not built"}
+        out = (C.c_int64 * 3)()
+        L.check(L.lib().rihip_sq8_index_stats(self.index._h, out), "sq8_index_stats")
+        n = int(self.index.ntotal)
+        bpv = 64 if self.embed_dim <= 64 else 128
+        f32_row = 4 * (32 if self.embed_dim <= 32 else bpv)      # the f32 index stores rows at its kernel width
+        return {
+            "n_vectors": n,
+            "embed_dim": self.embed_dim,
+            "n_lists": self.index.nlist,
+            "n_probe": self.n_probe,
+            "metric": "inner_product",
+            "n_item_ids": len(self.item_ids) if self.item_ids is not None else 0,
+            "bytes_per_vector": bpv,
+            "compression": f32_row / bpv,
+            "device_bytes": int(out[2]),
+            "queries_thresholded": int(out[0]),
+            "queries_redone": int(out[1]),
+        }
+
+    def set_n_probe(self, n_probe: int) -> None:
+        if int(n_probe) < 1:
+            raise ValueError(f"SQ8Index: n_probe={n_probe} must be at least 1")
+        self.n_probe = int(n_probe)
+        if self.index is not None:
+            self.index.nprobe = int(n_probe)
