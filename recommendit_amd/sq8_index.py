@@ -103,7 +103,9 @@ class SQ8Index:
                 raise ValueError(f"SQ8Index: ranges must be two [{d}] arrays, got {m.shape} and {s.shape}")
             if not (np.isfinite(m).all() and np.isfinite(s).all() and (s > 0).all()):
                 raise ValueError("SQ8Index: ranges must be finite with scale > 0")
-        obj = cls(embed_dim=d, n_lists=faiss_index.n_lists, n_probe=faiss_index.n_probe, exact=not faiss_index.index.is_ivf)
+        ivf = bool(faiss_index.index.is_ivf)
+        # a flat source becomes one list probed once: that is what the handle holds and what load() must hand back to it
+        obj = cls(embed_dim=d, n_lists=faiss_index.n_lists, n_probe=faiss_index.n_probe if ivf else 1, exact=not ivf)
         h = C.c_void_p()
         L.check(L.lib().rihip_sq8_index_from_ip_index(faiss_index.index._h, None if m is None else m.ctypes.data,
                                                       None if s is None else s.ctypes.data, C.byref(h), L.stream_ptr()),

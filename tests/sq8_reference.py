@@ -95,3 +95,157 @@ def probed_lists(Q, C, nprobe):
     for q in range(cs.shape[0]):
         out[q] = ids[np.lexsort((ids, -cs[q]))][:nprobe]
     return out
+
+
+# ---- additions for tests/test_gpu_sq8_paths.py: a faster exact reference and the driver's arithmetic --------------------
+def int_scores_blas(n, c):
+    """int_scores through a float64 matmul: every product is an integer below 2^22 and every partial sum below
+    32512 * 127 * 128 < 2^29, far inside the 2^53 of a double, so the result is exact in any summation order"""
+    out = n.astype(np.float64) @ c.astype(np.float64).T
+    r = np.rint(out)
+    assert (r == out).all()
+    return r.astype(np.int64)
+
+
+def topk_fast(S, k, allowed=None, chunk=256):
+    """topk() for large S: one int64 sort key per score (-S in the high bits, the row in the low 24), partition + sort"""
+    nq, N = S.shape
+    assert N < 2 ** 24 and np.abs(S).max() < 2 ** 38
+    rows = np.full((nq, k), -1, dtype=np.int64)
+    sc = np.zeros((nq, k), dtype=np.int64)
+    kk = min(k, N)
+    ar = np.arange(N, dtype=np.int64)
+    big = np.int64(2 ** 62)
+    for q0 in range(0, nq, chunk):
+        s = S[q0:q0 + chunk]
+        key = (-s) * (1 << 24) + ar[None, :]
+        if allowed is not None:
+            key = np.where(allowed[q0:q0 + chunk], key, big)
+        if kk < N:
+            key = np.partition(key, kk - 1, axis=1)[:, :kk]
+        key = np.sort(key, axis=1)
+        ok = key < big
+        r = np.where(ok, key & ((1 << 24) - 1), -1)
+        rows[q0:q0 + chunk, :kk] = r
+        sc[q0:q0 + chunk, :kk] = np.where(ok, np.take_along_axis(s, np.maximum(r, 0), axis=1), 0)
+    return rows, sc
+
+
+GRANULE = 64          # rows a list is padded to (TR)
+TILE = 32             # rows per scanned tile (TRS)
+SAMPLE_STEP = 16      # the threshold sample takes every 16th tile of a list (SQ8_SS)
+PASS_QUERIES = 4096   # queries per internal pass (SQ8_CH)
+
+
+def _tiles(list_len):
+    return (int(list_len) + GRANULE - 1) // GRANULE * (GRANULE // TILE)
+
+
+def plan(list_lens, probes_per_list, tile_step, target=4096):     # 4096: SQ8_TARGET = 16 * RIHIP_NCU in csrc/sq8.hip
+    """the work plan as the rule above ivf_plan_body states it: (tpi, n_seq per list, splits per list).  A wave takes one
+    list, 32 of the queries probing it and tpi consecutive sampled tiles; tpi = ceil(total_tiles / target)"""
+    n_seq = [(_tiles(l) + tile_step - 1) // tile_step for l in list_lens]
+    total = sum((int(p) + 31) // 32 * s for p, s in zip(probes_per_list, n_seq))
+    tpi = max(1, (total + target - 1) // target)
+    return tpi, n_seq, [(s + tpi - 1) // tpi for s in n_seq]
+
+
+def geometry(list_lens, nprobe):
+    """(nprobe used, cap_full, cap_lf, cap_df): rows of the nprobe longest lists; dense slots per (query, list) pair =
+    the longest list padded; dense slots per query"""
+    ll = sorted((int(l) for l in list_lens), reverse=True)
+    npr = min(int(nprobe), len(ll))
+    cap_full = max(1, sum(ll[:npr]))
+    cap_lf = max(_tiles(ll[0]) * TILE, TILE)
+    return npr, cap_full, cap_lf, cap_lf * npr
+
+
+def auto_is_thresholded(nq, k, list_lens, nprobe):
+    """the rule at SQ8_DENSE_AUTO: dense while the batch's dense slots stay within 2^23, or the probed rows within 16 384,
+    or the sample is too short for k (4 k > cap_full / 16)"""
+    _, cap_full, _, cap_df = geometry(list_lens, nprobe)
+    return not (nq * cap_df <= 2 ** 23 or cap_full <= 16384 or 4.0 * k > cap_full / SAMPLE_STEP)
+
+
+def dense_chunk(list_lens, nprobe):
+    """queries per dense pass, the rule at SQ8_DENSE_BUDGET: 2^26 dense slots at most, 4 096 queries at most"""
+    _, _, _, cap_df = geometry(list_lens, nprobe)
+    return max(1, min(PASS_QUERIES, 2 ** 26 // cap_df))
+
+
+def threshold_rank(k):
+    """the sampled score that becomes the threshold: the rank-th best, rank = ceil(m + 4 sqrt(m) + 4), m = k / 16"""
+    m = k / SAMPLE_STEP
+    return int(np.ceil(m + 4.0 * np.sqrt(m) + 4.0))
+
+
+def threshold_cap(k, list_lens, nprobe):
+    """candidate slots per query of the thresholded pass: the power of two from 4 096 up that holds 2.5 * rank * 16,
+    at most cap_full"""
+    cap = 4096
+    while cap < 2.5 * threshold_rank(k) * SAMPLE_STEP:
+        cap *= 2
+    return min(cap, geometry(list_lens, nprobe)[1])
+
+
+def flat_sample_rows(N):
+    """rows of a one-list index that the threshold sample scores: tiles 0, 16, 32, ..."""
+    r = np.arange(N)
+    return r[(r // TILE) % SAMPLE_STEP == 0]
+
+
+REDO, KEPT, EITHER = 1, 0, -1
+
+
+def _redo_state(scores, samp, rank, cap, k):
+    """one query: scores int64 [rows it probes], samp int64 [its sampled rows].  The rule above sq8_thresholded: the
+    threshold is the rank-th best sampled score, every probed row with S >= threshold becomes a candidate, and the query is
+    re-done when the candidates overflow its cap slots or are fewer than k under a real threshold.  A sample shorter than
+    rank gives no threshold: every probed row is a candidate and only overflow fails.
+
+    What the rule leaves open: the select that finds the threshold (finalize_kernel, mode 1) may stop its radix passes as
+    soon as exactly rank sampled keys remain above its prefix, so the threshold it hands on is SOME value t with
+    #{sampled >= t} == rank: anything above the (rank+1)-th best sampled score up to the rank-th best (only the rank-th
+    best itself when the two tie).  The candidate count is monotone in t, so the verdict is REDO / KEPT when both ends of
+    that interval agree and EITHER when they do not."""
+    if len(samp) < rank:
+        return REDO if len(scores) > cap else KEPT
+    top = -np.sort(-samp)[:rank + 1]
+    a = top[rank - 1]
+    lo = None if len(samp) == rank else (a if top[rank] == a else top[rank] + 1)
+    cnt_min = int((scores >= a).sum())
+    cnt_max = len(scores) if lo is None else int((scores >= lo).sum())
+    fail_hi, fail_lo = cnt_min > cap or cnt_min < k, cnt_max > cap or cnt_max < k
+    if cnt_min <= cap < cnt_max or cnt_min < k <= cnt_max:      # the verdict changes somewhere inside the interval
+        return EITHER
+    return REDO if fail_hi and fail_lo else (KEPT if not fail_hi and not fail_lo else EITHER)
+
+
+def redo_bounds(state):
+    """(fewest, most) queries a thresholded pass may re-do, from the states of its queries"""
+    state = np.asarray(state)
+    return int((state == REDO).sum()), int((state != KEPT).sum())
+
+
+def flat_thresholded_redo(S, k):
+    """int8 [nq] of REDO / KEPT / EITHER for a ONE-LIST index: the sample is every 16th tile of the list"""
+    nq, N = S.shape
+    rank, cap = threshold_rank(k), threshold_cap(k, [N], 1)
+    samp = flat_sample_rows(N)
+    return np.array([_redo_state(S[q], S[q, samp], rank, cap, k) for q in range(nq)], dtype=np.int8)
+
+
+def ivf_thresholded_redo(S, k, assign, probes, nlist):
+    """flat_thresholded_redo for an IVF index: assign int [N] (the list of every row; rows ascend inside a list, as
+    ip_index.h states), probes int [nq, nprobe].  The sample of a query is every 16th tile of each list it probes"""
+    nq, N = S.shape
+    list_lens = np.bincount(assign, minlength=nlist)
+    rank, cap = threshold_rank(k), threshold_cap(k, list_lens, probes.shape[1])
+    rows_of = [np.nonzero(assign == l)[0] for l in range(nlist)]
+    samp_of = [r[(np.arange(len(r)) // TILE) % SAMPLE_STEP == 0] for r in rows_of]
+    out = np.empty(nq, dtype=np.int8)
+    for q in range(nq):
+        probed = np.concatenate([rows_of[l] for l in probes[q]])
+        samp = np.concatenate([samp_of[l] for l in probes[q]])
+        out[q] = _redo_state(S[q, probed], S[q, samp], rank, cap, k)
+    return out
