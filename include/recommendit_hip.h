@@ -571,12 +571,26 @@ int rihip_ip_index_list_sizes(void* handle, int64_t* out);
  * predicate per query) or 0 (one shared by the batch).  Honours set_id_map.  Its exactness check is always synchronous
  * (set_deferred_check is ignored); RIHIP_ERR_STATE without tags or while a deferred search is pending.  A large flat
  * index takes the all-f32 scan whatever set_two_precision says.
- * filtered_stats: cumulative {queries searched filtered, of those re-done by the exact fallback}. */
+ * filtered_stats: cumulative {queries searched filtered, of those re-done by the exact fallback}.
+ * search_stats: what the search driver did since the handle was made, plain and filtered searches alike: 12 cumulative
+ * host-side counters (no kernel reads or writes them; reading them synchronises nothing).  A search of nq queries runs
+ * ceil(nq / 4096) internal passes, each on one path:
+ *   out[0]  passes on the flat dense path (N <= 65 536)
+ *   out[1]  passes on the flat thresholded path, all-f32 (set_two_precision(0), or a filtered search)
+ *   out[2]  ... two-precision with the fused refine (k <= 2048)       out[3]  ... two-precision, unfused re-score
+ *   out[4]  passes on the unfiltered IVF path as the first choice (its use as the exact re-do is not counted here)
+ *   out[5]  passes on the thresholded IVF path
+ *   out[6]  of out[2] + out[3], the passes whose threshold sample kept the best scores per stream in registers
+ *   out[7]  IVF prepares done in one launch (<= 8 queries; the re-do's prepares count)
+ *   out[8]  queries that went through a thresholded pass (flat or IVF)
+ *   out[9]  of those, the queries re-done exactly, those of rihip_ip_index_search_finish included
+ *   out[10] re-do chunks (8 queries flat, 64 IVF)                     out[11] internal passes in all */
 int rihip_ip_index_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream);
 int rihip_ip_index_has_tags(void* handle);
 int rihip_ip_index_search_filtered(void* handle, const float* Q, int64_t nq, int k, const uint32_t* pred_dev,
                                    int64_t pred_stride, float* out_scores, int64_t* out_rows, void* stream);
 int rihip_ip_index_filtered_stats(void* handle, int64_t* out);
+int rihip_ip_index_search_stats(void* handle, int64_t* out);     /* out: int64[12] */
 
 /* ---- 8-bit scalar-quantised index (faiss IndexScalarQuantizer / IndexIVFScalarQuantizer at 8 bits; the reference's
  * FAISSIndex has none) ----------------------------------------------------------------------

@@ -137,6 +137,7 @@ SIGNATURES = {
     "rihip_ip_index_has_tags": (C.c_int, [vp]),
     "rihip_ip_index_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, vp, c_i64, vp, vp, vp]),
     "rihip_ip_index_filtered_stats": (C.c_int, [vp, vp]),
+    "rihip_ip_index_search_stats": (C.c_int, [vp, vp]),
     "rihip_sq8_index_from_ip_index": (C.c_int, [vp, vp, vp, C.POINTER(vp), vp]),
     "rihip_sq8_index_destroy": (C.c_int, [vp]),
     "rihip_sq8_index_ntotal": (c_i64, [vp]),

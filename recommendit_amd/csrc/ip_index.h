@@ -12,6 +12,12 @@ constexpr int TR = 64;         // list granule: every IVF list is padded to a mu
 constexpr int TRS = 32;        // corpus rows per LDS tile of the exact-f32 scan kernel
 constexpr int K_MAX = 16384;   // largest k served by the device select/sort buffer (128 KiB of LDS)
 constexpr int NLIST_MAX = 2048;  // probe bitset: 64 words per query
+// slots of IpIndex::search_stats, in the order rihip_ip_index_search_stats reports them (recommendit_hip.h)
+enum SearchStat {
+  ST_FLAT_DENSE = 0, ST_FLAT_F32, ST_FLAT_FUSED, ST_FLAT_UNFUSED, ST_IVF_UNFILTERED, ST_IVF_THRESHOLDED, ST_SAMPLE_TOP,
+  ST_PREPARE_SMALL, ST_THR_QUERIES, ST_REDONE, ST_REDO_CHUNKS, ST_PASSES, ST_COUNT
+};
+static_assert(ST_COUNT == 12, "rihip_ip_index_search_stats reports 12 counters");
 
 template <typename T>
 struct DevBuf {
@@ -55,6 +61,9 @@ struct IpIndex {
   // (flat: [N] row order; IVF: [Np] physical order, padding slots 0); null = untagged
   uint32_t* tags = nullptr;
   int64_t filt_stats[2] = {0, 0};   // queries searched filtered, of those re-done by the exact fallback
+  // what the search driver did since the handle was made (rihip_ip_index_search_stats; slots: SearchStat).  Host
+  // counters of the driver functions in topk.hip: no kernel reads or writes them
+  int64_t search_stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<int64_t> list_len;  // host copy
   // scratch (grown on demand, owned by the handle)
   DevBuf<uint64_t> cand, scand, fcand, seg;   // seg: per (query, corpus split) survivor segments of the bf16 filter

@@ -223,7 +223,11 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
   }
 
   if (a.mode == 1) {
-    if (tid == 0) a.thr_out[q] = (k_sel > 0 && k_sel == a.rank) ? ord2f((uint32_t)(T >> 32)) : -INFINITY;
+    // A list with fewer than `rank` real keys has the empty key 0 as its rank-th best: that is no threshold (-inf, every
+    // row a candidate), not ord2f(0) -- a NaN that `score >= thr` rejects for every row and that `ivf_thr > -inf`
+    // below does not count as a threshold either, so an IVF query with few sampled rows came back empty.
+    if (tid == 0)
+      a.thr_out[q] = (k_sel > 0 && k_sel == a.rank && (uint32_t)(T >> 32) != 0u) ? ord2f((uint32_t)(T >> 32)) : -INFINITY;
     return;
   }
   FIN_STAMP(2);

@@ -141,6 +141,7 @@ int ivf_prepare(const Search& s, const IvfGeom& g, int first_tile_step, uint64_t
   RCCHK(h->work_off.reserve(nlist + 1)); RCCHK(h->plan.reserve(2));
   if (n <= 8) {   // one launch (see ivf_prepare_small_kernel): the single workgroup takes the queries 4 at a time, so beyond a
                   // handful of queries the four parallel kernels are faster (64 queries: 0.48 vs 0.37 ms per batch)
+    ++h->search_stats[ST_PREPARE_SMALL];
     PrepSmallArgs p;
     p.Q = s.Q; p.nq = n; p.C = h->C; p.nlist = nlist; p.nprobe = nprobe; p.cs = h->coarse.p; p.probe_list = h->probe_list.p;
     p.list_cnt = h->list_cnt.p; p.list_poff = h->list_poff; p.tile_step = first_tile_step; p.target_items = IVF_TARGET;
@@ -209,8 +210,10 @@ int ivf_redo(const Search& s, const IvfGeom& g, int nf) {
   IpIndex* h = s.h;
   const int FCH = 64;
   RCCHK(h->fQ.reserve((int64_t)FCH * h->d));
+  h->search_stats[ST_REDONE] += nf;
   for (int f0 = 0; f0 < nf; f0 += FCH) {
     const int nfc = (nf - f0 < FCH) ? nf - f0 : FCH;
+    ++h->search_stats[ST_REDO_CHUNKS];
     gather_rows(s, h->fail_list.p + f0, nfc, h->fQ.p);
     RCCHK(ivf_unfiltered(redo_of(s, h->fail_list.p + f0, nfc), g, h->fail_list.p + f0));
   }
@@ -232,6 +235,8 @@ int ivf_thresholded(const Search& s, const IvfGeom& g) {
   if (cap > g.cap_full) cap = g.cap_full;
   const int64_t cap_l = (g.max_tiles + SS - 1) / SS * TRS;             // sampled rows of the longest list
   const int64_t cap_s = cap_l * g.nprobe;
+  ++h->search_stats[ST_IVF_THRESHOLDED];
+  h->search_stats[ST_THR_QUERIES] += nq;
   RCCHK(h->scand.reserve(nq * cap_s));
   RCCHK(h->cand.reserve(nq * cap));
   // ---- pass A
@@ -312,6 +317,7 @@ int64_t f32_tiles(const IpIndex* h) { return (h->N + TRS - 1) / TRS; }
 int flat_dense(const Search& s) {
   IpIndex* h = s.h;
   const int64_t nq = s.nq;
+  ++h->search_stats[ST_FLAT_DENSE];
   RCCHK(h->cand.reserve(nq * h->N));
   hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s.st, h->count.p, nq, (int)h->N);
   ScanArgs sa = scan_args(s);
@@ -331,8 +337,10 @@ int flat_redo(const Search& s, int nf) {
   RCCHK(h->fcand.reserve((int64_t)FCH * h->N));
   RCCHK(h->fQ.reserve((int64_t)FCH * h->d));
   RCCHK(h->fcount.reserve(FCH));
+  h->search_stats[ST_REDONE] += nf;
   for (int f0 = 0; f0 < nf; f0 += FCH) {
     const int nfc = (nf - f0 < FCH) ? nf - f0 : FCH;
+    ++h->search_stats[ST_REDO_CHUNKS];
     gather_rows(s, h->fail_list.p + f0, nfc, h->fQ.p);
     hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, s.st, h->fcount.p, nfc, (int)h->N);
     ScanArgs fs = scan_args(redo_of(s, h->fail_list.p + f0, nfc));
@@ -387,6 +395,9 @@ int flat_thresholded(const Search& s) {
   const int64_t streams = (int64_t)2 * bf16_nsplit(nq, sample_tiles, 2);
   const bool sample_top = two_prec && (int64_t)rank * 4 <= streams * SAMPLE_T;
   const int64_t cap_s = sample_top ? streams * SAMPLE_T : S;
+  ++h->search_stats[!two_prec ? ST_FLAT_F32 : (k <= 2048 ? ST_FLAT_FUSED : ST_FLAT_UNFUSED)];
+  if (sample_top) ++h->search_stats[ST_SAMPLE_TOP];
+  h->search_stats[ST_THR_QUERIES] += nq;
 
   // ---- sample: a strided share of the corpus, dense (the register top-T sample writes every stream slot, empty streams as key 0)
   ScanArgs sa = scan_args(s);
@@ -475,6 +486,7 @@ int flat_thresholded(const Search& s) {
 int search_pass(const Search& s) {
   IpIndex* h = s.h;
   const int64_t nq = s.nq;
+  ++h->search_stats[ST_PASSES];
   RCCHK(h->count.reserve(nq * CSTRIDE));
   RCCHK(h->fail_flags.reserve(nq));
   RCCHK(h->fail_list.reserve(nq));
@@ -490,8 +502,10 @@ int search_pass(const Search& s) {
     IvfGeom g;
     RCCHK(ivf_geom(h, &g));
     // small populations or small batches (single requests): the unfiltered pass
-    if (g.cap_full <= 16384 || (double)s.k * 4.0 > (double)g.cap_full / IVF_SS || nq * g.cap_df <= (int64_t)(1 << 23))
+    if (g.cap_full <= 16384 || (double)s.k * 4.0 > (double)g.cap_full / IVF_SS || nq * g.cap_df <= (int64_t)(1 << 23)) {
+      ++h->search_stats[ST_IVF_UNFILTERED];   // (as a first choice: the re-dos count under ST_REDONE)
       return ivf_unfiltered(s, g, nullptr);
+    }
     return ivf_thresholded(s, g);
   }
   if (h->N <= 4 * (int64_t)SAMPLE) return flat_dense(s);
@@ -659,6 +673,14 @@ extern "C" int rihip_ip_index_filtered_stats(void* handle, int64_t* out) {
   IpIndex* h = (IpIndex*)handle;
   RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "ip_index_filtered_stats: bad arguments");
   out[0] = h->filt_stats[0]; out[1] = h->filt_stats[1];
+  return RIHIP_OK;
+}
+
+// What the driver did, cumulative since the handle was made: host counters only (IpIndex::search_stats).
+extern "C" int rihip_ip_index_search_stats(void* handle, int64_t* out) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "ip_index_search_stats: bad arguments");
+  for (int i = 0; i < ST_COUNT; ++i) out[i] = h->search_stats[i];
   return RIHIP_OK;
 }
 

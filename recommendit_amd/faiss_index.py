@@ -387,6 +387,17 @@ class FAISSIndex:
         L.check(L.lib().rihip_ip_index_filtered_stats(self.index._h, out), "ip_index_filtered_stats")
         return int(out[0]), int(out[1])
 
+    SEARCH_STATS = ("flat_dense", "flat_f32", "flat_fused", "flat_unfused", "ivf_unfiltered", "ivf_thresholded",
+                    "sample_top", "prepare_small", "thr_queries", "redone", "redo_chunks", "passes")
+
+    def search_stats(self) -> Dict[str, int]:
+        """What the search driver did since the handle was made (rihip_ip_index_search_stats): internal passes per path,
+        register top-T sample passes, one-launch IVF prepares, queries through a thresholded pass, of those re-done
+        exactly (finish_search's included), re-do chunks, internal passes in all."""
+        out = (C.c_int64 * len(self.SEARCH_STATS))()
+        L.check(L.lib().rihip_ip_index_search_stats(self.index._h, out), "ip_index_search_stats")
+        return {name: int(v) for name, v in zip(self.SEARCH_STATS, out)}
+
     def list_stats(self) -> Dict:
         """IVF list sizes: n_lists, min, max, mean, empty, imbalance = n_lists * sum(len^2) / sum(len)^2 (faiss
         imbalance_factor: 1.0 = even lists); it grows as updates drift away from the trained partition -- the signal

@@ -10,12 +10,18 @@ lists; -1 padding) and the HIP kernels must reproduce it from the SAME centroids
   (iii) Lloyd iterations                vs kmeans_ip            from the same initial centroids
 Float tolerance: exact-f32 fmaf chains vs float64, 2e-6 on unit vectors; a comparison is skipped only where the
 oracle itself shows a margin below 4x that tolerance (coarse probe boundary, k-th score boundary, arg-max margin)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import fixtures as fx
 from oracle import retrieval_np as R
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import search_reference as SR  # noqa: E402  (the driver's path arithmetic, restated)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
@@ -35,6 +41,19 @@ def _clustered(rng, N, d, n_centers, spread=0.35):
     which = rng.choice(n_centers, N, p=w)
     X = centers[which] + spread * rng.randn(N, d).astype(np.float32) / np.sqrt(d)
     return R.normalize_rows(X)
+
+
+def _route(idx, nq, k, nprobe):
+    """the route search_pass takes for one pass of nq queries, from the index's own list sizes"""
+    from recommendit_amd import _lib
+    sizes = np.empty(int(_lib.lib().rihip_ip_index_nlist(idx.index._h)), dtype=np.int64)
+    _lib.check(_lib.lib().rihip_ip_index_list_sizes(idx.index._h, sizes.ctypes.data))
+    return SR.plan(int(sizes.sum()), idx.embed_dim, nq, k, list_lens=sizes, nprobe=nprobe)["route"]
+
+
+def _delta(idx, before):
+    after = idx.search_stats()
+    return {n: after[n] - before[n] for n in after}
 
 
 def _compare_search(idx, Q, X, nprobe, k, min_checked=0.9):
@@ -182,12 +201,20 @@ def test_ivf_search_cfg5_1m_100_lists_nprobe10_k500(clustered):
     X = _clustered(rng, N, d, 64) if clustered else fx.unit_rows(rng, N, d)
     idx = _build(X, nlist, nprobe, kmeans_iters=4)
     Q = np.concatenate([fx.unit_rows(rng, 90, d), X[rng.choice(N, 38, replace=False)]])
+    assert _route(idx, len(Q), k, nprobe) == "ivf_thresholded" and _route(idx, 1, k, nprobe) == "ivf_unfiltered", \
+        "inputs no longer reach the path"
+    before = idx.search_stats()
     sc, rows, o_s, o_r = _compare_search(idx, Q, X, nprobe, k)
+    dl = _delta(idx, before)
+    assert (dl["ivf_thresholded"], dl["ivf_unfiltered"], dl["thr_queries"]) == (1, 0, len(Q)) and dl["redone"] <= len(Q), dl
     assert (rows >= 0).all()
-    # one query at a time == batch (different query blocks / tile lists / thresholds)
+    # one query at a time == batch: a single query takes the other route, the unfiltered pass
+    before = idx.search_stats()
     for q in (0, 64, 127):
         s1, r1 = idx.search(Q[q], k=k)
         assert list(r1) == list(rows[q])
+    dl = _delta(idx, before)
+    assert (dl["ivf_unfiltered"], dl["ivf_thresholded"], dl["prepare_small"]) == (3, 0, 3), dl
 
 
 def test_ivf_underfill_not_masked_by_list_padding():
@@ -200,7 +227,8 @@ def test_ivf_underfill_not_masked_by_list_padding():
     m = fx.unit_rows(rng, 1, d)
     C = R.normalize_rows(m + fx.unit_rows(rng, nlist, d))     # every centroid inside a cone around m
     per = 64 * 60 + 1                                          # 3841 rows per list -> 63 padding rows each; large
-    # enough (10 x 3904 probed rows) for the sampled-threshold scan, where a zero-score padding row passes thr <= 0
+    # enough (10 x 3904 probed rows) for the sampled-threshold scan, where a zero-score padding row passes thr <= 0 --
+    # in a batch of 224 or more queries (nq * 39 040 dense slots > 2^23); the 8 queries alone are the unfiltered pass
     X = np.concatenate([R.normalize_rows(C[c] + 0.3 * rng.randn(per, d).astype(np.float32) / np.sqrt(d))
                         for c in range(nlist)])
     a = np.repeat(np.arange(nlist), per).astype(np.int32)
@@ -208,8 +236,20 @@ def test_ivf_underfill_not_masked_by_list_padding():
     idx = FAISSIndex(embed_dim=d, n_lists=nlist, n_probe=nprobe)
     idx.build_from_device(torch.from_numpy(X).cuda(), np.arange(len(X)), centroids=C, assign=a)
     Q = R.normalize_rows(-m + 0.2 * fx.unit_rows(rng, 8, d))   # negative scores against every list
+    assert _route(idx, 8, k, nprobe) == "ivf_unfiltered" and _route(idx, 224, k, nprobe) == "ivf_thresholded", \
+        "inputs no longer reach the path"
+    before = idx.search_stats()
     sc, rows, o_s, o_r = _compare_search(idx, Q, X, nprobe, k, min_checked=0.5)
+    dl = _delta(idx, before)
+    assert (dl["ivf_unfiltered"], dl["ivf_thresholded"]) == (1, 0), dl
     assert (rows >= 0).all() and (sc < 0).all()
+    # the same queries 28 times over: the thresholded pass, the same answers
+    before = idx.search_stats()
+    sb, rb = idx.batch_search(np.tile(Q, (28, 1)), k=k)
+    dl = _delta(idx, before)
+    assert (dl["ivf_thresholded"], dl["ivf_unfiltered"], dl["thr_queries"]) == (1, 0, 224), dl
+    np.testing.assert_array_equal(rb, np.tile(rows, (28, 1)))
+    np.testing.assert_allclose(sb, np.tile(sc, (28, 1)), atol=TOL, rtol=0)
 
 
 def test_faiss_file_interop(tmp_path):
@@ -322,8 +362,9 @@ def test_rank_topk_large_candidate_sets_and_nan_scores():
 def test_deferred_exactness_check_equals_the_synchronous_search():
     """Serving chains defer the thresholded IVF pass's exactness check to their end (`set_deferred_check` /
     `finish_search`): the deferred search + finish must give what the synchronous search gives, including for queries
-    that take the exact re-do (here: 6 000 identical rows tie at the threshold and overflow the candidate lists)."""
-    from recommendit_amd import FAISSIndex
+    that take the exact re-do (here: 6 000 identical rows tie at the threshold and overflow the candidate lists).  The
+    route is asserted from the index's own list sizes, the re-dos from search_stats."""
+    from recommendit_amd import FAISSIndex, _lib
     rng = np.random.RandomState(5)
     N, d, nq, k = 300_000, 128, 600, 500
     X = fx.unit_rows(rng, N, d)
@@ -334,13 +375,26 @@ def test_deferred_exactness_check_equals_the_synchronous_search():
     idx = FAISSIndex(embed_dim=d, n_lists=100, n_probe=10)
     idx.build_from_device(torch.from_numpy(X).cuda(), np.arange(N))
     q = torch.from_numpy(Q).cuda()
+    sizes = np.empty(100, dtype=np.int64)
+    _lib.check(_lib.lib().rihip_ip_index_list_sizes(idx.index._h, sizes.ctypes.data))
+    assert SR.plan(N, d, nq, k, list_lens=sizes, nprobe=10)["route"] == "ivf_thresholded", "inputs no longer reach the path"
+    st0 = idx.search_stats()
     s0, r0 = idx.batch_search_device(q, k=k, normalized=True)            # synchronous check + re-do inside
+    torch.cuda.synchronize()
+    st1 = idx.search_stats()
+    assert st1["ivf_thresholded"] - st0["ivf_thresholded"] == 1 and st1["ivf_unfiltered"] == st0["ivf_unfiltered"]
+    assert st1["thr_queries"] - st0["thr_queries"] == nq
+    redone_sync = st1["redone"] - st0["redone"]
+    assert 40 <= redone_sync <= nq and st1["redo_chunks"] - st0["redo_chunks"] == -(-redone_sync // 64)
     idx.set_deferred_check(True)
     s1, r1 = idx.batch_search_device(q, k=k, normalized=True)
     assert idx.search_pending()
+    assert idx.search_stats()["redone"] == st1["redone"]                  # nothing re-done before the finish
     n = idx.finish_search()
     idx.set_deferred_check(False)
+    st2 = idx.search_stats()
     assert n >= 40, n                                                     # the tied queries were re-done
+    assert st2["redone"] - st1["redone"] == n == redone_sync and st2["ivf_thresholded"] - st1["ivf_thresholded"] == 1
     assert not idx.search_pending()
     torch.testing.assert_close(r1, r0, rtol=0, atol=0)
     torch.testing.assert_close(s1, s0, rtol=0, atol=0)

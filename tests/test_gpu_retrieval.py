@@ -4,6 +4,8 @@ tests for the FAISSIndex wrapper (tests/test_models.py:151-246 of the reference)
 Float scores: |score - oracle| <= 2e-6 (unit vectors, exact-f32 fmaf chain vs float64).  Row sets:
 bit-exact whenever the oracle's k-th/(k+1)-th gap exceeds that tolerance; near-ties are checked
 through the score of the returned row instead.  Integer-valued inputs: bit-exact incl. tie-break."""
+import os
+import sys
 import tempfile
 from pathlib import Path
 
@@ -13,6 +15,9 @@ import torch
 
 from oracle import fixtures as fx
 from oracle import retrieval_np as R
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import search_reference as SR  # noqa: E402  (the driver's path arithmetic, restated)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
@@ -68,14 +73,27 @@ def test_integer_inputs_bit_exact_with_ties():
     np.testing.assert_array_equal(rows.cpu().numpy(), ref_rows)
 
 
+def _stats_delta(idx, before):
+    after = idx.search_stats()
+    return {n: after[n] - before[n] for n in after}
+
+
 def test_all_identical_rows_take_the_exact_fallback():
+    """70 000 identical rows: every score of a query ties, the candidate list of the thresholded two-precision pass
+    overflows for all 11 queries and flat_redo takes them in chunks of 8 and 3"""
     N, d, k = 70000, 32, 50
+    assert SR.plan(N, d, 11, k)["route"] == "flat_fused" and SR.redo_chunks(11, False) == [8, 3], \
+        "inputs no longer reach the path"
     X = np.tile(fx.unit_rows(np.random.RandomState(0), 1, d), (N, 1))
     Q = fx.unit_rows(np.random.RandomState(1), 11, d)
     from recommendit_amd import FAISSIndex
     idx = FAISSIndex(embed_dim=d, exact=True)
     idx.build_from_device(torch.from_numpy(X).cuda(), np.arange(N))
+    before = idx.search_stats()
     sc, rows = idx._search_device(torch.from_numpy(Q).cuda(), k)
+    torch.cuda.synchronize()
+    delta = _stats_delta(idx, before)
+    assert (delta["flat_fused"], delta["thr_queries"], delta["redone"], delta["redo_chunks"]) == (1, 11, 11, 2), delta
     np.testing.assert_array_equal(rows.cpu().numpy(), np.tile(np.arange(k), (11, 1)))
     assert (sc.cpu().numpy() == sc.cpu().numpy()[:, :1]).all()
 
@@ -214,9 +232,17 @@ def test_two_precision_search_equals_all_f32():
     Q[:5] = X[:5]                                  # exact self-matches (score 1.0 on the boundary of the range)
     idx = FAISSIndex(embed_dim=d, exact=True)
     idx.build_ivf_index(X, list(range(N)))
+    assert SR.plan(N, d, nq, k)["route"] == "flat_fused" and SR.plan(N, d, nq, k, two_precision=False)["route"] == "flat_f32", \
+        "inputs no longer reach the path"
+    before = idx.search_stats()
     s2, r2 = idx.batch_search(Q, k=k)              # default: two-precision
+    delta = _stats_delta(idx, before)
+    assert (delta["flat_fused"], delta["flat_f32"], delta["thr_queries"]) == (1, 0, nq), delta
     _lib.check(_lib.lib().rihip_ip_index_set_two_precision(idx.index._h, 0))
+    before = idx.search_stats()
     s1, r1 = idx.batch_search(Q, k=k)              # all-f32
+    delta = _stats_delta(idx, before)
+    assert (delta["flat_fused"], delta["flat_f32"], delta["thr_queries"]) == (0, 1, nq), delta
     _check_topk(s2, r2, Q, X, k)
     np.testing.assert_allclose(s2, s1, atol=1e-6, rtol=0)
     same = (r1 == r2).mean()
@@ -243,10 +269,19 @@ def test_two_precision_large_k_unfused_rescore(d, k):
     X, Q = fx.unit_rows(rng, N, d), fx.unit_rows(rng, nq, d)
     idx = FAISSIndex(embed_dim=d, exact=True)
     idx.build_ivf_index(X, list(range(N)))
+    p = SR.plan(N, d, nq, k)
+    assert p["route"] == "flat_unfused" and p["sample_top"] is (k == 2049), "inputs no longer reach the path"
+    before = idx.search_stats()
     s2, r2 = idx.batch_search(Q, k=k)              # default: two-precision
+    after = idx.search_stats()
+    assert after["flat_unfused"] - before["flat_unfused"] == 1 and after["passes"] - before["passes"] == 1
+    assert after["sample_top"] - before["sample_top"] == int(k == 2049)
+    assert after["thr_queries"] - before["thr_queries"] == nq
     _check_topk(s2, r2, Q, X, k)
     _lib.check(_lib.lib().rihip_ip_index_set_two_precision(idx.index._h, 0))
+    assert SR.plan(N, d, nq, k, two_precision=False)["route"] == "flat_f32", "inputs no longer reach the path"
     s1, r1 = idx.batch_search(Q, k=k)              # all-f32
+    assert idx.search_stats()["flat_f32"] - after["flat_f32"] == 1
     np.testing.assert_allclose(s2, s1, atol=1e-6, rtol=0)
     for q in range(nq):
         assert set(r1[q]) == set(r2[q]) or np.abs(s1[q, -1] - s1[q, -2]) < 1e-6, q
@@ -286,8 +321,15 @@ def test_two_precision_scratch_reuse_across_batch_sizes():
     X = fx.unit_rows(rng, N, d)
     idx = _index(X)
     Qa, Qb = fx.unit_rows(rng, 1500, d), fx.unit_rows(rng, 200, d)
+    pa, pb = SR.plan(N, d, 1500, k), SR.plan(N, d, 200, k)
+    assert pa["route"] == pb["route"] == "flat_fused", "inputs no longer reach the path"
+    assert pa["filter"]["nsplit"] == 128 and pb["filter"]["nsplit"] == 768, "inputs no longer reach the path"
+    assert pb["filter"]["nsplit"] - pb["filter"]["used"] == 116, "inputs no longer reach the path"
+    before = idx.search_stats()
     idx.batch_search(Qa, k=k)                      # 6 query blocks -> 128 splits
     s, r = idx.batch_search(Qb, k=k)               # 1 query block  -> 768 splits, 116 of them empty
+    delta = _stats_delta(idx, before)
+    assert (delta["flat_fused"], delta["passes"], delta["thr_queries"]) == (2, 2, 1700), delta
     sel = rng.choice(200, 24, replace=False)
     _check_topk(s[sel], r[sel] - 1000, Qb[sel], X, k)
     s2, r2 = idx.batch_search(Qb, k=k)
@@ -312,23 +354,43 @@ def test_two_precision_dense_survivors_queue_overflow():
 def test_ivf_large_lists_thresholded_path():
     """Lists large enough for the sampled-threshold IVF scan: with nprobe == nlist the result must be the exact
     top-k; with nprobe < nlist every returned (score,row) is a true inner product, sorted, k of them, and the
-    batch result equals the one-query-at-a-time result (different blocks / tile lists / thresholds)."""
-    from recommendit_amd import FAISSIndex
+    batch result equals the one-query-at-a-time result, which takes the other route: a single query is always the
+    unfiltered pass.  At nprobe = 5 the 150 queries alone hold too few dense slots for the thresholded pass
+    (150 * 5 * ~9 000 < 2^23), so they are searched as a batch of 300 (the queries twice: 300 * 5 * 6 016 > 2^23 for
+    any partition); the routes are asserted from the index's own list sizes."""
+    from recommendit_amd import FAISSIndex, _lib
+    miss = "inputs no longer reach the path"
     rng = np.random.RandomState(21)
     N, d, nq, k = 300000, 64, 150, 100
     X, Q = fx.unit_rows(rng, N, d), fx.unit_rows(rng, nq, d)
     ivf = FAISSIndex(embed_dim=d, n_lists=50, n_probe=50)
     ivf.build_ivf_index(X, list(range(N)), kmeans_iters=5)
+    sizes = np.empty(50, dtype=np.int64)
+    _lib.check(_lib.lib().rihip_ip_index_list_sizes(ivf.index._h, sizes.ctypes.data))
+    assert SR.plan(N, d, nq, k, list_lens=sizes, nprobe=50)["route"] == "ivf_thresholded", miss
+    before = ivf.search_stats()
     sc, rows = ivf.batch_search(Q, k=k)
+    delta = _stats_delta(ivf, before)
+    assert (delta["ivf_thresholded"], delta["ivf_unfiltered"], delta["thr_queries"]) == (1, 0, nq), delta
     _check_topk(sc, rows, Q, X, k)
     ivf.set_n_probe(5)
-    sc5, rows5 = ivf.batch_search(Q, k=k)
+    assert SR.plan(N, d, 2 * nq, k, list_lens=sizes, nprobe=5)["route"] == "ivf_thresholded", miss
+    assert SR.plan(N, d, 1, k, list_lens=sizes, nprobe=5)["route"] == "ivf_unfiltered", miss
+    before = ivf.search_stats()
+    sc10, rows10 = ivf.batch_search(np.concatenate([Q, Q]), k=k)
+    delta = _stats_delta(ivf, before)
+    assert (delta["ivf_thresholded"], delta["ivf_unfiltered"], delta["thr_queries"]) == (1, 0, 2 * nq), delta
+    assert np.array_equal(rows10[:nq], rows10[nq:]) and np.array_equal(sc10[:nq], sc10[nq:])
+    sc5, rows5 = sc10[:nq], rows10[:nq]
     assert (rows5 >= 0).all() and (np.diff(sc5, axis=1) <= 0).all()
     S = Q.astype(np.float64) @ X.astype(np.float64).T
     np.testing.assert_allclose(sc5, np.take_along_axis(S, rows5, 1), atol=TOL)
+    before = ivf.search_stats()
     for q in (0, 7, 149):
         s1, r1 = ivf.search(Q[q], k=k)
         assert list(r1) == list(rows5[q])
+    delta = _stats_delta(ivf, before)
+    assert (delta["ivf_unfiltered"], delta["ivf_thresholded"], delta["prepare_small"]) == (3, 0, 3), delta
     ref_sc, ref_rows = R.topk_ip_exact(Q, X, k)
     recall = np.mean([len(set(rows5[q]) & set(ref_rows[q])) / k for q in range(nq)])
     assert recall > 0.3, recall
@@ -351,7 +413,12 @@ def test_ivf_thresholded_path_at_d32():
     assert cap_full > 16384
     assert 4 * k <= cap_full / 16
     assert nq * cap_df > 2 ** 23
+    assert SR.plan(N, d, nq, k, list_lens=sizes, nprobe=nprobe)["route"] == "ivf_thresholded", "inputs no longer reach the path"
+    before = ivf.search_stats()
     sc, rows = ivf.batch_search(Q, k=k)
+    after = ivf.search_stats()
+    assert after["ivf_thresholded"] - before["ivf_thresholded"] == 1 and after["ivf_unfiltered"] == before["ivf_unfiltered"]
+    assert after["thr_queries"] - before["thr_queries"] == nq and after["redone"] - before["redone"] <= nq
     _check_topk(sc, rows, Q, X, k)
 
 
