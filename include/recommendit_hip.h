@@ -630,6 +630,53 @@ int rihip_sq8_index_stats(void* handle, int64_t* out);
 int rihip_sq8_index_save(void* handle, const char* path);          /* host path; synchronous */
 int rihip_sq8_index_load(const char* path, void** handle);         /* host path; synchronous */
 
+/* ---- SQ8 index: exact f32 re-ranking of the 8-bit candidates, with a per-query certificate (faiss has the first half as
+ * IndexRefineFlat).  Opt-in: without attached vectors every call above returns what it returned before.  The calls take
+ * an sq8_index handle; they carry a prefix of their own, rihip_sq8_refine_*, so the rihip_sq8_index_* family stays the set it was.
+ * attach_vectors: copies the f32 rows of a built ip_index into the handle, in insertion-row order [N, dk] (the source may
+ * be destroyed afterwards).  The source must hold the handle's rows in the handle's order: same N, width, list count and
+ * list lengths, and the same row of every physical slot (compared on the device); anything else, an index updated since
+ * the encode included, is RIHIP_ERR_STATE and leaves the handle as it was.  The call also computes, in f64 over the
+ * stored rows and the STORED codes c_ij (so a clamped code of an injected quantiser counts with its full error),
+ *   e_j = max_i | x_ij - (m_j + s_j * c_ij) |      (s_j * c_ij exact; one rounding in the sum, one in the difference)
+ *   a_j = max_i | x_ij |
+ * without atomics.  get_ranges: host f64 [d] each, synchronous.  drop_vectors / has_vectors: as named.  stats out[2]
+ * counts the vectors; save / load do not carry them: a loaded index has none until they are attached again.
+ *
+ * search, k <= k_scan <= rihip_ip_index_max_k():
+ *   Stage 1: rihip_sq8_index_search at k_scan in `mode`: the top k_scan of the probed rows by (S descending, row ascending).
+ *   Stage 2: every valid stage-1 candidate is re-scored as f(q, x_row) in f32 and the top k by (f + 0.f descending, row
+ *   ascending) is written: scores f32 [nq,k] (-inf pad), rows i64 [nq,k] (-1 pad where stage 1 held fewer than k rows;
+ *   set_id_map applied after the select).  No host synchronisation beyond stage 1's.
+ *   f(q, x), one fixed function of the two rows zero-padded to dk = 32 / 64 / 128 columns -- not of the batch, k, k_scan, the
+ *   candidate's position or mode:  P = dk / 16;  for l = 0 .. 15:  s_l = 0.f, then for j = l*P .. l*P + P-1 ascending
+ *   s_l = fmaf(q_j, x_j, s_l);  then for o = 8, 4, 2, 1:  s_l = s_l + s_(l xor o)  for all l at once;  f = s_0.
+ *   Certificate: out_cert u8 [nq], out_bound f64 [nq] or NULL, all f64 on the device, sums in ascending j over j < d:
+ *     E1 = sum_j |q_j| * e_j          the codes' error
+ *     E2 = 127 * sum_j | q_j * s_j - t * n_j |     the query's 16-bit rounding (both products exact in f64), |c_ij| <= 127
+ *     A  = sum_j |q_j| * a_j,   E3 = g * A,   g = u / (1 - u),  u = dk * 2^-24      f's own rounding: at most dk roundings on
+ *                                                                                   any path from a product to f
+ *     M  = sum_j |q_j * m_j|,   W = 127 * sum_j |t * n_j|       (magnitudes of b and of any t * S)
+ *     slack = 2^-44 * ((((M + W) + A) + E1) + E2) + dk * 2^-126
+ *     bound = ((E1 + E2) + E3) + slack
+ *   slack: b is a sum of d exact products (relative error below 128 * 2^-53 of M); t * S rounds once (2^-53 W); each of
+ *   the sums has at most 128 additions and three roundings per term (below 132 * 2^-53 relative); e_j carries two
+ *   roundings, at most 2^-52 (a_j + e_j), i.e. 2^-52 (A + E1) in E1; U below adds three times (4 * 2^-53 of its terms).
+ *   Together below 300 * 2^-53 of (M + W + A + E1 + E2); 2^-44 = 512 * 2^-53.  dk * 2^-126 covers f32 underflow in f.
+ *   With S_cut the smallest integer score among the stage-1 candidates and U = (b + t * S_cut) + bound:
+ *     cert = 1  iff  stage 1 returned fewer than k_scan valid rows (every probed row was re-scored)
+ *                    or the k-th refined score > U.
+ *   cert = 1 implies: the output equals the top k by (f, row) over ALL rows of the probed lists.  A probed row outside the
+ *   candidates has S <= S_cut, so its real inner product is at most b + t * S_cut + E1 + E2 (its decoded row is within e of
+ *   it, and the integer score is within E2 / t of the decoded row's product with q) and its f at most that plus E3; it is
+ *   below the k-th refined score, and the k best candidates are k rows with a larger f.  bound does not depend on stage 1. */
+int rihip_sq8_refine_attach_vectors(void* handle, void* ip_handle, void* stream);   /* synchronous */
+int rihip_sq8_refine_drop_vectors(void* handle);                                    /* synchronous */
+int rihip_sq8_refine_has_vectors(void* handle);
+int rihip_sq8_refine_get_ranges(void* handle, double* e, double* a);         /* synchronous */
+int rihip_sq8_refine_search(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode, float* out_scores,
+                                   int64_t* out_rows, uint8_t* out_cert, double* out_bound, void* stream);
+
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict
  * (ranker.py:174): raw score = sum over trees of the reached leaf value, float64.

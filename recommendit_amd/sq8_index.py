@@ -8,12 +8,18 @@ not faiss's QT_8bit and faiss SQ files are not read or written. 
 dtypes and -1 padding; scores are (float)(b + t * S) of the integer score S, i.e. the inner product of the query with
 the DECODED vectors up to the query's own 16-bit rounding.
 
+Refined search (opt-in): with the source's f32 vectors attached (``keep_vectors=True`` / ``attach_vectors``) a search
+may re-score the 8-bit search's best ``k_scan = ceil(factor * k)`` candidates exactly in f32 and return the top k of
+those, with a per-query certificate that the list is the exact top k of the probed lists (``refine=``,
+``return_cert=``, ``set_refine``, ``search_certified``; rihip_sq8_refine_search in recommendit_hip.h).
+
 There is no NumPy or torch path for encode or search: everything runs in csrc/sq8.hip.
 """
 from __future__ import annotations
 
 import ctypes as C
 import logging
+import math
 import pickle
 from pathlib import Path
 from typing import Dict, Optional, Tuple
@@ -27,6 +33,7 @@ from .faiss_index import FAISSIndex
 logger = logging.getLogger(__name__)
 
 MODES = {"auto": 0, "dense": 1, "thresholded": 2}
+_DEFAULT = object()   # refine=: "the index's sticky factor (set_refine)"
 
 
 class _SQ8Handle:
@@ -62,6 +69,18 @@ class _SQ8Handle:
             pass
 
 
+def _factor(refine) -> Optional[float]:
+    """a refine factor as given by a caller -> None (plain search) or a finite float >= 1"""
+    if refine is None:
+        return None
+    if isinstance(refine, bool) or not isinstance(refine, (int, float, np.integer, np.floating)):
+        raise ValueError(f"SQ8Index: refine={refine!r} must be None or a number >= 1")
+    f = float(refine)
+    if not math.isfinite(f) or f < 1.0:
+        raise ValueError(f"SQ8Index: refine={refine!r} must be finite and at least 1")
+    return f
+
+
 def _mode(mode) -> int:
     if mode not in MODES:
         raise ValueError(f"SQ8Index: unknown search mode {mode!r} (one of {sorted(MODES)})")
@@ -80,12 +99,15 @@ class SQ8Index:
         self.item_ids: Optional[np.ndarray] = None
         self._item_id_to_faiss_idx: Dict[int, int] = {}
         self._item_ids_dev: Optional[torch.Tensor] = None
+        self._refine: Optional[float] = None
 
     # -- build ----------------------------------------------------------------------------------------------------
     @classmethod
-    def from_index(cls, faiss_index: FAISSIndex, ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> "SQ8Index":
+    def from_index(cls, faiss_index: FAISSIndex, ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None,
+                   keep_vectors: bool = False) -> "SQ8Index":
         """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  ranges: (centre,
-        scale), two f32 [embed_dim] arrays that replace the trained per-dimension quantiser; scale > 0."""
+        scale), two f32 [embed_dim] arrays that replace the trained per-dimension quantiser; scale > 0.
+        keep_vectors=True also copies the f32 vectors (attach_vectors), which a refined search needs."""
         if not isinstance(faiss_index, FAISSIndex):
             raise ValueError(f"SQ8Index.from_index needs a FAISSIndex, got {type(faiss_index).__name__}")
         if faiss_index.index is None:
@@ -115,7 +137,50 @@ class SQ8Index:
         obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())
         obj._item_id_to_faiss_idx = dict(faiss_index._item_id_to_faiss_idx)
         logger.info("SQ8 index built: %d vectors, %d lists, probe=%d", obj.index.ntotal, obj.index.nlist, obj.n_probe)
+        if keep_vectors:
+            obj.attach_vectors(faiss_index)
         return obj
+
+    # -- refined search: the f32 vectors next to the codes ------------------------------------------------------------
+    def attach_vectors(self, faiss_index: FAISSIndex) -> None:
+        """Copy the f32 vectors of the FAISSIndex this index was encoded from (it may be dropped afterwards).  An index
+        with other rows, another row order or other lists -- one updated since the encode included -- is refused
+        (RuntimeError) and leaves this index as it was."""
+        h = self._built()
+        if not isinstance(faiss_index, FAISSIndex):
+            raise ValueError(f"SQ8Index.attach_vectors needs a FAISSIndex, got {type(faiss_index).__name__}")
+        if faiss_index.index is None:
+            raise RuntimeError("Index not built.")
+        if faiss_index.search_pending():
+            raise RuntimeError("a deferred search is pending: call finish_search() before attaching the index")
+        L.check(L.lib().rihip_sq8_refine_attach_vectors(h._h, faiss_index.index._h, L.stream_ptr()), "sq8_refine_attach_vectors")
+
+    def drop_vectors(self) -> None:
+        L.check(L.lib().rihip_sq8_refine_drop_vectors(self._built()._h), "sq8_refine_drop_vectors")
+
+    @property
+    def has_vectors(self) -> bool:
+        return self.index is not None and bool(L.lib().rihip_sq8_refine_has_vectors(self.index._h))
+
+    def set_refine(self, factor: Optional[float]) -> None:
+        """The refine factor of every search that does not name one (None: plain 8-bit search, the default).  Sticky, so
+        a serve chain that calls batch_search_device(q, k, normalized=True) gets refined candidates and their f32
+        scores."""
+        f = _factor(factor)
+        if f is not None and not self.has_vectors:
+            raise RuntimeError("SQ8Index.set_refine: no vectors attached (from_index(keep_vectors=True) or attach_vectors)")
+        self._refine = f
+
+    def refine_ranges(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(e, a): f64 [embed_dim] each -- the largest decode error and the largest magnitude of every column"""
+        h = self._built()
+        e = np.empty(self.embed_dim, dtype=np.float64)
+        a = np.empty(self.embed_dim, dtype=np.float64)
+        L.check(L.lib().rihip_sq8_refine_get_ranges(h._h, e.ctypes.data, a.ctypes.data), "sq8_refine_get_ranges")
+        return e, a
+
+    def _k_scan(self, k: int, factor: float) -> int:
+        return min(max(k, int(math.ceil(factor * k))), int(L.lib().rihip_ip_index_max_k()))
 
     def _built(self) -> _SQ8Handle:
         if self.index is None:
@@ -167,13 +232,40 @@ class SQ8Index:
             raise ValueError("SQ8Index: no queries")
         return queries.to(device=L.device(), dtype=torch.float32).contiguous()
 
-    def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool, mode: int, return_int: bool):
+    def _refined_device(self, q_dev: torch.Tensor, k: int, k_scan: int, item_ids: bool, mode: int):
+        """(scores f32 [nq, k], rows or ids i64 [nq, k], cert u8 [nq], bound f64 [nq]) of one refined search"""
         h = self._built()
         lib = L.lib()
+        if not self.has_vectors:
+            raise RuntimeError("SQ8Index: refine needs the f32 vectors (from_index(keep_vectors=True) or attach_vectors)")
+        nq = q_dev.shape[0]
+        L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr() if item_ids else None),
+                "sq8_index_set_id_map")
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=q_dev.device)
+        cert = torch.empty((nq,), dtype=torch.uint8, device=q_dev.device)
+        bound = torch.empty((nq,), dtype=torch.float64, device=q_dev.device)
+        L.check(lib.rihip_sq8_refine_search(h._h, q_dev.data_ptr(), nq, k, k_scan, mode, scores.data_ptr(),
+                                                   rows.data_ptr(), cert.data_ptr(), bound.data_ptr(), L.stream_ptr()),
+                "sq8_refine_search")
+        return scores, rows, cert, bound
+
+    def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool, mode: int, return_int: bool, refine=_DEFAULT,
+                       return_cert: bool = False):
+        h = self._built()
+        lib = L.lib()
+        factor = self._refine if refine is _DEFAULT else _factor(refine)
         if k < 1:
             raise ValueError(f"SQ8Index: k={k} must be at least 1")
         if k > int(lib.rihip_ip_index_max_k()):
             raise ValueError(f"k={k} exceeds the device select buffer ({int(lib.rihip_ip_index_max_k())})")
+        if factor is not None:
+            if return_int:
+                raise ValueError("SQ8Index: return_int gives the 8-bit search's integer scores; a refined search has none")
+            out = self._refined_device(q_dev, k, self._k_scan(k, factor), item_ids, mode)
+            return out if return_cert else out[:2]
+        if return_cert:
+            raise ValueError("SQ8Index: return_cert needs a refined search (refine= or set_refine)")
         nq = q_dev.shape[0]
         L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr() if item_ids else None),
                 "sq8_index_set_id_map")
@@ -184,7 +276,7 @@ class SQ8Index:
                                            L.ptr(ints), L.stream_ptr()), "sq8_index_search")
         return (scores, rows, ints) if return_int else (scores, rows)
 
-    def search(self, query_vector: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, query_vector: np.ndarray, k: int = 500, refine=_DEFAULT) -> Tuple[np.ndarray, np.ndarray]:
         h = self._built()
         query = np.atleast_2d(query_vector).astype(np.float32)
         if query.shape[1] != self.embed_dim:
@@ -192,12 +284,13 @@ class SQ8Index:
         query = query / np.maximum(np.linalg.norm(query, axis=1, keepdims=True), 1e-8)
         k = min(k, h.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(query[:1])).to(L.device())
-        scores, rows = self._search_device(q_dev, k, False, 0, False)
+        scores, rows = self._search_device(q_dev, k, False, 0, False, refine)
         distances, idx = scores[0].cpu().numpy(), rows[0].cpu().numpy()
         valid = idx >= 0
         return distances[valid], self.item_ids[idx[valid]]
 
-    def batch_search(self, query_vectors: np.ndarray, k: int = 500) -> Tuple[np.ndarray, np.ndarray]:
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500, refine=_DEFAULT, return_cert: bool = False):
+        """(scores, item ids) as NumPy arrays; return_cert=True appends (cert u8 [nq], bound f64 [nq])"""
         h = self._built()
         queries = np.asarray(query_vectors).astype(np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.embed_dim:
@@ -205,25 +298,57 @@ class SQ8Index:
         queries = queries / np.maximum(np.linalg.norm(queries, axis=1, keepdims=True), 1e-8)
         k = min(k, h.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
-        scores, ids = self._search_device(self._queries(q_dev), k, True, 0, False)
-        return scores.cpu().numpy(), ids.cpu().numpy()
+        out = self._search_device(self._queries(q_dev), k, True, 0, False, refine, return_cert)
+        return tuple(t.cpu().numpy() for t in out)
 
     def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, mode: str = "auto",
-                            return_int: bool = False):
+                            return_int: bool = False, refine=_DEFAULT, return_cert: bool = False):
         """queries f32 [nq, embed_dim] on the device -> (scores f32, item ids i64) [nq, k] on the device, -1 padded;
         return_int=True appends the integer scores i32 [nq, k].  mode: "auto", "dense" or "thresholded" (the same bytes
-        from each; "thresholded" synchronises the stream for its completeness check)."""
+        from each; "thresholded" synchronises the stream for its completeness check).
+
+        refine: a factor >= 1 re-scores the best k_scan = min(max(k, ceil(factor * k)), max_k) candidates of the 8-bit
+        search exactly in f32 and returns the top k of those with their f32 scores; None is the plain search; left
+        out, the factor of set_refine.  return_cert=True appends (cert u8 [nq], bound f64 [nq]): cert = 1 proves the
+        list is the exact top k of the probed lists."""
         h = self._built()
         m = _mode(mode)
         q = self._queries(queries)
         if not normalized:
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
-        return self._search_device(q, min(k, h.ntotal), True, m, return_int)
+        return self._search_device(q, min(k, h.ntotal), True, m, return_int, refine, return_cert)
 
-    def search_rows_device(self, queries: torch.Tensor, k: int, mode: str = "auto", return_int: bool = False):
+    def search_rows_device(self, queries: torch.Tensor, k: int, mode: str = "auto", return_int: bool = False, refine=_DEFAULT,
+                           return_cert: bool = False):
         """batch_search_device on queries taken as they are, returning ROWS (insertion order) instead of item ids and k
         as given (padded beyond ntotal)"""
-        return self._search_device(self._queries(queries), k, False, _mode(mode), return_int)
+        return self._search_device(self._queries(queries), k, False, _mode(mode), return_int, refine, return_cert)
+
+    def search_certified(self, queries: torch.Tensor, k: int = 500, start: float = 2.0, normalized: bool = False):
+        """Refine at factor `start`, then repeat only the queries without a certificate with k_scan doubled until they
+        have one or k_scan reaches the select buffer's size.  -> (scores f32 [nq, k], item ids i64 [nq, k], cert u8 [nq])
+        on the device; a query whose flag is still 0 is reported as it is, not repaired."""
+        h = self._built()
+        f = _factor(start)
+        if f is None:
+            raise ValueError("SQ8Index.search_certified: start must be a number >= 1")
+        q = self._queries(queries)
+        if not normalized:
+            q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
+        max_k = int(L.lib().rihip_ip_index_max_k())
+        k = min(k, h.ntotal)
+        if k < 1 or k > max_k:
+            raise ValueError(f"SQ8Index: k={k} outside 1..{max_k}")
+        k_scan = self._k_scan(k, f)
+        scores, ids, cert, _ = self._refined_device(q, k, k_scan, True, 0)
+        while k_scan < max_k:
+            todo = torch.nonzero(cert == 0).flatten()
+            if todo.numel() == 0:
+                break
+            k_scan = min(2 * k_scan, max_k)
+            s2, i2, c2, _ = self._refined_device(q[todo].contiguous(), k, k_scan, True, 0)
+            scores[todo], ids[todo], cert[todo] = s2, i2, c2
+        return scores, ids, cert
 
     # -- the calls a serve chain makes on its index; an SQ8 search has no pending state -------------------------------
     def set_deferred_check(self, enable: bool) -> None:
@@ -304,6 +429,8 @@ class SQ8Index:
             "device_bytes": int(out[2]),
             "queries_thresholded": int(out[0]),
             "queries_redone": int(out[1]),
+            "has_vectors": self.has_vectors,
+            "refine": self._refine,
         }
 
     def set_n_probe(self, n_probe: int) -> None:
