@@ -630,6 +630,34 @@ int rihip_sq8_index_stats(void* handle, int64_t* out);
 int rihip_sq8_index_save(void* handle, const char* path);          /* host path; synchronous */
 int rihip_sq8_index_load(const char* path, void** handle);         /* host path; synchronous */
 
+/* ---- SQ8 index: tag filters inside the int8 scan.  Opt-in: without tags every call above returns what it returned
+ * before.  The calls take an sq8_index handle and carry a prefix of their own, rihip_sq8_filter_*, as the refined search's do.
+ * Filtered search (the ip_index's predicate, word for word): every stored row carries one 32-bit tag word, a query carries
+ * (any_of, all_of, none_of), and row r passes iff
+ *   (any_of == 0 || (tag[r] & any_of) != 0) && (tag[r] & all_of) == all_of && (tag[r] & none_of) == 0.
+ * A filtered search returns the exact top k by (S descending, row ascending) of the PASSING rows of the probed lists:
+ * probing does not look at tags, ties go to the lower row, padding is -inf / -1 / INT32_MIN, the reported score is the
+ * plain search's (float)(b + t * S), and the predicate (0,0,0) returns rihip_sq8_index_search's bytes in every mode.  A
+ * failing row is simply absent from the scan's output: it enters neither the threshold sample nor the survivor list nor
+ * a dense slot (its slot holds the empty key 0).  So the thresholded pass keeps its integer completeness argument
+ * unchanged under any pass rate, with "row" read as "passing row": the threshold is the rank-th best passing sampled
+ * score; a sample with fewer than rank passing rows gives no threshold (INT_MIN: every passing probed row is a
+ * candidate, as the plain search does for a short sample); a query that overflows its candidate slots, or holds fewer
+ * than k candidates under a real threshold (one with fewer than k passing rows included), is re-done dense with its
+ * predicate applied.  No passing rows are counted beforehand.
+ * set_tags: device uint32 [ntotal] in insertion-row order, copied through the handle's row ids into the order the scan
+ * reads, padding rows 0; NULL clears; synchronises the stream; captured graphs are stale afterwards
+ * (rihip_scratch_generation advances).  save / load do not carry tags; rihip_sq8_index_stats out[2] counts 4 bytes per padded row.
+ * search: rihip_sq8_index_search with pred_dev device uint32, query q's three words at
+ * pred_dev[q * pred_stride]; pred_stride = 3 (one predicate per query) or 0 (one shared by the batch).  Honours
+ * set_id_map.  RIHIP_ERR_STATE without tags.
+ * stats: cumulative {queries searched filtered (any mode), of those re-done dense by the thresholded pass}. */
+int rihip_sq8_filter_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream);
+int rihip_sq8_filter_has_tags(void* handle);
+int rihip_sq8_filter_search(void* handle, const float* Q, int64_t nq, int k, int mode, const uint32_t* pred_dev,
+                            int64_t pred_stride, float* out_scores, int64_t* out_rows, int32_t* out_iscores, void* stream);
+int rihip_sq8_filter_stats(void* handle, int64_t* out);     /* out: int64[2] */
+
 /* ---- SQ8 index: exact f32 re-ranking of the 8-bit candidates, with a per-query certificate (faiss has the first half as
  * IndexRefineFlat).  Opt-in: without attached vectors every call above returns what it returned before.  The calls take
  * an sq8_index handle; they carry a prefix of their own, rihip_sq8_refine_*, so the rihip_sq8_index_* family stays the set it was.
@@ -669,13 +697,24 @@ int rihip_sq8_index_load(const char* path, void** handle);         /* host path;
  *   cert = 1 implies: the output equals the top k by (f, row) over ALL rows of the probed lists.  A probed row outside the
  *   candidates has S <= S_cut, so its real inner product is at most b + t * S_cut + E1 + E2 (its decoded row is within e of
  *   it, and the integer score is within E2 / t of the decoded row's product with q) and its f at most that plus E3; it is
- *   below the k-th refined score, and the k best candidates are k rows with a larger f.  bound does not depend on stage 1. */
+ *   below the k-th refined score, and the k best candidates are k rows with a larger f.  bound does not depend on stage 1.
+ *
+ * search_filtered: rihip_sq8_refine_search with the two predicate arguments of rihip_sq8_filter_search.  Stage 1
+ * is the filtered search at k_scan; stage 2 and the certificate are the same kernels with the same inputs.  cert = 1 then
+ * proves that the list is the exact top k by (f, row) of the PASSING rows of the probed lists: the certificate's first
+ * clause, "stage 1 returned fewer than k_scan valid rows", reads n_valid < k_scan, and a filtered stage 1 returns fewer
+ * than k_scan rows exactly when fewer than k_scan probed rows pass -- it ran out of passing rows and every one of them
+ * was re-scored; in the second clause S_cut bounds every passing probed row outside the candidates, and rows that fail
+ * are outside the claim.  RIHIP_ERR_STATE without vectors or without tags. */
 int rihip_sq8_refine_attach_vectors(void* handle, void* ip_handle, void* stream);   /* synchronous */
 int rihip_sq8_refine_drop_vectors(void* handle);                                    /* synchronous */
 int rihip_sq8_refine_has_vectors(void* handle);
 int rihip_sq8_refine_get_ranges(void* handle, double* e, double* a);         /* synchronous */
 int rihip_sq8_refine_search(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode, float* out_scores,
                                    int64_t* out_rows, uint8_t* out_cert, double* out_bound, void* stream);
+int rihip_sq8_refine_search_filtered(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode,
+                                     const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
+                                     uint8_t* out_cert, double* out_bound, void* stream);
 
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict

@@ -150,6 +150,10 @@ SIGNATURES = {
     "rihip_sq8_index_encode_queries": (C.c_int, [vp, vp, c_i64, vp, vp, vp, vp]),
     "rihip_sq8_index_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp]),
     "rihip_sq8_index_stats": (C.c_int, [vp, vp]),
+    "rihip_sq8_filter_set_tags": (C.c_int, [vp, vp, vp]),
+    "rihip_sq8_filter_has_tags": (C.c_int, [vp]),
+    "rihip_sq8_filter_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, vp, c_i64, vp, vp, vp, vp]),
+    "rihip_sq8_filter_stats": (C.c_int, [vp, vp]),
     "rihip_sq8_index_save": (C.c_int, [vp, C.c_char_p]),
     "rihip_sq8_index_load": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_sq8_refine_attach_vectors": (C.c_int, [vp, vp, vp]),
@@ -157,6 +161,7 @@ SIGNATURES = {
     "rihip_sq8_refine_has_vectors": (C.c_int, [vp]),
     "rihip_sq8_refine_get_ranges": (C.c_int, [vp, vp, vp]),
     "rihip_sq8_refine_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "rihip_sq8_refine_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, c_i64, vp, vp, vp, vp, vp]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

@@ -58,6 +58,9 @@ struct Sq8Index {
   std::vector<int64_t> list_len;
   const int64_t* id_map = nullptr;   // not owned
   int64_t stats[2] = {0, 0};         // queries searched thresholded, of those re-done dense
+  // filtered search (rihip_sq8_filter_set_tags): one 32-bit tag word per physical row, padding rows 0, or null
+  uint32_t* tags = nullptr;          // [Np]
+  int64_t filt_stats[2] = {0, 0};    // queries searched filtered, of those re-done dense
   // refined search (rihip_sq8_refine_attach_vectors): the f32 rows next to the codes, or null
   float* vec = nullptr;              // [N, dk] insertion-row order (stage 1 returns rows: no inverse map)
   double* ref_e = nullptr;           // [dk] e_j = max_i |x_ij - (m_j + s_j c_ij)| over the stored rows
@@ -67,6 +70,7 @@ struct Sq8Index {
   DevBuf<float> qt, qpad, fQ, coarse, thr;
   DevBuf<double> qb;
   DevBuf<uint64_t> cand, scand, fcand;
+  DevBuf<uint32_t> fpred;            // the predicates of one re-do chunk
   // refined search: stage 1's output at k_scan, the f32 keys, valid candidates and smallest integer score per query
   DevBuf<float> rs;
   DevBuf<int64_t> rr;
@@ -78,7 +82,14 @@ struct Sq8Index {
 
 int64_t held_bytes(const Sq8Index* h) {
   return (int64_t)h->Np * h->dpad + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
-         4 * (int64_t)h->nlist + 8 * h->Np + (h->vec ? 4 * h->N * h->dk + 2 * 8 * (int64_t)h->dk : 0);
+         4 * (int64_t)h->nlist + 8 * h->Np + (h->vec ? 4 * h->N * h->dk + 2 * 8 * (int64_t)h->dk : 0) + (h->tags ? 4 * h->Np : 0);
+}
+
+void drop_tags(Sq8Index* h) {
+  if (!h->tags) return;
+  rihip_bump_generation();
+  hipFree(h->tags);
+  h->tags = nullptr;
 }
 
 void drop_vectors(Sq8Index* h) {
@@ -91,6 +102,8 @@ void drop_vectors(Sq8Index* h) {
 void free_sq8(Sq8Index* h) {
   rihip_bump_generation();
   drop_vectors(h);
+  drop_tags(h);
+  h->fpred.release();
   h->rs.release(); h->rr.release(); h->ri.release(); h->rnv.release(); h->rcut.release(); h->rkeys.release();
   hipFree(h->codes); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
   hipFree(h->row_ids);
@@ -240,6 +253,10 @@ struct Sq8LmArgs {
   int nlist, tile_step, nprobe, count_stride;
   int64_t dense_cap;         // > 0: dense slots, cand = [nq*nprobe, dense_cap]
   int dense_ids;             // dense slots carry the original row id instead of 0 (threshold sample)
+  // filtered search (sq8_scan_lm_kernel<DP, true> only)
+  const uint32_t* tags;      // [Np] tag word of every physical row (padding rows 0)
+  const uint32_t* pred;      // query q's predicate (any_of, all_of, none_of) at pred[q * pred_stride]
+  int pred_stride;           // 3 = one per query, 0 = one shared by the batch
 };
 
 __device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
@@ -252,7 +269,12 @@ __device__ __forceinline__ int sq8_score_of_word(uint32_t hw) { return (int)(hw 
 // the A-operand registers (lane (r, h) holds bytes 32 ks + 16 h .. + 15 of row r for k-step ks -- the same bytes of its
 // query on the B side, so whatever order the instruction gives the 16 bytes of a lane, both operands agree on it), the
 // next tile's loads are in flight under the chain.  No LDS, no barrier, no float arithmetic.
-template <int DP>
+//
+// FILT: a lane holds query column lane & 31, so it keeps that query's three predicate words; the tag words of its 16
+// accumulator rows (four runs of four consecutive rows: acc_row) are four 16-byte loads per tile, issued with the next
+// tile's code loads.  A row that fails is absent from all three emissions: its dense or sample slot holds the empty key 0
+// and it is not a survivor.
+template <int DP, bool FILT = false>
 __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
   constexpr int KS = DP / 32;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -300,11 +322,25 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) dst[ks] = src[ks * 2];
   };
+  Pred pr{0u, 0u, 0u};
+  uint4 tw[4], tn[4];
+  auto load_tags = [&](int64_t i, uint4* dst) {   // rows 4 hh + 8 g .. + 3 of tile i: the lane's accumulator rows 4 g .. 4 g + 3
+    const uint4* tp = reinterpret_cast<const uint4*>(a.tags + p0 + i * tstep * TRS + 4 * hh);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) dst[g] = tp[2 * g];
+  };
+  if constexpr (FILT) {
+    pr = load_pred(a.pred, q, a.pred_stride);
+    load_tags(i0, tw);
+  }
   load_tile(i0, av);
 #pragma unroll 1
   for (int64_t i = i0; i < i1; ++i) {
     const bool more = i + 1 < i1;
-    if (more) load_tile(i + 1, nx);
+    if (more) {
+      load_tile(i + 1, nx);
+      if constexpr (FILT) load_tags(i + 1, tn);
+    }
     i32x16 ah, al;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { ah[r] = 0; al[r] = 0; }
@@ -323,13 +359,13 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
           const int rr = acc_row(r, lane);
           const int64_t sl = i * TRS + rr;
           if (sl < a.dense_cap)
-            my_dense[sl] = rr < n_ok ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
+            my_dense[sl] = (rr < n_ok && (!FILT || pr.pass(tag_of(tw, r)))) ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
         }
       } else {
         unsigned hits = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr) hits |= (1u << r);
+          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr && (!FILT || pr.pass(tag_of(tw, r)))) hits |= (1u << r);
         if (hits) {
           int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
 #pragma unroll
@@ -346,6 +382,10 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     if (more) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) av[ks] = nx[ks];
+      if constexpr (FILT) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) tw[g] = tn[g];
+      }
     }
   }
 }
@@ -392,6 +432,8 @@ struct Sq8Search {
   int k;
   float* out_s; int64_t* out_r;   // [nq, k]: finalize's raw output, decoded by the caller
   hipStream_t st;
+  const uint32_t* pred;   // filtered search: these queries' predicates, query q's at pred[q * pred_stride]; else null
+  int pred_stride;
 };
 
 struct Sq8Geom {
@@ -443,9 +485,15 @@ int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* c
   x.row_ids = h->row_ids; x.list_poff = h->list_poff; x.list_len = h->list_len_dev; x.list_qoff = h->list_qoff.p;
   x.list_q = h->list_q.p; x.work_off = h->work_off.p; x.plan = h->plan.p; x.nlist = g.nlist; x.tile_step = tile_step;
   x.nprobe = g.nprobe; x.count_stride = CSTRIDE; x.dense_cap = dense_cap; x.dense_ids = dense_ids;
+  x.tags = s.pred ? h->tags : nullptr; x.pred = s.pred; x.pred_stride = s.pred_stride;
   // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
   const int64_t bound = (int64_t)SQ8_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
   const dim3 grid((unsigned)((bound + 3) / 4));
+  if (x.tags) {
+    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, true>), grid, dim3(256), 0, s.st, x);
+    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, true>), grid, dim3(256), 0, s.st, x);
+    return check_launch("filtered sq8 scan");
+  }
   if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64>), grid, dim3(256), 0, s.st, x);
   else hipLaunchKernelGGL((sq8_scan_lm_kernel<128>), grid, dim3(256), 0, s.st, x);
   return check_launch("sq8 scan");
@@ -471,10 +519,13 @@ int sq8_dense(const Sq8Search& s, const Sq8Geom& g, const int* out_slot) {
   return launch_finalize(f2, (unsigned)n, s.st);
 }
 
-// the `nf` failed queries of h->fail_list, dense, 64 at a time, into their own output rows
+// the `nf` failed queries of h->fail_list, dense, 64 at a time, into their own output rows; a filtered search's chunk
+// carries its queries' own predicates (one shared by the batch is handed on as it is)
 int sq8_redo(const Sq8Search& s, const Sq8Geom& g, int nf) {
   Sq8Index* h = s.h;
   const int FCH = 64;
+  const bool own_pred = s.pred && s.pred_stride != 0;
+  if (own_pred) RCCHK(h->fpred.reserve((int64_t)FCH * 3));
   RCCHK(h->fQ.reserve((int64_t)FCH * h->dk));
   RCCHK(h->fhi.reserve((int64_t)FCH * h->dpad));
   RCCHK(h->flo.reserve((int64_t)FCH * h->dpad));
@@ -484,6 +535,10 @@ int sq8_redo(const Sq8Search& s, const Sq8Geom& g, int nf) {
                        s.Qf, h->fail_list.p + f0, nfc, h->dpad, h->dk, h->fhi.p, h->flo.p, h->fQ.p);
     Sq8Search r = s;
     r.Qf = h->fQ.p; r.qhi = h->fhi.p; r.qlo = h->flo.p; r.nq = nfc;
+    if (own_pred) {
+      launch_gather_pred(s.pred, h->fail_list.p + f0, nfc, h->fpred.p, s.st);
+      r.pred = h->fpred.p;
+    }
     RCCHK(sq8_dense(r, g, h->fail_list.p + f0));
   }
   return RIHIP_OK;
@@ -493,6 +548,8 @@ int sq8_redo(const Sq8Search& s, const Sq8Geom& g, int nf) {
 // sampled score is the query's threshold; (B) all probed tiles, S >= threshold appended; select; a query whose list
 // overflowed, or that holds fewer than k candidates under a real threshold, is re-done dense.  Integer scores: a query that
 // passes holds every probed row with S >= threshold and at least k of them, so its top k is complete -- no epsilon.
+// Filtered: "row" reads "passing row" throughout (a failing row is in neither the sample nor the survivors), so the same
+// argument holds under any pass rate; a sample with fewer than rank passing rows gives no threshold.
 int sq8_thresholded(const Sq8Search& s, const Sq8Geom& g) {
   Sq8Index* h = s.h;
   const int64_t nq = s.nq;
@@ -523,6 +580,7 @@ int sq8_thresholded(const Sq8Search& s, const Sq8Geom& g) {
   HIPCHK(hipStreamSynchronize(s.st));
   const int nf = *h->h_nfail;
   h->stats[0] += nq; h->stats[1] += nf;
+  if (s.pred) h->filt_stats[1] += nf;
   return nf > 0 ? sq8_redo(s, g, nf) : RIHIP_OK;
 }
 
@@ -537,7 +595,7 @@ int sq8_transform_queries(Sq8Index* h, const float* Q, int64_t nq, int16_t* n16,
 }
 
 int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* out_s, int64_t* out_r, int* out_i,
-               hipStream_t st) {
+               hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0) {
   RCCHK(sq8_transform_queries(h, Q, nq, nullptr, nullptr, nullptr, st));
   const float* Qf = Q;
   if (h->du != h->dk) {
@@ -558,9 +616,11 @@ int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* 
   if (!h->h_nfail) HIPCHK(hipHostMalloc((void**)&h->h_nfail, sizeof(int)));
   for (int64_t q0 = 0; q0 < nq; q0 += ch) {
     const int64_t n = std::min(ch, nq - q0);
-    const Sq8Search s{h, Qf + q0 * h->dk, h->qhi.p + q0 * h->dpad, h->qlo.p + q0 * h->dpad, n, k, out_s + q0 * k, out_r + q0 * k, st};
+    const Sq8Search s{h, Qf + q0 * h->dk, h->qhi.p + q0 * h->dpad, h->qlo.p + q0 * h->dpad, n, k, out_s + q0 * k, out_r + q0 * k, st,
+                      pred ? pred + q0 * pred_stride : nullptr, pred_stride};
     RCCHK(thresholded ? sq8_thresholded(s, g) : sq8_dense(s, g, nullptr));
   }
+  if (pred) h->filt_stats[0] += nq;
   const int64_t tot = nq * k;
   hipLaunchKernelGGL(sq8_decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, out_s, out_r, out_i, nq, k, h->qt.p,
                      h->qb.p, h->id_map);
@@ -836,7 +896,7 @@ __global__ __launch_bounds__(128) void sq8_cert_kernel(const float* __restrict__
 }
 
 int sq8_search_refined(Sq8Index* h, const float* Q, int64_t nq, int k, int k_scan, int mode, float* out_s, int64_t* out_r,
-                       uint8_t* out_cert, double* out_bound, hipStream_t st) {
+                       uint8_t* out_cert, double* out_bound, hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0) {
   const int64_t ch = std::max<int64_t>(1, std::min<int64_t>(nq, (1ll << 24) / k_scan));   // stage-1 slots per pass: 2^24
   RCCHK(h->rs.reserve(ch * k_scan)); RCCHK(h->rr.reserve(ch * k_scan)); RCCHK(h->ri.reserve(ch * k_scan));
   RCCHK(h->rkeys.reserve(ch * k_scan)); RCCHK(h->rnv.reserve(ch)); RCCHK(h->rcut.reserve(ch));
@@ -845,7 +905,8 @@ int sq8_search_refined(Sq8Index* h, const float* Q, int64_t nq, int k, int k_sca
     const int64_t n = std::min(ch, nq - q0);
     const float* Qc = Q + q0 * h->du;
     h->id_map = nullptr;   // stage 1 hands on rows; the map is applied after the select
-    const int rc = sq8_search(h, Qc, n, k_scan, mode, h->rs.p, h->rr.p, h->ri.p, st);
+    const int rc = sq8_search(h, Qc, n, k_scan, mode, h->rs.p, h->rr.p, h->ri.p, st, pred ? pred + q0 * pred_stride : nullptr,
+                              pred_stride);
     h->id_map = id_map;
     RCCHK(rc);
     RCCHK(dispatch_d(h->dk, [&](auto D) {
@@ -1002,6 +1063,63 @@ extern "C" int rihip_sq8_index_search(void* handle, const float* Q, int64_t nq, 
   RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "sq8_index_search: k=%d outside [1,%d]", k, K_MAX);
   RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_index_search: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
   return sq8_search(h, Q, nq, k, mode, out_scores, out_rows, out_iscores, (hipStream_t)stream);
+}
+
+// ---- filtered search: per-query tag predicates inside the int8 scan ---------------------------------------------------
+extern "C" int rihip_sq8_filter_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_set_tags: index is empty");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipStreamSynchronize(st));   // (searches in flight still read the old copy)
+  drop_tags(h);
+  if (!tags_by_row_dev) return RIHIP_OK;
+  uint32_t* t = nullptr;
+  HIPCHK(hipMalloc((void**)&t, sizeof(uint32_t) * (size_t)h->Np));
+  launch_tags_to_scan_order(tags_by_row_dev, h->row_ids, h->Np, t, st);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // the caller's array may go away after the call
+  if (e != hipSuccess) { hipFree(t); rihip_set_error("sq8_filter_set_tags: %s", hipGetErrorString(e)); return RIHIP_ERR_HIP; }
+  rihip_bump_generation();
+  h->tags = t;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_filter_has_tags(void* handle) { return handle && ((Sq8Index*)handle)->tags ? 1 : 0; }
+
+extern "C" int rihip_sq8_filter_stats(void* handle, int64_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_filter_stats: bad arguments");
+  out[0] = h->filt_stats[0]; out[1] = h->filt_stats[1];
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_filter_search(void* handle, const float* Q, int64_t nq, int k, int mode, const uint32_t* pred_dev,
+                                       int64_t pred_stride, float* out_scores, int64_t* out_rows, int32_t* out_iscores,
+                                       void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_search: index is empty");
+  RIHIP_REQUIRE(h->tags, RIHIP_ERR_STATE, "sq8_filter_search: the index has no tags (rihip_sq8_filter_set_tags)");
+  RIHIP_REQUIRE(Q && pred_dev && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "sq8_filter_search: bad arguments");
+  RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "sq8_filter_search: pred_stride=%lld (0 or 3)", (long long)pred_stride);
+  RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "sq8_filter_search: k=%d outside [1,%d]", k, K_MAX);
+  RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_filter_search: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
+  return sq8_search(h, Q, nq, k, mode, out_scores, out_rows, out_iscores, (hipStream_t)stream, pred_dev, (int)pred_stride);
+}
+
+extern "C" int rihip_sq8_refine_search_filtered(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode,
+                                                const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
+                                                uint8_t* out_cert, double* out_bound, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_search_filtered: index is empty");
+  RIHIP_REQUIRE(h->vec, RIHIP_ERR_STATE, "sq8_refine_search_filtered: no vectors attached (rihip_sq8_refine_attach_vectors)");
+  RIHIP_REQUIRE(h->tags, RIHIP_ERR_STATE, "sq8_refine_search_filtered: the index has no tags (rihip_sq8_filter_set_tags)");
+  RIHIP_REQUIRE(Q && pred_dev && out_scores && out_rows && out_cert && nq > 0, RIHIP_ERR_ARG, "sq8_refine_search_filtered: bad arguments");
+  RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "sq8_refine_search_filtered: pred_stride=%lld (0 or 3)", (long long)pred_stride);
+  RIHIP_REQUIRE(k >= 1 && k <= k_scan && k_scan <= K_MAX, RIHIP_ERR_ARG,
+                "sq8_refine_search_filtered: k=%d, k_scan=%d (1 <= k <= k_scan <= %d)", k, k_scan, K_MAX);
+  RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_refine_search_filtered: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
+  return sq8_search_refined(h, Q, nq, k, k_scan, mode, out_scores, out_rows, out_cert, out_bound, (hipStream_t)stream, pred_dev,
+                            (int)pred_stride);
 }
 
 extern "C" int rihip_sq8_refine_attach_vectors(void* handle, void* ip_handle, void* stream) {

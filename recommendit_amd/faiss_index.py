@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
-import math
 import pickle
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
@@ -29,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .exclusion import ExcludingSearch
 
 logger = logging.getLogger(__name__)
 
@@ -135,7 +135,7 @@ def _list_stats(sizes: np.ndarray) -> Dict:
             "imbalance": n * sq / (tot * tot) if tot else 0.0}
 
 
-class FAISSIndex:
+class FAISSIndex(ExcludingSearch):
     def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
         """exact=True skips the IVF partition (brute-force inner product; not in the reference)."""
         self.embed_dim = embed_dim
@@ -515,65 +515,7 @@ class FAISSIndex:
         L.check(L.lib().rihip_ip_index_last_fail_count(self.index._h, C.byref(n), L.stream_ptr()), "ip_index_last_fail_count")
         return int(n.value)
 
-    # -- seen-item exclusion (not in the reference: SURVEY.md §3.4 hazard ii; seen.py, csrc/exclude.hip) ---------
-    def filter_excluded(self, scores: torch.Tensor, ids: torch.Tensor, k: int, seen, user_ids: Optional[torch.Tensor],
-                        out_scores: torch.Tensor, out_ids: torch.Tensor, out_slot: Optional[torch.Tensor] = None) -> None:
-        """rows of an over-fetched result [nq, k_eff] -> their first k allowed entries, written to row out_slot[q]
-        (int32 device tensor; None: row q) of out_scores / out_ids [.., k]; user_ids None: list q of `seen` belongs to
-        query q.  A result that already holds the whole corpus cannot have been fetched short: not counted."""
-        if self._deficit is None:
-            self._deficit = torch.zeros(1, dtype=torch.int32, device=scores.device)
-        nq, kc = ids.shape
-        whole = kc >= self.index.ntotal
-        L.check(L.lib().rihip_exclude_topk(scores.data_ptr(), ids.data_ptr(), nq, kc, L.ptr(user_ids),
-                                           seen.offsets.data_ptr(), seen.n_users, seen.items.data_ptr(), k,
-                                           out_scores.data_ptr(), out_ids.data_ptr(), L.ptr(out_slot),
-                                           None if whole else self._deficit.data_ptr(), L.stream_ptr()), "exclude_topk")
-
-    def exclusion_deficit(self) -> int:
-        """queries so far whose over-fetch was too small to fill k allowed entries (one synchronisation); 0 whenever
-        the plan of seen.py chose k_eff"""
-        return 0 if self._deficit is None else int(self._deficit.item())
-
-    def _search_excluding(self, q: torch.Tensor, k: int, seen, user_ids, item_filter=None
-                          ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """q normalised f32 [nq,d] on device -> (scores, item ids) [nq,k] without each query's excluded items.
-        user_ids: host sequence (queries are grouped by how far they have to over-fetch, one search per group), a
-        device tensor (one group at the store's longest list) or None (list q of `seen` belongs to query q)."""
-        from .seen import overfetch_k, plan_overfetch
-        nq, ntotal = q.shape[0], self.index.ntotal
-        k_max = int(L.lib().rihip_ip_index_max_k())
-        if isinstance(user_ids, torch.Tensor) and user_ids.is_cuda:
-            uid = user_ids.to(dtype=torch.long).contiguous()
-            plan = [(overfetch_k(k, seen.max_count, ntotal, k_max), None)]
-            nothing = seen.max_count == 0
-        else:
-            host = np.arange(nq) if user_ids is None else np.asarray(user_ids, dtype=np.int64).reshape(-1)
-            if host.shape[0] != nq:
-                raise ValueError(f"{host.shape[0]} user ids for {nq} queries")
-            # a deferred exactness check belongs to ONE search of the handle: no groups under it
-            extra = seen.counts_of(host)
-            plan = plan_overfetch(extra, k, ntotal, k_max, math.inf if self._deferred else None)
-            uid = None if user_ids is None else torch.from_numpy(host).to(q.device)
-            nothing = not extra.any()
-        if len(plan) == 1:
-            k_eff = plan[0][0]
-            s, c = self._search_device(q, k_eff, item_ids=True, item_filter=item_filter)
-            if nothing:
-                return s, c
-            scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            self.filter_excluded(s, c, k, seen, uid, scores, ids)
-            return scores, ids
-        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        for k_eff, pos in plan:
-            slot = torch.from_numpy(pos.astype(np.int32)).to(q.device)
-            sel = slot.to(torch.long)
-            s, c = self._search_device(q[sel].contiguous(), k_eff, item_ids=True,
-                                       item_filter=None if item_filter is None else _sub_filter(item_filter, sel))
-            self.filter_excluded(s, c, k, seen, sel if uid is None else uid[sel], scores, ids, slot)
-        return scores, ids
+    # -- seen-item exclusion: filter_excluded, exclusion_deficit and _search_excluding come from exclusion.ExcludingSearch
 
     def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None, item_filter=None
                ) -> Tuple[np.ndarray, np.ndarray]:

@@ -203,9 +203,12 @@ class GpuRecommendationPipeline:
         replaces the one behind seen-item exclusion and item_filter, so it composes with both, and it is one launch
         without synchronisation: graph=True works.
 
-        index may be an SQ8Index (the 8-bit scalar-quantised index, sq8_index.py) for the plain chain: tower -> SQ8
-        search -> features -> ranker -> top-k.  A seen store, item_filter, diversity, the cold-start calls and
-        graph=True are not built for it yet: each raises ValueError.
+        index may be an SQ8Index (the 8-bit scalar-quantised index, sq8_index.py): tower -> SQ8 search -> features ->
+        ranker -> top-k, with the refined search when the index's set_refine is on.  recommend_batch(item_filter=...)
+        runs the same chain on the filtered SQ8 search when the index has item tags (SQ8Index.set_item_tags) and raises
+        ValueError, before anything is launched, when it has none.  A seen store on the pipeline, diversity, the
+        cold-start calls and graph=True are not built for it: each raises ValueError (seen items can be excluded on the
+        index itself: SQ8Index.batch_search_device(exclude=...)).
 
         feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
         device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
@@ -231,7 +234,7 @@ class GpuRecommendationPipeline:
 
     def _no_sq8(self, what: str, asked: bool) -> None:
         if self._sq8 and asked:
-            raise ValueError(f"{what} is not supported on an SQ8 index (SQ8Index serves the plain chain only)")
+            raise ValueError(f"{what} is not supported on an SQ8 index (SQ8Index serves the plain and the filtered chain only)")
 
     def set_seen(self, seen: Optional[SeenItems]) -> None:
         """attach / replace / detach (None) the store of excluded items; captured graphs are re-captured"""
@@ -282,7 +285,8 @@ class GpuRecommendationPipeline:
         the outputs are then in MMR selection order, not in score order."""
         k = k or self.top_k_results
         self._no_sq8("graph=True", bool(graph))
-        self._no_sq8("item_filter", item_filter is not None)
+        if self._sq8 and item_filter is not None and self.index._tags is None:      # (host state only: nothing is launched)
+            raise ValueError("item_filter on an SQ8 index needs item tags: call SQ8Index.set_item_tags() first")
         self._no_sq8("exclude_seen", bool(exclude_seen))
         self._no_sq8("diversity", diversity is not _DEFAULT and diversity is not None)
         div = self._diversity_stage(diversity, k)

@@ -13,6 +13,11 @@ may re-score the 8-bit search's best ``k_scan = ceil(factor * k)`` candidates ex
 those, with a per-query certificate that the list is the exact top k of the probed lists (``refine=``,
 ``return_cert=``, ``set_refine``, ``search_certified``; rihip_sq8_refine_search in recommendit_hip.h).
 
+Filtered retrieval and seen-item exclusion, as on FAISSIndex: ``set_item_tags`` gives every item a 32-bit tag word and
+``item_filter=(any_of, all_of, none_of)`` restricts a search to the items whose word passes, tested inside the int8 scan
+(rihip_sq8_filter_* in recommendit_hip.h); ``exclude=`` / ``user_ids=`` over-fetch and drop each query's seen items on
+the device (exclusion.py).  Both compose with ``mode=``, ``refine=`` and ``return_cert=``.
+
 There is no NumPy or torch path for encode or search: everything runs in csrc/sq8.hip.
 """
 from __future__ import annotations
@@ -28,7 +33,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .faiss_index import FAISSIndex
+from .exclusion import ExcludingSearch
+from .faiss_index import FAISSIndex, _filter_device, _sub_filter
 
 logger = logging.getLogger(__name__)
 
@@ -87,7 +93,25 @@ def _mode(mode) -> int:
     return MODES[mode]
 
 
-class SQ8Index:
+def _tag_words(tags, n: int) -> np.ndarray:
+    """uint32 / int32 words [n] (host array or tensor) -> uint32 [n] on the host (FAISSIndex._tags_dev's checks)"""
+    if isinstance(tags, torch.Tensor):
+        a = tags.detach().cpu().numpy()
+        a = a.view(np.uint32) if a.dtype == np.int32 else a.astype(np.uint32)
+    else:
+        a = np.asarray(tags)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"tags must be uint32 words, got {a.dtype}")
+        if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 32)):
+            raise ValueError("tags must fit 32 bits")
+        a = (a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    a = np.ascontiguousarray(a.reshape(-1))
+    if a.shape[0] != n:
+        raise ValueError(f"{a.shape[0]} tag words for {n} items")
+    return a
+
+
+class SQ8Index(ExcludingSearch):
     def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
         if not 1 <= int(embed_dim) <= 128:
             raise ValueError(f"SQ8Index: embed_dim={embed_dim} outside 1..128")
@@ -100,6 +124,9 @@ class SQ8Index:
         self._item_id_to_faiss_idx: Dict[int, int] = {}
         self._item_ids_dev: Optional[torch.Tensor] = None
         self._refine: Optional[float] = None
+        self._deficit: Optional[torch.Tensor] = None
+        self._tags: Optional[np.ndarray] = None        # uint32 [ntotal] on the host, row order (the handle holds its own copy)
+        self._pred_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}   # shared predicates already on the device
 
     # -- build ----------------------------------------------------------------------------------------------------
     @classmethod
@@ -107,7 +134,8 @@ class SQ8Index:
                    keep_vectors: bool = False) -> "SQ8Index":
         """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  ranges: (centre,
         scale), two f32 [embed_dim] arrays that replace the trained per-dimension quantiser; scale > 0.
-        keep_vectors=True also copies the f32 vectors (attach_vectors), which a refined search needs."""
+        keep_vectors=True also copies the f32 vectors (attach_vectors), which a refined search needs.  A source with item
+        tags hands them on (set_item_tags); one without leaves the new index untagged."""
         if not isinstance(faiss_index, FAISSIndex):
             raise ValueError(f"SQ8Index.from_index needs a FAISSIndex, got {type(faiss_index).__name__}")
         if faiss_index.index is None:
@@ -139,7 +167,67 @@ class SQ8Index:
         logger.info("SQ8 index built: %d vectors, %d lists, probe=%d", obj.index.ntotal, obj.index.nlist, obj.n_probe)
         if keep_vectors:
             obj.attach_vectors(faiss_index)
+        if faiss_index._tags is not None:
+            obj.set_item_tags(faiss_index.item_tags())
         return obj
+
+    # -- item tags (filtered retrieval; FAISSIndex's semantics and error texts) ---------------------------------------
+    def _push_tags(self) -> None:
+        t = None if self._tags is None else torch.from_numpy(self._tags.view(np.int32)).to(L.device())
+        L.check(L.lib().rihip_sq8_filter_set_tags(self.index._h, L.ptr(t), L.stream_ptr()), "sq8_filter_set_tags")
+
+    def set_item_tags(self, tags, item_ids=None) -> None:
+        """Give every stored item a 32-bit tag word.  tags uint32 [ntotal] in row order; with item_ids, tags[i] belongs to
+        item_ids[i] and items that are not named keep their word (0 on an index that had none).  ValueError for an id
+        that is not stored.  Tags are not saved: a loaded index has none."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        n = int(self.item_ids.shape[0])
+        if item_ids is None:
+            new = _tag_words(tags, n)
+        else:
+            ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+            t = _tag_words(tags, ids.shape[0])
+            order = np.argsort(self.item_ids, kind="stable")
+            pos = np.minimum(np.searchsorted(self.item_ids[order], ids), n - 1)
+            rows = order[pos]
+            missing = self.item_ids[rows] != ids
+            if missing.any():
+                raise ValueError(f"item id {int(ids[missing][0])} is not stored")
+            new = self._tags.copy() if self._tags is not None else np.zeros(n, dtype=np.uint32)
+            new[rows] = t
+        self._tags = new
+        self._push_tags()
+
+    def item_tags(self) -> Optional[np.ndarray]:
+        """uint32 [ntotal] tag words in row order (None without tags)"""
+        return None if self._tags is None else self._tags.copy()
+
+    def clear_item_tags(self) -> None:
+        self._tags = None
+        if self.index is not None:
+            self._push_tags()
+
+    @property
+    def has_item_tags(self) -> bool:
+        return self.index is not None and bool(L.lib().rihip_sq8_filter_has_tags(self.index._h))
+
+    def filtered_stats(self) -> Tuple[int, int]:
+        """(queries searched with an item_filter, of those re-done dense by the thresholded pass) since the handle was made"""
+        out = (C.c_int64 * 2)()
+        L.check(L.lib().rihip_sq8_filter_stats(self._built()._h, out), "sq8_filter_stats")
+        return int(out[0]), int(out[1])
+
+    def _pred(self, item_filter, nq: int, device) -> Tuple[torch.Tensor, int]:
+        """item_filter in any of FAISSIndex's forms -> (int32 device words, stride 3 or 0); host-only checks first"""
+        if self._tags is None:
+            raise ValueError("item_filter needs item tags: call set_item_tags() first")
+        if isinstance(item_filter, tuple) and item_filter in self._pred_cache:
+            return self._pred_cache[item_filter], 0
+        pred, stride = _filter_device(item_filter, nq, device)
+        if stride == 0 and isinstance(item_filter, tuple) and len(self._pred_cache) < 1024:
+            self._pred_cache[item_filter] = pred
+        return pred, stride
 
     # -- refined search: the f32 vectors next to the codes ------------------------------------------------------------
     def attach_vectors(self, faiss_index: FAISSIndex) -> None:
@@ -232,26 +320,32 @@ class SQ8Index:
             raise ValueError("SQ8Index: no queries")
         return queries.to(device=L.device(), dtype=torch.float32).contiguous()
 
-    def _refined_device(self, q_dev: torch.Tensor, k: int, k_scan: int, item_ids: bool, mode: int):
+    def _refined_device(self, q_dev: torch.Tensor, k: int, k_scan: int, item_ids: bool, mode: int, item_filter=None):
         """(scores f32 [nq, k], rows or ids i64 [nq, k], cert u8 [nq], bound f64 [nq]) of one refined search"""
         h = self._built()
         lib = L.lib()
         if not self.has_vectors:
             raise RuntimeError("SQ8Index: refine needs the f32 vectors (from_index(keep_vectors=True) or attach_vectors)")
         nq = q_dev.shape[0]
+        pred = None if item_filter is None else self._pred(item_filter, nq, q_dev.device)
         L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr() if item_ids else None),
                 "sq8_index_set_id_map")
         scores = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=q_dev.device)
         cert = torch.empty((nq,), dtype=torch.uint8, device=q_dev.device)
         bound = torch.empty((nq,), dtype=torch.float64, device=q_dev.device)
+        if pred is not None:
+            L.check(lib.rihip_sq8_refine_search_filtered(h._h, q_dev.data_ptr(), nq, k, k_scan, mode, pred[0].data_ptr(), pred[1],
+                                                         scores.data_ptr(), rows.data_ptr(), cert.data_ptr(), bound.data_ptr(),
+                                                         L.stream_ptr()), "sq8_refine_search_filtered")
+            return scores, rows, cert, bound
         L.check(lib.rihip_sq8_refine_search(h._h, q_dev.data_ptr(), nq, k, k_scan, mode, scores.data_ptr(),
                                                    rows.data_ptr(), cert.data_ptr(), bound.data_ptr(), L.stream_ptr()),
                 "sq8_refine_search")
         return scores, rows, cert, bound
 
     def _search_device(self, q_dev: torch.Tensor, k: int, item_ids: bool, mode: int, return_int: bool, refine=_DEFAULT,
-                       return_cert: bool = False):
+                       return_cert: bool = False, item_filter=None):
         h = self._built()
         lib = L.lib()
         factor = self._refine if refine is _DEFAULT else _factor(refine)
@@ -262,21 +356,41 @@ class SQ8Index:
         if factor is not None:
             if return_int:
                 raise ValueError("SQ8Index: return_int gives the 8-bit search's integer scores; a refined search has none")
-            out = self._refined_device(q_dev, k, self._k_scan(k, factor), item_ids, mode)
+            out = self._refined_device(q_dev, k, self._k_scan(k, factor), item_ids, mode, item_filter)
             return out if return_cert else out[:2]
         if return_cert:
             raise ValueError("SQ8Index: return_cert needs a refined search (refine= or set_refine)")
         nq = q_dev.shape[0]
+        pred = None if item_filter is None else self._pred(item_filter, nq, q_dev.device)
         L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr() if item_ids else None),
                 "sq8_index_set_id_map")
         scores = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=q_dev.device)
         ints = torch.empty((nq, k), dtype=torch.int32, device=q_dev.device) if return_int else None
+        if pred is not None:
+            L.check(lib.rihip_sq8_filter_search(h._h, q_dev.data_ptr(), nq, k, mode, pred[0].data_ptr(), pred[1], scores.data_ptr(),
+                                                rows.data_ptr(), L.ptr(ints), L.stream_ptr()), "sq8_filter_search")
+            return (scores, rows, ints) if return_int else (scores, rows)
         L.check(lib.rihip_sq8_index_search(h._h, q_dev.data_ptr(), nq, k, mode, scores.data_ptr(), rows.data_ptr(),
                                            L.ptr(ints), L.stream_ptr()), "sq8_index_search")
         return (scores, rows, ints) if return_int else (scores, rows)
 
-    def search(self, query_vector: np.ndarray, k: int = 500, refine=_DEFAULT) -> Tuple[np.ndarray, np.ndarray]:
+    def _excluding(self, q: torch.Tensor, k: int, seen, user_ids, item_filter, mode: int, return_int: bool, refine,
+                   return_cert: bool):
+        """the search without each query's seen items: the over-fetched k_eff of seen.plan_overfetch is what is searched
+        (and, with a refine factor, refined: k_scan = ceil(factor * k_eff)); a certificate then speaks of the over-fetched
+        list, whose first k unseen entries are the result"""
+        if return_int:
+            raise ValueError("SQ8Index: return_int is not available with exclude (the device filter moves scores and ids only)")
+
+        def run(qq, kk, flt):
+            return self._search_device(qq, kk, True, mode, False, refine, return_cert, flt)
+        return self._search_excluding(q, k, seen, user_ids, item_filter, search=run)
+
+    def search(self, query_vector: np.ndarray, k: int = 500, refine=_DEFAULT, exclude_items=None, item_filter=None
+               ) -> Tuple[np.ndarray, np.ndarray]:
+        """exclude_items: item ids that must not be returned; item_filter: (any_of, all_of, none_of) over the items' tag
+        words, as in batch_search_device"""
         h = self._built()
         query = np.atleast_2d(query_vector).astype(np.float32)
         if query.shape[1] != self.embed_dim:
@@ -284,13 +398,24 @@ class SQ8Index:
         query = query / np.maximum(np.linalg.norm(query, axis=1, keepdims=True), 1e-8)
         k = min(k, h.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(query[:1])).to(L.device())
-        scores, rows = self._search_device(q_dev, k, False, 0, False, refine)
+        if exclude_items is not None:
+            from .seen import SeenItems
+            ex = np.asarray(exclude_items, dtype=np.int64).reshape(-1)
+            seen = SeenItems.from_pairs(np.zeros(ex.shape[0], np.int64), ex, 1)
+            scores, ids = self._search_excluding(
+                q_dev, k, seen, None, item_filter,
+                search=lambda qq, kk, flt: self._search_device(qq, kk, True, 0, False, refine, False, flt))
+            distances, ids = scores[0].cpu().numpy(), ids[0].cpu().numpy()
+            return distances[ids >= 0], ids[ids >= 0]
+        scores, rows = self._search_device(q_dev, k, False, 0, False, refine, item_filter=item_filter)
         distances, idx = scores[0].cpu().numpy(), rows[0].cpu().numpy()
         valid = idx >= 0
         return distances[valid], self.item_ids[idx[valid]]
 
-    def batch_search(self, query_vectors: np.ndarray, k: int = 500, refine=_DEFAULT, return_cert: bool = False):
-        """(scores, item ids) as NumPy arrays; return_cert=True appends (cert u8 [nq], bound f64 [nq])"""
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500, refine=_DEFAULT, return_cert: bool = False,
+                     exclude=None, user_ids=None, item_filter=None):
+        """(scores, item ids) as NumPy arrays; return_cert=True appends (cert u8 [nq], bound f64 [nq]); exclude /
+        user_ids / item_filter as in batch_search_device"""
         h = self._built()
         queries = np.asarray(query_vectors).astype(np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.embed_dim:
@@ -298,11 +423,15 @@ class SQ8Index:
         queries = queries / np.maximum(np.linalg.norm(queries, axis=1, keepdims=True), 1e-8)
         k = min(k, h.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
-        out = self._search_device(self._queries(q_dev), k, True, 0, False, refine, return_cert)
+        if exclude is not None:
+            out = self._excluding(self._queries(q_dev), k, exclude, user_ids, item_filter, 0, False, refine, return_cert)
+        else:
+            out = self._search_device(self._queries(q_dev), k, True, 0, False, refine, return_cert, item_filter)
         return tuple(t.cpu().numpy() for t in out)
 
     def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, mode: str = "auto",
-                            return_int: bool = False, refine=_DEFAULT, return_cert: bool = False):
+                            return_int: bool = False, refine=_DEFAULT, return_cert: bool = False, exclude=None,
+                            user_ids=None, item_filter=None):
         """queries f32 [nq, embed_dim] on the device -> (scores f32, item ids i64) [nq, k] on the device, -1 padded;
         return_int=True appends the integer scores i32 [nq, k].  mode: "auto", "dense" or "thresholded" (the same bytes
         from each; "thresholded" synchronises the stream for its completeness check).
@@ -310,24 +439,40 @@ class SQ8Index:
         refine: a factor >= 1 re-scores the best k_scan = min(max(k, ceil(factor * k)), max_k) candidates of the 8-bit
         search exactly in f32 and returns the top k of those with their f32 scores; None is the plain search; left
         out, the factor of set_refine.  return_cert=True appends (cert u8 [nq], bound f64 [nq]): cert = 1 proves the
-        list is the exact top k of the probed lists."""
+        list is the exact top k of the probed lists.
+
+        item_filter (needs set_item_tags): a 3-tuple of ints (any_of, all_of, none_of) shared by the batch, a uint32
+        array [nq,3], or an int32 device tensor [nq,3] read as a bit pattern, as FAISSIndex.batch_search_device.  The
+        result is the exact top k, by integer score, of the passing items of the probed lists, -1 padded when fewer
+        pass; (0,0,0) equals the plain search.  The predicate is tested inside the int8 scan in every mode.  With
+        refine the filtered search is stage 1 and cert = 1 proves the exact top k of the passing probed items.
+        ValueError without tags or on a bad shape.
+
+        exclude (a seen.SeenItems) with user_ids [nq]: query q never returns an item of row user_ids[q] of the store
+        (user_ids None: of row q); host user ids are searched in groups by how far each has to over-fetch (seen.plan_overfetch), a device tensor as
+        one group at the store's longest list.  The over-fetched k_eff is what is searched and, with refine, refined.
+        With item_filter the result is filter AND not-seen.  Not with return_int."""
         h = self._built()
         m = _mode(mode)
         q = self._queries(queries)
         if not normalized:
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
-        return self._search_device(q, min(k, h.ntotal), True, m, return_int, refine, return_cert)
+        if exclude is not None:
+            return self._excluding(q, min(k, h.ntotal), exclude, user_ids, item_filter, m, return_int, refine, return_cert)
+        return self._search_device(q, min(k, h.ntotal), True, m, return_int, refine, return_cert, item_filter)
 
     def search_rows_device(self, queries: torch.Tensor, k: int, mode: str = "auto", return_int: bool = False, refine=_DEFAULT,
-                           return_cert: bool = False):
+                           return_cert: bool = False, item_filter=None):
         """batch_search_device on queries taken as they are, returning ROWS (insertion order) instead of item ids and k
         as given (padded beyond ntotal)"""
-        return self._search_device(self._queries(queries), k, False, _mode(mode), return_int, refine, return_cert)
+        return self._search_device(self._queries(queries), k, False, _mode(mode), return_int, refine, return_cert, item_filter)
 
-    def search_certified(self, queries: torch.Tensor, k: int = 500, start: float = 2.0, normalized: bool = False):
+    def search_certified(self, queries: torch.Tensor, k: int = 500, start: float = 2.0, normalized: bool = False,
+                         item_filter=None):
         """Refine at factor `start`, then repeat only the queries without a certificate with k_scan doubled until they
         have one or k_scan reaches the select buffer's size.  -> (scores f32 [nq, k], item ids i64 [nq, k], cert u8 [nq])
-        on the device; a query whose flag is still 0 is reported as it is, not repaired."""
+        on the device; a query whose flag is still 0 is reported as it is, not repaired.  item_filter: as in
+        batch_search_device; a repeat carries the predicates of the queries it repeats."""
         h = self._built()
         f = _factor(start)
         if f is None:
@@ -340,13 +485,14 @@ class SQ8Index:
         if k < 1 or k > max_k:
             raise ValueError(f"SQ8Index: k={k} outside 1..{max_k}")
         k_scan = self._k_scan(k, f)
-        scores, ids, cert, _ = self._refined_device(q, k, k_scan, True, 0)
+        scores, ids, cert, _ = self._refined_device(q, k, k_scan, True, 0, item_filter)
         while k_scan < max_k:
             todo = torch.nonzero(cert == 0).flatten()
             if todo.numel() == 0:
                 break
             k_scan = min(2 * k_scan, max_k)
-            s2, i2, c2, _ = self._refined_device(q[todo].contiguous(), k, k_scan, True, 0)
+            s2, i2, c2, _ = self._refined_device(q[todo].contiguous(), k, k_scan, True, 0,
+                                                 None if item_filter is None else _sub_filter(item_filter, todo))
             scores[todo], ids[todo], cert[todo] = s2, i2, c2
         return scores, ids, cert
 
@@ -361,9 +507,6 @@ class SQ8Index:
         return False
 
     def last_fail_count(self) -> int:
-        return 0
-
-    def exclusion_deficit(self) -> int:
         return 0
 
     # -- persistence ------------------------------------------------------------------------------------------------
@@ -430,6 +573,7 @@ class SQ8Index:
             "queries_thresholded": int(out[0]),
             "queries_redone": int(out[1]),
             "has_vectors": self.has_vectors,
+            "has_item_tags": self.has_item_tags,
             "refine": self._refine,
         }
 
