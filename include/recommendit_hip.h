@@ -716,6 +716,41 @@ int rihip_sq8_refine_search_filtered(void* handle, const float* Q, int64_t nq, i
                                      const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
                                      uint8_t* out_cert, double* out_bound, void* stream);
 
+/* ---- SQ8 index: add / remove / replace items without the f32 source and without re-encoding the rows that stay (what
+ * rihip_ip_index_update is to the ip_index).  The calls take an sq8_index handle and carry a prefix of their own,
+ * rihip_sq8_update_*.  ONE repack of the code matrix on the device under the handle's own centroids and its own
+ * quantiser (centre, scale); neither is retrained.  The quantiser is per row and per dimension, so a kept row keeps its
+ * code; only the new rows are encoded, c_ij = clamp(rintf((x_ij - m_j) / s_j), -127, 127) as above.
+ * apply: item_ids: device [N], the id of every stored row; drop_ids: device [n_drop], any order, ids that are not stored
+ * are ignored; X_add: device f32 [n_add,d] normalised rows, 16-byte aligned, appended in call order as rows N_keep ..
+ * N_keep+n_add-1 with the ids add_ids (device [n_add]); add_tags: device uint32 [n_add], the tag words of the new rows,
+ * or NULL meaning 0 (ignored on a handle without tags); surviving rows keep their relative order and are renumbered
+ * densely.  item_ids_out: device [N + n_add], receives the id of every row of the result (first *n_total entries).  Host
+ * outputs: *n_total rows of the result, *n_dropped stored rows removed, *n_clamped the pairs (new row i, column j < d)
+ * whose unclamped rintf((x_ij - m_j) / s_j) lies outside +-127: an integer count, the drift signal of a frozen quantiser.
+ * The handle is left bit for bit in the state that
+ *   rihip_sq8_index_from_ip_index(ip, centre, scale) with ip an f32 index of the final corpus (same centroids, kept rows
+ *   in their lists, new rows in their arg-max list, lowest list id on ties) and the handle's own quantiser,
+ *   rihip_sq8_filter_set_tags of the final tag words, if the handle had tags, and
+ *   rihip_sq8_refine_attach_vectors(ip), if the handle had vectors (e_j and a_j are recomputed over the final rows against
+ *   the final stored codes, not updated incrementally: removing a row can shrink a maximum)
+ * would leave it in.  A flat-built handle (one list) keeps its one list.  set_id_map is reset to NULL.  Refused with
+ * RIHIP_ERR_ARG and *bad_kind = 1: an id is repeated inside drop_ids or add_ids, 2: an id to add is stored and not
+ * dropped by this call (*bad_id names one such id), 3: the result would be empty; more than 2^31 rows are refused.  A
+ * refused or failed call leaves the index searchable exactly as it was (the new arrays are built next to the old ones and
+ * swapped at the end; peak device memory: the old plus the new index).  A call that drops and adds nothing changes
+ * nothing.  One host synchronisation for the checks and one before the swap.  Captured serve graphs are stale afterwards
+ * (rihip_scratch_generation advances).
+ * assign: assign_out device int32 [n] = the list each of the n device rows X [n,d] would be added to (arg-max inner
+ * product with the centroids, lowest list id on ties); a flat-built handle gives 0 for every row.
+ * stats: cumulative {updates applied, rows dropped, rows added, code values clamped} since the handle was made. */
+int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                           const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add,
+                           int64_t* item_ids_out, int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped,
+                           int64_t* bad_id, int* bad_kind, void* stream);
+int rihip_sq8_update_assign(void* handle, const float* X, int64_t n, int32_t* assign_out, void* stream);
+int rihip_sq8_update_stats(void* handle, int64_t* out);     /* out: int64[4] */
+
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict
  * (ranker.py:174): raw score = sum over trees of the reached leaf value, float64.

@@ -162,6 +162,10 @@ SIGNATURES = {
     "rihip_sq8_refine_get_ranges": (C.c_int, [vp, vp, vp]),
     "rihip_sq8_refine_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "rihip_sq8_refine_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, c_i64, vp, vp, vp, vp, vp]),
+    "rihip_sq8_update_apply": (C.c_int, [vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp, C.POINTER(c_i64), C.POINTER(c_i64),
+                                         C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_int), vp]),
+    "rihip_sq8_update_assign": (C.c_int, [vp, vp, c_i64, vp, vp]),
+    "rihip_sq8_update_stats": (C.c_int, [vp, vp]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

@@ -26,6 +26,7 @@
 
 #include "search_kernels.h"
 #include "search_keys.h"
+#include "sq8_index.h"
 
 using namespace rihip_index;
 
@@ -41,44 +42,6 @@ constexpr int64_t SQ8_DENSE_AUTO = 1ll << 23;    // auto: dense while the batch'
 constexpr int SQ8_TARGET = 16 * RIHIP_NCU;      // wave work items aimed at (as the f32 list-major scan)
 constexpr int SQ8_SS = 16;                      // threshold sample: every 16th probed tile
 constexpr int64_t SQ8_CH = 4096;                // queries per internal pass at most
-
-struct Sq8Index {
-  int du = 0;        // caller's width (1 .. 128)
-  int dk = 0;        // width of the f32 side (centroids, coarse queries): 32 / 64 / 128, as the source index
-  int dpad = 0;      // bytes per code row: 64 / 128
-  int64_t N = 0, Np = 0;
-  int nlist = 0, nprobe = 1;
-  int8_t* codes = nullptr;        // [Np, dpad] physical order, padding rows and columns 0
-  float* centre = nullptr;        // [dpad] (columns >= du: 0)
-  float* scale = nullptr;         // [dpad] (columns >= du: 1)
-  float* C = nullptr;             // [nlist, dk]
-  int64_t* list_poff = nullptr;   // [nlist+1]
-  int* list_len_dev = nullptr;    // [nlist]
-  int64_t* row_ids = nullptr;     // [Np] original row, -1 = padding
-  std::vector<int64_t> list_len;
-  const int64_t* id_map = nullptr;   // not owned
-  int64_t stats[2] = {0, 0};         // queries searched thresholded, of those re-done dense
-  // filtered search (rihip_sq8_filter_set_tags): one 32-bit tag word per physical row, padding rows 0, or null
-  uint32_t* tags = nullptr;          // [Np]
-  int64_t filt_stats[2] = {0, 0};    // queries searched filtered, of those re-done dense
-  // refined search (rihip_sq8_refine_attach_vectors): the f32 rows next to the codes, or null
-  float* vec = nullptr;              // [N, dk] insertion-row order (stage 1 returns rows: no inverse map)
-  double* ref_e = nullptr;           // [dk] e_j = max_i |x_ij - (m_j + s_j c_ij)| over the stored rows
-  double* ref_a = nullptr;           // [dk] a_j = max_i |x_ij|
-  // scratch
-  DevBuf<int8_t> qhi, qlo, fhi, flo;
-  DevBuf<float> qt, qpad, fQ, coarse, thr;
-  DevBuf<double> qb;
-  DevBuf<uint64_t> cand, scand, fcand;
-  DevBuf<uint32_t> fpred;            // the predicates of one re-do chunk
-  // refined search: stage 1's output at k_scan, the f32 keys, valid candidates and smallest integer score per query
-  DevBuf<float> rs;
-  DevBuf<int64_t> rr;
-  DevBuf<int> ri, rnv, rcut;
-  DevBuf<uint64_t> rkeys;
-  DevBuf<int> count, probe_list, list_q, list_cnt, list_qoff, list_cur, work_off, plan, fail_flags, fail_list, n_fail;
-  int* h_nfail = nullptr;   // pinned
-};
 
 int64_t held_bytes(const Sq8Index* h) {
   return (int64_t)h->Np * h->dpad + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
@@ -154,11 +117,6 @@ __global__ void sq8_colrange_final_kernel(const float* __restrict__ part, int nb
   centre[j] = m; scale[j] = s;
 }
 
-__device__ __forceinline__ int sq8_code(float x, float m, float s) {
-  float v = rintf((x - m) / s);            // one f32 subtraction, one correctly rounded f32 division, round to nearest even
-  v = fminf(fmaxf(v, -127.f), 127.f);
-  return (int)v;
-}
 // four codes per thread; rows beyond n_src, padding rows (row_ids < 0) and columns >= dk are 0
 __global__ void sq8_encode_kernel(const float* __restrict__ X, const int64_t* __restrict__ row_ids, int64_t n_src, int64_t Np,
                                   int dk, int dpad, const float* __restrict__ centre, const float* __restrict__ scale,

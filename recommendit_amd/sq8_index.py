@@ -18,7 +18,14 @@ Filtered retrieval and seen-item exclusion, as on FAISSIndex: ``set_item_tags`` 
 (rihip_sq8_filter_* in recommendit_hip.h); ``exclude=`` / ``user_ids=`` over-fetch and drop each query's seen items on
 the device (exclusion.py).  Both compose with ``mode=``, ``refine=`` and ``return_cert=``.
 
-There is no NumPy or torch path for encode or search: everything runs in csrc/sq8.hip.
+Live catalogue, as on FAISSIndex and without one: ``add_items`` / ``remove_items`` / ``update_items`` are one repack
+of the code matrix on the device under the index's own centroids and its own quantiser (rihip_sq8_update_* in
+recommendit_hip.h, csrc/sq8_update.hip).  Kept rows keep their codes, new rows are encoded on the fly, tag words and
+attached vectors travel along, and the handle ends bit for bit where ``from_index`` of the final corpus with
+``ranges=quantizer()`` would leave it.  Neither centroids nor quantiser are retrained: ``update_stats()["clamped"]``
+counts the code values of added rows that fell outside the quantiser's range.
+
+There is no NumPy or torch path for encode, search or repack: everything runs in csrc/sq8.hip and csrc/sq8_update.hip.
 """
 from __future__ import annotations
 
@@ -127,6 +134,22 @@ class SQ8Index(ExcludingSearch):
         self._deficit: Optional[torch.Tensor] = None
         self._tags: Optional[np.ndarray] = None        # uint32 [ntotal] on the host, row order (the handle holds its own copy)
         self._pred_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}   # shared predicates already on the device
+                                                                          # (three words each: no row count in them)
+        self._last_clamped = 0                         # code values clamped by the last update that changed the index
+
+    @property
+    def _item_id_to_faiss_idx(self) -> Dict[int, int]:
+        """{item id: row}: the plain dict after from_index or load; after add_items / remove_items / update_items it is
+        rebuilt from item_ids on the first read (save() reads it), not inside the update"""
+        if self._id_map_stale:
+            self._id_map = {int(iid): row for row, iid in enumerate(self.item_ids.tolist())}
+            self._id_map_stale = False
+        return self._id_map
+
+    @_item_id_to_faiss_idx.setter
+    def _item_id_to_faiss_idx(self, value: Dict[int, int]) -> None:
+        self._id_map = value
+        self._id_map_stale = False
 
     # -- build ----------------------------------------------------------------------------------------------------
     @classmethod
@@ -170,6 +193,131 @@ class SQ8Index(ExcludingSearch):
         if faiss_index._tags is not None:
             obj.set_item_tags(faiss_index.item_tags())
         return obj
+
+    # -- live catalogue (FAISSIndex's add_items / remove_items / update_items on the 8-bit index) ---------------------
+    # Every call is ONE repack of the code matrix on the device under the index's own centroids and its own quantiser
+    # (csrc/sq8_update.hip): O(N), so batch the changes; no f32 index is needed.  Neither the centroids nor the
+    # quantiser is retrained: watch update_stats()["clamped"], the code values of added rows that fell outside the
+    # quantiser's range.  The handle ends bit for bit in the state from_index(f32 index of the final corpus with the same
+    # centroids and lists, ranges=self.quantizer()) would give, tags and attached vectors included.
+    def _apply_update(self, drop_ids, x_add: Optional[torch.Tensor], add_ids, tags=None) -> Tuple[int, int]:
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        dev = self._item_ids_dev.device
+
+        def ids_dev(ids):
+            if ids is None:
+                return None, 0
+            if isinstance(ids, torch.Tensor):
+                t = ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+            else:
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))).to(dev)
+            return t, int(t.shape[0])
+
+        drop, n_drop = ids_dev(drop_ids)
+        add, n_add = ids_dev(add_ids)
+        x = None
+        if n_add or x_add is not None:
+            if x_add.dim() != 2 or x_add.shape[1] != self.embed_dim:
+                raise ValueError(f"Expected embeddings [n, {self.embed_dim}], got {tuple(x_add.shape)}")
+            if x_add.shape[0] != n_add:
+                raise ValueError(f"{x_add.shape[0]} embeddings for {n_add} item ids")
+            x = x_add.to(device=dev, dtype=torch.float32).contiguous()
+        if tags is not None:
+            if self._tags is None:
+                raise ValueError("tags= on an index without tags: call set_item_tags() first")
+            tags = _tag_words(tags, n_add)
+        old_ids, old_tags = self._item_ids_dev, self._tags
+        if old_tags is not None and tags is None and n_add:
+            # the appended rows take the word their id carried before the call, else 0 (positions found on the device)
+            srt, order = torch.sort(old_ids)
+            pos = torch.searchsorted(srt, add).clamp(max=old_ids.shape[0] - 1)
+            hit, rows = (srt[pos] == add).cpu().numpy(), order[pos].cpu().numpy()
+            tags = np.where(hit, old_tags[rows], np.uint32(0)).astype(np.uint32)
+        t_dev = None
+        if old_tags is not None and n_add:
+            t_dev = torch.from_numpy(np.ascontiguousarray(tags).view(np.int32)).to(dev)
+        n_old = self.index.ntotal
+        out = torch.empty(n_old + n_add, dtype=torch.int64, device=dev)
+        n_total, n_dropped, n_clamped = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        bad_id, bad_kind = C.c_int64(0), C.c_int(0)
+        rc = L.lib().rihip_sq8_update_apply(self.index._h, self._item_ids_dev.data_ptr(), L.ptr(drop) if n_drop else None,
+                                            n_drop, L.ptr(x) if n_add else None, L.ptr(add) if n_add else None,
+                                            L.ptr(t_dev), n_add, out.data_ptr(), C.byref(n_total), C.byref(n_dropped),
+                                            C.byref(n_clamped), C.byref(bad_id), C.byref(bad_kind), L.stream_ptr())
+        if rc != 0 and bad_kind.value != 0:
+            raise ValueError(L.lib().rihip_last_error().decode("utf-8", "replace"))
+        L.check(rc, "sq8_update_apply")
+        if n_dropped.value == 0 and n_add == 0:
+            return 0, 0
+        logger.info("SQ8 index updated: %d rows dropped, %d added, %d code values clamped", n_dropped.value, n_add,
+                    n_clamped.value)
+        self._last_clamped = int(n_clamped.value)
+        self._item_ids_dev = out[:n_total.value]
+        self.item_ids = self._item_ids_dev.cpu().numpy()
+        self._id_map_stale = True
+        if old_tags is not None:
+            # the handle moved its own copy of the words inside the repack; the host mirror follows
+            keep = np.ones(n_old, dtype=bool) if n_drop == 0 else (~torch.isin(old_ids, drop)).cpu().numpy()
+            self._tags = np.ascontiguousarray(np.concatenate([old_tags[keep]] + ([tags] if n_add else [])), dtype=np.uint32)
+            assert self._tags.shape[0] == n_total.value
+        return int(n_dropped.value), n_add
+
+    def _normalised(self, embeddings: np.ndarray) -> torch.Tensor:
+        embeddings = np.asarray(embeddings)
+        if embeddings.dtype != np.float32:
+            raise ValueError("Embeddings must be float32")
+        if embeddings.ndim != 2 or embeddings.shape[1] != self.embed_dim:
+            raise ValueError(f"Expected embeddings [n, {self.embed_dim}], got {embeddings.shape}")
+        norms = np.linalg.norm(embeddings, axis=1, keepdims=True)
+        return torch.from_numpy(np.ascontiguousarray(embeddings / np.maximum(norms, 1e-8), dtype=np.float32)).to(L.device())
+
+    def add_items(self, embeddings: np.ndarray, item_ids, tags=None) -> int:
+        """Append f32 [n, embed_dim] rows (normalised as build_ivf_index does) as rows N .. N+n-1 with these ids; -> n.
+        ValueError for an id that is already stored or repeated.  tags: uint32 [n] tag words of the new rows of a tagged
+        index (0 when omitted).  The rows are encoded with the index's own quantiser, which is not retrained."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        return self.add_items_device(self._normalised(embeddings), item_ids, tags=tags)
+
+    def add_items_device(self, x_dev: torch.Tensor, item_ids, tags=None) -> int:
+        """add_items for rows that are already normalised and on the device"""
+        return self._apply_update(None, x_dev, item_ids, tags)[1]
+
+    def remove_items(self, item_ids) -> int:
+        """Remove the stored items with these ids (ids that are not stored are ignored, as faiss remove_ids does);
+        surviving rows keep their relative order and are renumbered densely.  -> number of items removed"""
+        return self._apply_update(item_ids, None, None)[0]
+
+    def update_items(self, embeddings: np.ndarray, item_ids, tags=None) -> Tuple[int, int]:
+        """Upsert in one repack: a stored id is dropped and its new vector appended, an unknown id is appended; the
+        result is that of remove_items(ids) followed by add_items(embeddings, ids).  -> (replaced, added).  tags: uint32
+        [n] tag words of these ids on a tagged index; omitted, a replaced id keeps its word and a new id gets 0."""
+        if self.index is None:
+            raise RuntimeError("Index not built.")
+        replaced, n = self._apply_update(item_ids, self._normalised(embeddings), item_ids, tags)
+        return replaced, n - replaced
+
+    def assign_lists(self, x_dev: torch.Tensor) -> torch.Tensor:
+        """int32 [n] on device: the list each f32 [n,d] device row would be added to (arg-max inner product with the
+        centroids, lowest list on ties; all 0 for an index encoded from an exact FAISSIndex)."""
+        h = self._built()
+        x = x_dev.to(device=L.device(), dtype=torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.embed_dim:
+            raise ValueError(f"Expected embeddings [n, {self.embed_dim}], got {tuple(x.shape)}")
+        out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+        if x.shape[0]:
+            L.check(L.lib().rihip_sq8_update_assign(h._h, x.data_ptr(), x.shape[0], out.data_ptr(), L.stream_ptr()),
+                    "sq8_update_assign")
+        return out
+
+    def update_stats(self) -> Dict:
+        """cumulative since the handle was made: updates that changed the index, rows dropped, rows added, and the code
+        values of added rows that the frozen quantiser clamped to +-127 (its drift signal)"""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().rihip_sq8_update_stats(self._built()._h, out), "sq8_update_stats")
+        return {"updates": int(out[0]), "dropped": int(out[1]), "added": int(out[2]), "clamped": int(out[3]),
+                "last_clamped": self._last_clamped}
 
     # -- item tags (filtered retrieval; FAISSIndex's semantics and error texts) ---------------------------------------
     def _push_tags(self) -> None:
