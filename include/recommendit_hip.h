@@ -591,6 +591,38 @@ int rihip_ip_index_search_filtered(void* handle, const float* Q, int64_t nq, int
                                    int64_t pred_stride, float* out_scores, int64_t* out_rows, void* stream);
 int rihip_ip_index_filtered_stats(void* handle, int64_t* out);
 int rihip_ip_index_search_stats(void* handle, int64_t* out);     /* out: int64[12] */
+/* Seen-item exclusion inside the scan (not in the reference; the second implementation next to the over-fetch of
+ * rihip_exclude_topk): query q of user u = user_ids[q] never returns a row whose item id is in row u of the seen lists.
+ * The result is the first k rows, in the plain search's order (score descending, lower row first on ties), among the rows
+ * of the probed lists (flat: all rows) that are not excluded and, with pred_dev, pass the predicate; -inf / -1 padded when
+ * fewer qualify.  Scores and rows are bit for bit those rihip_ip_index_search reports for the same row.  There is no
+ * over-fetch, so k + |seen| is not bounded by rihip_ip_index_max_k().
+ * Seen lists: seen_offsets device i64 [n_seen_rows + 1], seen_items device i32 item ids, ascending and unique per row
+ * (the convention of rihip_exclude_topk); user_ids device i64 [nq], NULL = row q, an id outside [0, n_seen_rows) excludes
+ * nothing.  row_of: device i32 [n_ids], item id -> insertion row, -1 = not stored; ids outside the table or mapped to -1
+ * are ignored.  pred_dev / pred_stride as in search_filtered; pred_dev may be NULL (no tag filter, tags not needed).
+ * The scans test one bit per (query, row): bit p & 31 of word q * W + (p >> 5), W = ceil(P / 32), is set iff the row at
+ * scan position p is excluded for query q (flat: p = row, P = ntotal; IVF: p = the list-major physical position, P = the
+ * padded row count).  The mask is scratch of the handle, all zero between calls: a chunk of queries sets its bits,
+ * searches and clears the words it touched.  The batch is taken in chunks of queries whose mask fits the budget
+ * (set_exclusion_budget, bytes; 0 restores the default of 64 MiB; at least one query per chunk); results do not depend on
+ * it.  The search goes the way a filtered one goes (synchronous exactness check, all-f32 scan on a large flat index).
+ * RIHIP_ERR_STATE while a deferred search is pending or with pred_dev on an index without tags; a refused call leaves the
+ * handle as it was.
+ * exclusion_mask_words: W.   exclusion_mask: writes the mask [nq, W] the search would build to out_mask (device).
+ * exclusion_scratch_nonzero: non-zero words of the handle's mask scratch (0 between calls; synchronises).
+ * exclusion_stats: cumulative {queries searched this way, of those re-done by the exact fallback, mask chunks}. */
+int rihip_ip_index_search_excluding(void* handle, const float* Q, int64_t nq, int k, const int64_t* user_ids,
+                                    const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items,
+                                    const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev, int64_t pred_stride,
+                                    float* out_scores, int64_t* out_rows, void* stream);
+int rihip_ip_index_exclusion_mask_words(void* handle, int64_t* words_per_query);
+int rihip_ip_index_exclusion_mask(void* handle, int64_t nq, const int64_t* user_ids, const int64_t* seen_offsets,
+                                  int64_t n_seen_rows, const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                                  uint32_t* out_mask, void* stream);
+int rihip_ip_index_set_exclusion_budget(void* handle, int64_t bytes);
+int rihip_ip_index_exclusion_scratch_nonzero(void* handle, int64_t* n_words, void* stream);
+int rihip_ip_index_exclusion_stats(void* handle, int64_t* out);  /* out: int64[3] */
 
 /* ---- 8-bit scalar-quantised index (faiss IndexScalarQuantizer / IndexIVFScalarQuantizer at 8 bits; the reference's
  * FAISSIndex has none) ----------------------------------------------------------------------
@@ -715,6 +747,41 @@ int rihip_sq8_refine_search(void* handle, const float* Q, int64_t nq, int k, int
 int rihip_sq8_refine_search_filtered(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode,
                                      const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
                                      uint8_t* out_cert, double* out_bound, void* stream);
+
+/* ---- SQ8 index: seen-item exclusion inside the int8 scan (the SQ8 side of rihip_ip_index_search_excluding; the calls
+ * take an sq8_index handle and carry the prefix rihip_sq8_exclude_*, the refined one rihip_sq8_refine_*).
+ * exclude_search: rihip_sq8_index_search / rihip_sq8_filter_search (pred_dev non-NULL; NULL needs no tags) over the rows
+ * that are not excluded for the query's user: the first k of the probed rows by (S descending, row ascending) among the
+ * rows whose item id is not in the user's seen list and that pass the predicate; -inf / -1 / INT32_MIN padded.  Scores,
+ * integer scores and rows are bit for bit those the plain search reports for the same row, in every mode.  user_ids,
+ * seen_offsets, seen_items, row_of and the mask layout are those of rihip_ip_index_search_excluding; scan positions are the
+ * handle's physical rows (a flat-built handle is one list, padded to 64 rows), W = ceil(padded rows / 32).  The mask is
+ * handle scratch, all zero between calls (set, search, clear the touched words per chunk of queries); the chunk is the
+ * smaller of the search's own and what the budget holds.  rihip_sq8_update_apply drops the row -> position table with the
+ * row order; it is rebuilt on the next call.  RIHIP_ERR_STATE with pred_dev on an index without tags; a refused call
+ * leaves the handle as it was.
+ * refine_search_excluding: rihip_sq8_refine_search whose stage 1 is exclude_search at k_scan.  Stage 2, f, the bound and
+ * the certificate are the same kernels; "stage 1 returned fewer than k_scan valid rows" then means that every probed row
+ * that is not excluded (and passes) was re-scored, so cert = 1 implies: the output equals the top k by (f, row) over all
+ * such rows of the probed lists.
+ * exclude_mask_words / exclude_mask / exclude_set_exclusion_budget / exclude_scratch_nonzero / exclude_exclusion_stats:
+ * as the rihip_ip_index_exclusion_* calls. */
+int rihip_sq8_exclude_search(void* handle, const float* Q, int64_t nq, int k, int mode, const int64_t* user_ids,
+                             const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items,
+                             const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev, int64_t pred_stride,
+                             float* out_scores, int64_t* out_rows, int32_t* out_iscores, void* stream);
+int rihip_sq8_refine_search_excluding(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode,
+                                      const int64_t* user_ids, const int64_t* seen_offsets, int64_t n_seen_rows,
+                                      const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                                      const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
+                                      uint8_t* out_cert, double* out_bound, void* stream);
+int rihip_sq8_exclude_mask_words(void* handle, int64_t* words_per_query);
+int rihip_sq8_exclude_mask(void* handle, int64_t nq, const int64_t* user_ids, const int64_t* seen_offsets,
+                           int64_t n_seen_rows, const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                           uint32_t* out_mask, void* stream);
+int rihip_sq8_exclude_set_exclusion_budget(void* handle, int64_t bytes);
+int rihip_sq8_exclude_scratch_nonzero(void* handle, int64_t* n_words, void* stream);
+int rihip_sq8_exclude_exclusion_stats(void* handle, int64_t* out);   /* out: int64[3] */
 
 /* ---- SQ8 index: add / remove / replace items without the f32 source and without re-encoding the rows that stay (what
  * rihip_ip_index_update is to the ip_index).  The calls take an sq8_index handle and carry a prefix of their own,

@@ -138,6 +138,12 @@ SIGNATURES = {
     "rihip_ip_index_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, vp, c_i64, vp, vp, vp]),
     "rihip_ip_index_filtered_stats": (C.c_int, [vp, vp]),
     "rihip_ip_index_search_stats": (C.c_int, [vp, vp]),
+    "rihip_ip_index_search_excluding": (C.c_int, [vp, vp, c_i64, C.c_int, vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, vp, vp]),
+    "rihip_ip_index_exclusion_mask_words": (C.c_int, [vp, C.POINTER(c_i64)]),
+    "rihip_ip_index_exclusion_mask": (C.c_int, [vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp, vp]),
+    "rihip_ip_index_set_exclusion_budget": (C.c_int, [vp, c_i64]),
+    "rihip_ip_index_exclusion_scratch_nonzero": (C.c_int, [vp, C.POINTER(c_i64), vp]),
+    "rihip_ip_index_exclusion_stats": (C.c_int, [vp, vp]),
     "rihip_sq8_index_from_ip_index": (C.c_int, [vp, vp, vp, C.POINTER(vp), vp]),
     "rihip_sq8_index_destroy": (C.c_int, [vp]),
     "rihip_sq8_index_ntotal": (c_i64, [vp]),
@@ -162,6 +168,15 @@ SIGNATURES = {
     "rihip_sq8_refine_get_ranges": (C.c_int, [vp, vp, vp]),
     "rihip_sq8_refine_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "rihip_sq8_refine_search_filtered": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, c_i64, vp, vp, vp, vp, vp]),
+    "rihip_sq8_exclude_search": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, vp,
+                                           vp, vp]),
+    "rihip_sq8_refine_search_excluding": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, c_i64, vp, vp, c_i64,
+                                                    vp, c_i64, vp, vp, vp, vp, vp]),
+    "rihip_sq8_exclude_mask_words": (C.c_int, [vp, C.POINTER(c_i64)]),
+    "rihip_sq8_exclude_mask": (C.c_int, [vp, c_i64, vp, vp, c_i64, vp, vp, c_i64, vp, vp]),
+    "rihip_sq8_exclude_set_exclusion_budget": (C.c_int, [vp, c_i64]),
+    "rihip_sq8_exclude_scratch_nonzero": (C.c_int, [vp, C.POINTER(c_i64), vp]),
+    "rihip_sq8_exclude_exclusion_stats": (C.c_int, [vp, vp]),
     "rihip_sq8_update_apply": (C.c_int, [vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp, C.POINTER(c_i64), C.POINTER(c_i64),
                                          C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_int), vp]),
     "rihip_sq8_update_assign": (C.c_int, [vp, vp, c_i64, vp, vp]),

@@ -12,6 +12,7 @@ constexpr int TR = 64;         // list granule: every IVF list is padded to a mu
 constexpr int TRS = 32;        // corpus rows per LDS tile of the exact-f32 scan kernel
 constexpr int K_MAX = 16384;   // largest k served by the device select/sort buffer (128 KiB of LDS)
 constexpr int NLIST_MAX = 2048;  // probe bitset: 64 words per query
+constexpr int64_t XMASK_BUDGET = 64ll << 20;   // bytes of exclusion-mask scratch a search may hold: 512 queries at 1 M rows
 // slots of IpIndex::search_stats, in the order rihip_ip_index_search_stats reports them (recommendit_hip.h)
 enum SearchStat {
   ST_FLAT_DENSE = 0, ST_FLAT_F32, ST_FLAT_FUSED, ST_FLAT_UNFUSED, ST_IVF_UNFILTERED, ST_IVF_THRESHOLDED, ST_SAMPLE_TOP,
@@ -61,6 +62,15 @@ struct IpIndex {
   // (flat: [N] row order; IVF: [Np] physical order, padding slots 0); null = untagged
   uint32_t* tags = nullptr;
   int64_t filt_stats[2] = {0, 0};   // queries searched filtered, of those re-done by the exact fallback
+  // seen-item exclusion inside the scan (rihip_ip_index_search_excluding): bit p & 31 of xmask[q * W + (p >> 5)],
+  // W = ceil(rows scanned / 32), is set iff the row at scan position p is excluded for query q of the chunk in flight.
+  // The scratch is all zero between calls: a chunk sets its bits, searches and clears exactly the words it touched
+  // (xmask_dirty: a call that failed in between; the next one zeroes the whole buffer first).
+  int* inv_pos = nullptr;           // IVF: [N] original row -> physical position; built on first use (drop_inv_pos)
+  DevBuf<uint32_t> xmask;
+  bool xmask_dirty = false;
+  int64_t xmask_budget = XMASK_BUDGET;
+  int64_t excl_stats[3] = {0, 0, 0};   // queries searched this way, of those re-done exactly, mask chunks
   // what the search driver did since the handle was made (rihip_ip_index_search_stats; slots: SearchStat).  Host
   // counters of the driver functions in topk.hip: no kernel reads or writes them
   int64_t search_stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -89,9 +99,15 @@ inline void drop_tags(IpIndex* h) {
   if (h->tags) { hipFree(h->tags); h->tags = nullptr; }
 }
 
+// ... and the inverse of row_ids the exclusion mask is built through
+inline void drop_inv_pos(IpIndex* h) {
+  if (h->inv_pos) { hipFree(h->inv_pos); h->inv_pos = nullptr; }
+}
+
 inline void free_index_arrays(IpIndex* h) {
   rihip_bump_generation();
   drop_tags(h);
+  drop_inv_pos(h);
   hipFree(h->X); hipFree(h->C); hipFree(h->tile_list); hipFree(h->list_poff); hipFree(h->list_len_dev); hipFree(h->row_ids); hipFree(h->Xb);
   h->X = nullptr; h->C = nullptr; h->tile_list = nullptr; h->list_poff = nullptr; h->list_len_dev = nullptr; h->row_ids = nullptr; h->Xb = nullptr;
   h->N = 0; h->Np = 0; h->ivf = false; h->nlist = 0; h->list_len.clear();

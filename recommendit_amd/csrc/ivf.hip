@@ -312,6 +312,7 @@ namespace rihip_index {
 int derive_ivf_aux(IpIndex* h, hipStream_t st) {
   const int nlist = h->nlist;
   drop_tags(h);   // (a new physical order)
+  drop_inv_pos(h);
   std::vector<int64_t> poff(nlist + 1, 0);
   std::vector<int> len(nlist, 0);
   for (int c = 0; c < nlist; ++c) {

@@ -210,8 +210,12 @@ __global__ __launch_bounds__(256, 2) void ivf_prepare_small_kernel(PrepSmallArgs
 
 // FILT: the tile's 32 tag words are contiguous in the physical order the handle keeps them in; every lane loads the four
 // 16-byte runs of its accumulator rows before the MFMA chain (two addresses per wave and load, in flight under the chain).
-template <int D, bool FILT = false>
+// FM (search_keys.h): FM_TAGS as above; FM_TAGS_MASK / FM_MASK add the seen-item mask -- the tile is one aligned word of the
+// lane's query, loaded where the tag words are (in flight under the chain); FM_MASK compiles the tag test out, so an
+// untagged index is excluded from as well.  FM_NONE and FM_TAGS are the kernels as they were.
+template <int D, int FM = FM_NONE>
 __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
+  constexpr bool FILT = FM == FM_TAGS || FM == FM_TAGS_MASK, XM = FM == FM_TAGS_MASK || FM == FM_MASK;
   constexpr int KB = D / 8, LDX = D + 4;
   constexpr int NL = (TRS * (D / 4)) / 64;  // 16-byte pieces per lane per tile (fully coalesced 1-KiB wave loads)
   // wave-private staging tile: no workgroup barrier anywhere (a wave's LDS operations execute in order)
@@ -250,6 +254,16 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
   Pred pr{0u, 0u, 0u};
   if constexpr (FILT) pr = load_pred(a.pred, q, a.pred_stride);
   uint4 tw[4];
+  const uint32_t* my_mask = nullptr;   // XM: the lane's query's mask row
+  uint32_t mw = 0u;
+  if constexpr (XM) my_mask = a.xmask + (size_t)(a.xrow ? a.xrow[q] : q) * a.xW;
+  // FILT / XM: may accumulator row r of the lane be a candidate?
+  auto row_ok = [&](int r) -> bool {
+    bool ok = true;
+    if constexpr (FILT) ok = pr.pass(tag_of(tw, r));
+    if constexpr (XM) ok = ok && !((mw >> acc_row(r, lane)) & 1u);
+    return ok;
+  };
   // dense mode (threshold sample): slot = (pair, sampled tile, row): no atomics, no row-id gather
   uint64_t* my_dense = a.dense_cap > 0 ? a.cand + (size_t)pair * a.dense_cap : nullptr;
   const int64_t per = tpi;
@@ -294,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
         const int rr = acc_row(r, lane);
         const int64_t sl = i * TRS + rr;
         if (sl < a.dense_cap)
-          my_dense[sl] = (rr < n_ok && (!FILT || pr.pass(tag_of(tw, r))))
+          my_dense[sl] = (rr < n_ok && row_ok(r))
                              ? make_key(acc[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
       }
       return;
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
     unsigned hits = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (acc_row(r, lane) < n_ok && acc[r] >= thr && (!FILT || pr.pass(tag_of(tw, r)))) hits |= (1u << r);
+      if (acc_row(r, lane) < n_ok && acc[r] >= thr && row_ok(r)) hits |= (1u << r);
     if (hits) {
       int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
 #pragma unroll
@@ -326,6 +340,7 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_lm_kernel(LmArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) tw[g] = tp[2 * g];
     }
+    if constexpr (XM) mw = my_mask[(p0 + i * tstep * TRS) >> 5];
     const f32x16 acc = chain();
     if (more) store_tile();              // after the chain's LDS reads (same wave: in order)
     emit(acc, i);
@@ -365,10 +380,12 @@ void launch_ivf_scatter(const int* probe_list, int64_t n_pairs, int nprobe, int*
 
 int launch_ivf_scan(int d, const LmArgs& a, unsigned grid, hipStream_t st) {
   RCCHK(dispatch_d(d, [&](auto D) {
-    if (a.tags) hipLaunchKernelGGL((ivf_scan_lm_kernel<decltype(D)::value, true>), dim3(grid), dim3(256), 0, st, a);
+    if (a.xmask && a.tags) hipLaunchKernelGGL((ivf_scan_lm_kernel<decltype(D)::value, FM_TAGS_MASK>), dim3(grid), dim3(256), 0, st, a);
+    else if (a.xmask) hipLaunchKernelGGL((ivf_scan_lm_kernel<decltype(D)::value, FM_MASK>), dim3(grid), dim3(256), 0, st, a);
+    else if (a.tags) hipLaunchKernelGGL((ivf_scan_lm_kernel<decltype(D)::value, FM_TAGS>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((ivf_scan_lm_kernel<decltype(D)::value>), dim3(grid), dim3(256), 0, st, a);
   }));
-  return check_launch(a.tags ? "filtered ivf scan" : "ivf scan");
+  return check_launch(a.xmask ? "masked ivf scan" : a.tags ? "filtered ivf scan" : "ivf scan");
 }
 
 }  // namespace rihip_index

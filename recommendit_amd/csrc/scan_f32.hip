@@ -23,9 +23,13 @@ __device__ __forceinline__ uint32_t* tag_tiles() {   // LDS only in the filtered
 // the threshold test / candidate emission of tile t, one barrier per tile.
 // FILT: every tile brings its 32 tag words along through the same prefetch (one coalesced 128-byte load by 32 threads, a
 // slot of LDS per stage); emit tests the lane's query predicate against them.  A failing row is key 0 (below every score)
-// in a dense slot and simply no hit in append mode.  FILT = false compiles to the unfiltered kernel as it was.
-template <int D, bool FILT = false>
+// in a dense slot and simply no hit in append mode.  FM_NONE compiles to the unfiltered kernel as it was.
+// FM_TAGS_MASK / FM_MASK (seen-item exclusion, search_exclude.hip): a stride-1 tile is one aligned mask word of the lane's
+// query, loaded two tiles ahead with the operand prefetch and handed down a register per stage; a strided pass (the
+// threshold sample) scans rows that are not adjacent and reads each row's own bit in emit.  FM_MASK compiles the tag test out.
+template <int D, int FM = FM_NONE>
 __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
+  constexpr bool FILT = FM == FM_TAGS || FM == FM_TAGS_MASK, XM = FM == FM_TAGS_MASK || FM == FM_MASK;
   constexpr int LDX = D + 4, KB = D / 8;
   constexpr int EPK = 16 / KB > 0 ? 16 / KB : 1;
   constexpr int NV = (TRS * (D / 4) + 255) / 256;
@@ -45,6 +49,10 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
   Pred pr{0u, 0u, 0u};
   if constexpr (FILT) pr = load_pred(a.pred, qrow, a.pred_stride);
   uint32_t tg = 0u;   // FILT: staged tag word (threads 0..31)
+  const uint32_t* my_mask = nullptr;   // XM: the lane's query's mask row
+  uint32_t mw0 = 0u, mw1 = 0u, mw2 = 0u;   // XM, stride 1: mask words of the tile in emit, the next one and the prefetched one
+  if constexpr (XM) my_mask = a.xmask + (size_t)(a.xrow ? a.xrow[qrow] : qrow) * a.xW;
+  const bool x_tile = XM && a.row_stride == 1;
 
   const int64_t n_seq = (a.n_virtual + TRS - 1) / TRS;
   const int64_t per = (n_seq + a.nsplit - 1) / a.nsplit;
@@ -70,6 +78,9 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
       tg = 0u;
       if (tid < TRS && v_base + tid < a.n_virtual) tg = a.tags[(size_t)((v_base + tid) * a.row_stride)];
     }
+    if constexpr (XM) {
+      if (x_tile) mw2 = my_mask[tile];
+    }
   };
   auto store_tile = [&](int buf) {
 #pragma unroll
@@ -90,11 +101,23 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) tw[g] = *reinterpret_cast<const uint4*>(&Ts[buf * TRS + 8 * g + 4 * hh]);
     }
+    // XM: is accumulator row r of the lane (virtual row v < n_virtual) excluded for the lane's query?
+    auto masked = [&](int r, int64_t v) -> bool {
+      if (x_tile) return (mw0 >> acc_row(r, lane)) & 1u;
+      const int64_t p = v * a.row_stride;
+      return (my_mask[p >> 5] >> (p & 31)) & 1u;
+    };
     if (a.dense) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t v = v_base + acc_row(r, lane);
-        if constexpr (FILT) {
+        if constexpr (XM) {
+          if (v < a.n_virtual) {
+            bool ok = !masked(r, v);
+            if constexpr (FILT) ok = ok && pr.pass(tag_of(tw, r));
+            my_cand[v] = ok ? make_key(acc[r], (uint32_t)v) : 0ull;
+          }
+        } else if constexpr (FILT) {
           if (v < a.n_virtual) my_cand[v] = pr.pass(tag_of(tw, r)) ? make_key(acc[r], (uint32_t)v) : 0ull;
         } else {
           if (v < a.n_virtual) my_cand[v] = make_key(acc[r], (uint32_t)v);
@@ -106,7 +129,13 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
     unsigned hits = 0;  // per-lane aggregation: one atomic per (query, tile) that has survivors
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      if constexpr (FILT) {
+      if constexpr (XM) {
+        if (acc_row(r, lane) < n_ok && acc[r] >= thr) {
+          bool ok = !masked(r, v_base + acc_row(r, lane));
+          if constexpr (FILT) ok = ok && pr.pass(tag_of(tw, r));
+          if (ok) hits |= (1u << r);
+        }
+      } else if constexpr (FILT) {
         if (acc_row(r, lane) < n_ok && acc[r] >= thr && pr.pass(tag_of(tw, r))) hits |= (1u << r);
       } else {
         if (acc_row(r, lane) < n_ok && acc[r] >= thr) hits |= (1u << r);
@@ -137,9 +166,11 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
 
   load_tile(tile_at(i0));
   store_tile(0);
+  if constexpr (XM) mw0 = mw2;
   if (i0 + 1 < i1) {
     load_tile(tile_at(i0 + 1));
     store_tile(1);
+    if constexpr (XM) mw1 = mw2;
   }
   __syncthreads();
   f32x16 st = zero16();
@@ -156,14 +187,17 @@ __global__ __launch_bounds__(256, 2) void scan_kernel(ScanArgs a) {
     emit(st, tile_at(i), it);
     if (has_pre) store_tile(pre);
     st = sn;
+    if constexpr (XM) { mw0 = mw1; mw1 = mw2; }
     __syncthreads();
   }
 }
 
 template <int D>
 void launch_scan_d(const ScanArgs& a, dim3 grid, hipStream_t st) {
-  if (a.tags) hipLaunchKernelGGL((scan_kernel<D, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((scan_kernel<D, false>), grid, dim3(256), 0, st, a);
+  if (a.xmask && a.tags) hipLaunchKernelGGL((scan_kernel<D, FM_TAGS_MASK>), grid, dim3(256), 0, st, a);
+  else if (a.xmask) hipLaunchKernelGGL((scan_kernel<D, FM_MASK>), grid, dim3(256), 0, st, a);
+  else if (a.tags) hipLaunchKernelGGL((scan_kernel<D, FM_TAGS>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((scan_kernel<D, FM_NONE>), grid, dim3(256), 0, st, a);
 }
 
 }  // namespace

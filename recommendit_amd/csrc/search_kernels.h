@@ -38,6 +38,11 @@ struct ScanArgs {
   const uint32_t* tags;       // [N] tag word of every corpus row
   const uint32_t* pred;       // query q's predicate (any_of, all_of, none_of) at pred[q * pred_stride]
   int pred_stride;            // 3 = one per query, 0 = one shared by the batch
+  // seen-item exclusion (the masked instantiations of scan_kernel): row v * row_stride is excluded for query q iff bit
+  // (row & 31) of xmask[mrow * xW + (row >> 5)] is set, mrow = xrow ? xrow[q] : q (xrow: the re-do's original queries)
+  const uint32_t* xmask;
+  int64_t xW;
+  const int* xrow;
 };
 
 // ---- finalize: radix-select the k_sel best keys of query q, sort them, emit -------------------
@@ -117,6 +122,11 @@ struct LmArgs {
   const uint32_t* tags;      // [Np] tag word of every physical row (padding slots 0)
   const uint32_t* pred;      // query q's predicate at pred[q * pred_stride]
   int pred_stride;
+  // seen-item exclusion (the masked instantiations): a 32-row tile at physical row p is the one aligned word
+  // xmask[mrow * xW + (p >> 5)] of every query, mrow = xrow ? xrow[q] : q (xrow: the re-do's original queries)
+  const uint32_t* xmask;
+  int64_t xW;
+  const int* xrow;
 };
 
 // one-launch IVF prepare of a small query batch (ivf_prepare_small_kernel, ivf_search.hip)
@@ -133,7 +143,8 @@ inline int check_launch(const char* what) {
   return RIHIP_OK;
 }
 
-// ---- scan_f32.hip: exact-f32 scan (a.tags != null: the filtered instantiation); grid = (query blocks, corpus splits)
+// ---- scan_f32.hip: exact-f32 scan (a.tags != null: the filtered instantiation, a.xmask != null: the masked ones);
+// grid = (query blocks, corpus splits)
 int launch_scan(int d, const ScanArgs& a, dim3 grid, hipStream_t st);
 
 // ---- scan_bf16.hip: bf16 filter (mode 0) and its sample passes (1: dense, 2: register top-T) over a.nsplit corpus splits
@@ -160,7 +171,7 @@ void launch_ivf_select(const float* cs, int64_t nq, int nlist, int nprobe, int* 
 void launch_ivf_plan(const int* list_cnt, const int64_t* list_poff, int nlist, int tile_step, int target_items, int* list_qoff,
                      int* list_cur, int* work_off, int* plan, int* count, int64_t n_count, hipStream_t st);
 void launch_ivf_scatter(const int* probe_list, int64_t n_pairs, int nprobe, int* list_cur, int* list_q, hipStream_t st);
-int launch_ivf_scan(int d, const LmArgs& a, unsigned grid, hipStream_t st);   // a.tags != null: filtered
+int launch_ivf_scan(int d, const LmArgs& a, unsigned grid, hipStream_t st);   // a.tags != null: filtered, a.xmask != null: masked
 
 // ---- search_filter.hip: helpers of the filtered search
 // n_pass[q] (pred_stride 3) or n_pass[0] (one shared predicate, pred_stride 0) = rows of the flat index that pass
@@ -173,5 +184,32 @@ void launch_count_pass_ivf(const uint32_t* tags, const int64_t* list_poff, const
 void launch_filt_thr(float* thr, const int* n_pass, int n_pass_stride, int64_t cap, int64_t nq, hipStream_t st);
 void launch_gather_pred(const uint32_t* pred, const int* idx, int n, uint32_t* out, hipStream_t st);
 void launch_tags_to_scan_order(const uint32_t* by_row, const int64_t* row_ids, int64_t Np, uint32_t* out, hipStream_t st);
+
+
+// ---- search_exclude.hip: the per-query exclusion mask of a seen-item search inside the scan
+// the seen lists every mask is built from (device arrays of the caller); query q reads row user_ids[q] (null: row q)
+struct SeenArgs {
+  const int64_t* user_ids;      // [nq] or null; an id outside [0, n_seen_rows) excludes nothing
+  const int64_t* seen_offsets;  // [n_seen_rows + 1]
+  int64_t n_seen_rows;
+  const int32_t* seen_items;    // item ids, ascending and unique per row
+  const int32_t* row_of;        // [n_ids] item id -> original row, -1 absent
+  int64_t n_ids;
+};
+// inv_pos[row_ids[p]] = p for the real rows of the physical order
+void launch_inv_pos(const int64_t* row_ids, int64_t Np, int* inv_pos, hipStream_t st);
+// queries q0 .. q0 + nq of `s` -> mask rows 0 .. nq: set = 1 ORs the bit of every stored seen item in, set = 0 zeroes the
+// words those bits live in.  inv_pos null: position = row (flat index)
+void launch_xmask(const SeenArgs& s, int64_t q0, int64_t nq, const int* inv_pos, int64_t N, uint32_t* mask, int64_t W, int set,
+                  hipStream_t st);
+// n_pass[q] = rows of the flat index that pass query q's predicate (tags null: every row) and are not masked
+void launch_count_pass_x(const uint32_t* tags, int64_t N, const uint32_t* pred, int pred_stride, const uint32_t* xmask, int64_t W,
+                         int64_t nq, int* n_pass, hipStream_t st);
+// n_pass[q] += such rows of query q's probed lists
+void launch_count_pass_ivf_x(const uint32_t* tags, const int64_t* list_poff, const int* list_len, const int* probe_list, int64_t nq,
+                             int nprobe, const uint32_t* pred, int pred_stride, const uint32_t* xmask, int64_t W, int* n_pass,
+                             hipStream_t st);
+// *out += non-zero words of buf[0 .. n)
+void launch_count_nonzero(const uint32_t* buf, int64_t n, unsigned long long* out, hipStream_t st);
 
 }  // namespace rihip_index

@@ -29,6 +29,10 @@ __device__ __forceinline__ Pred load_pred(const uint32_t* pred, int64_t q, int s
   const uint32_t* p = pred + q * stride;
   return Pred{p[0], p[1], p[2]};
 }
+// What a scan's emit tests besides the threshold (template parameter of the scan kernels): the tag predicate, the seen-item
+// mask (search_exclude.hip), both, or nothing
+enum FilterMode { FM_NONE = 0, FM_TAGS = 1, FM_TAGS_MASK = 2, FM_MASK = 3 };
+
 // the tag words of a lane's 16 accumulator rows: four runs of four rows (acc_row)
 __device__ __forceinline__ uint32_t tag_of(const uint4* tw, int r) {
   const uint4 t = tw[r >> 2];

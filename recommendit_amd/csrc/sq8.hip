@@ -66,7 +66,8 @@ void free_sq8(Sq8Index* h) {
   rihip_bump_generation();
   drop_vectors(h);
   drop_tags(h);
-  h->fpred.release();
+  h->fpred.release(); h->xmask.release();
+  hipFree(h->inv_pos);
   h->rs.release(); h->rr.release(); h->ri.release(); h->rnv.release(); h->rcut.release(); h->rkeys.release();
   hipFree(h->codes); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
   hipFree(h->row_ids);
@@ -215,6 +216,11 @@ struct Sq8LmArgs {
   const uint32_t* tags;      // [Np] tag word of every physical row (padding rows 0)
   const uint32_t* pred;      // query q's predicate (any_of, all_of, none_of) at pred[q * pred_stride]
   int pred_stride;           // 3 = one per query, 0 = one shared by the batch
+  // seen-item exclusion (the masked instantiations): a tile at physical row p is the one aligned word
+  // xmask[mrow * xW + (p >> 5)] of every query, mrow = xrow ? xrow[q] : q (xrow: the re-do's original queries)
+  const uint32_t* xmask;
+  int64_t xW;
+  const int* xrow;
 };
 
 __device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
@@ -232,8 +238,12 @@ __device__ __forceinline__ int sq8_score_of_word(uint32_t hw) { return (int)(hw 
 // accumulator rows (four runs of four consecutive rows: acc_row) are four 16-byte loads per tile, issued with the next
 // tile's code loads.  A row that fails is absent from all three emissions: its dense or sample slot holds the empty key 0
 // and it is not a survivor.
-template <int DP, bool FILT = false>
+// FM (search_keys.h): FM_TAGS is the above; FM_TAGS_MASK / FM_MASK add the seen-item mask: the tile is one aligned word of
+// the lane's query, loaded one tile ahead with the code and tag loads; FM_MASK compiles the tag test out (an untagged
+// index).  FM_NONE and FM_TAGS are the kernels as they were.
+template <int DP, int FM = FM_NONE>
 __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
+  constexpr bool FILT = FM == FM_TAGS || FM == FM_TAGS_MASK, XM = FM == FM_TAGS_MASK || FM == FM_MASK;
   constexpr int KS = DP / 32;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r31 = lane & 31, hh = lane >> 5;
@@ -291,6 +301,18 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     pr = load_pred(a.pred, q, a.pred_stride);
     load_tags(i0, tw);
   }
+  const uint32_t* my_mask = nullptr;
+  uint32_t mw = 0u, mn = 0u;
+  if constexpr (XM) {
+    my_mask = a.xmask + (size_t)(a.xrow ? a.xrow[q] : q) * a.xW;
+    mw = my_mask[(p0 + i0 * tstep * TRS) >> 5];
+  }
+  auto row_ok = [&](int r) -> bool {   // FILT / XM: may accumulator row r of the lane be a candidate?
+    bool ok = true;
+    if constexpr (FILT) ok = pr.pass(tag_of(tw, r));
+    if constexpr (XM) ok = ok && !((mw >> acc_row(r, lane)) & 1u);
+    return ok;
+  };
   load_tile(i0, av);
 #pragma unroll 1
   for (int64_t i = i0; i < i1; ++i) {
@@ -298,6 +320,7 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     if (more) {
       load_tile(i + 1, nx);
       if constexpr (FILT) load_tags(i + 1, tn);
+      if constexpr (XM) mn = my_mask[(p0 + (i + 1) * tstep * TRS) >> 5];
     }
     i32x16 ah, al;
 #pragma unroll
@@ -317,13 +340,13 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
           const int rr = acc_row(r, lane);
           const int64_t sl = i * TRS + rr;
           if (sl < a.dense_cap)
-            my_dense[sl] = (rr < n_ok && (!FILT || pr.pass(tag_of(tw, r)))) ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
+            my_dense[sl] = (rr < n_ok && row_ok(r)) ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
         }
       } else {
         unsigned hits = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr && (!FILT || pr.pass(tag_of(tw, r)))) hits |= (1u << r);
+          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr && row_ok(r)) hits |= (1u << r);
         if (hits) {
           int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
 #pragma unroll
@@ -344,6 +367,7 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) tw[g] = tn[g];
       }
+      if constexpr (XM) mw = mn;
     }
   }
 }
@@ -392,6 +416,10 @@ struct Sq8Search {
   hipStream_t st;
   const uint32_t* pred;   // filtered search: these queries' predicates, query q's at pred[q * pred_stride]; else null
   int pred_stride;
+  // seen-item exclusion inside the scan: these queries' mask rows (row q, or xrow[q] in the re-do), xW words each; else null
+  const uint32_t* xmask = nullptr;
+  int64_t xW = 0;
+  const int* xrow = nullptr;
 };
 
 struct Sq8Geom {
@@ -444,12 +472,23 @@ int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* c
   x.list_q = h->list_q.p; x.work_off = h->work_off.p; x.plan = h->plan.p; x.nlist = g.nlist; x.tile_step = tile_step;
   x.nprobe = g.nprobe; x.count_stride = CSTRIDE; x.dense_cap = dense_cap; x.dense_ids = dense_ids;
   x.tags = s.pred ? h->tags : nullptr; x.pred = s.pred; x.pred_stride = s.pred_stride;
+  x.xmask = s.xmask; x.xW = s.xW; x.xrow = s.xrow;
   // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
   const int64_t bound = (int64_t)SQ8_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
   const dim3 grid((unsigned)((bound + 3) / 4));
+  if (x.xmask && x.tags) {
+    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_TAGS_MASK>), grid, dim3(256), 0, s.st, x);
+    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_TAGS_MASK>), grid, dim3(256), 0, s.st, x);
+    return check_launch("masked filtered sq8 scan");
+  }
+  if (x.xmask) {
+    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_MASK>), grid, dim3(256), 0, s.st, x);
+    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_MASK>), grid, dim3(256), 0, s.st, x);
+    return check_launch("masked sq8 scan");
+  }
   if (x.tags) {
-    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, true>), grid, dim3(256), 0, s.st, x);
-    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, true>), grid, dim3(256), 0, s.st, x);
+    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_TAGS>), grid, dim3(256), 0, s.st, x);
+    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_TAGS>), grid, dim3(256), 0, s.st, x);
     return check_launch("filtered sq8 scan");
   }
   if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64>), grid, dim3(256), 0, s.st, x);
@@ -497,6 +536,7 @@ int sq8_redo(const Sq8Search& s, const Sq8Geom& g, int nf) {
       launch_gather_pred(s.pred, h->fail_list.p + f0, nfc, h->fpred.p, s.st);
       r.pred = h->fpred.p;
     }
+    if (s.xmask) r.xrow = h->fail_list.p + f0;   // (the fail list holds the queries' positions in `s`: their mask rows)
     RCCHK(sq8_dense(r, g, h->fail_list.p + f0));
   }
   return RIHIP_OK;
@@ -539,6 +579,7 @@ int sq8_thresholded(const Sq8Search& s, const Sq8Geom& g) {
   const int nf = *h->h_nfail;
   h->stats[0] += nq; h->stats[1] += nf;
   if (s.pred) h->filt_stats[1] += nf;
+  if (s.xmask) h->excl_stats[1] += nf;
   return nf > 0 ? sq8_redo(s, g, nf) : RIHIP_OK;
 }
 
@@ -552,8 +593,24 @@ int sq8_transform_queries(Sq8Index* h, const float* Q, int64_t nq, int16_t* n16,
   return check_launch("sq8 query transform");
 }
 
+// the handle's inverse of row_ids, made on first use
+int sq8_ensure_inv_pos(Sq8Index* h, hipStream_t st) {
+  if (h->inv_pos) return RIHIP_OK;
+  int* ip = nullptr;
+  HIPCHK(hipMalloc((void**)&ip, sizeof(int) * (size_t)h->N));
+  launch_inv_pos(h->row_ids, h->Np, ip, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    hipFree(ip); rihip_set_error("sq8_index: building the row -> position table failed"); return RIHIP_ERR_HIP;
+  }
+  h->inv_pos = ip;
+  return RIHIP_OK;
+}
+
+// seen: the excluded search (rihip_sq8_exclude_search) -- the queries are query q_base .. of the caller's batch; every
+// internal chunk sets its mask bits, searches and clears the words it touched
 int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* out_s, int64_t* out_r, int* out_i,
-               hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0) {
+               hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0, const SeenArgs* seen = nullptr,
+               int64_t q_base = 0) {
   RCCHK(sq8_transform_queries(h, Q, nq, nullptr, nullptr, nullptr, st));
   const float* Qf = Q;
   if (h->du != h->dk) {
@@ -568,16 +625,39 @@ int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* 
     thresholded = !(nq * g.cap_df <= SQ8_DENSE_AUTO || g.cap_full <= 16384 || (double)k * 4.0 > (double)g.cap_full / SQ8_SS);
   int64_t ch = SQ8_CH;
   if (!thresholded) ch = std::max<int64_t>(1, std::min<int64_t>(SQ8_CH, SQ8_DENSE_BUDGET / g.cap_df));
+  const int64_t W = (h->Np + 31) / 32;
+  if (seen) {   // queries per chunk: what the mask budget holds as well (whole 128-query blocks where it holds one)
+    int64_t per = h->xmask_budget / (int64_t)(sizeof(uint32_t) * W);
+    if (per >= QB) per = per / QB * QB;
+    ch = std::max<int64_t>(1, std::min(ch, per));
+    RCCHK(sq8_ensure_inv_pos(h, st));
+    const int64_t want = std::min(nq, ch) * W;
+    const bool grown = h->xmask.n < want;
+    RCCHK(h->xmask.reserve(want));
+    if (grown || h->xmask_dirty) HIPCHK(hipMemsetAsync(h->xmask.p, 0, sizeof(uint32_t) * (size_t)h->xmask.n, st));
+    h->xmask_dirty = true;   // (until the last chunk's clear is enqueued: an error return in between leaves bits behind)
+  }
   const int64_t nmax = std::min(nq, ch);
   RCCHK(h->count.reserve(nmax * CSTRIDE));
   RCCHK(h->fail_flags.reserve(nmax)); RCCHK(h->fail_list.reserve(nmax)); RCCHK(h->thr.reserve(nmax)); RCCHK(h->n_fail.reserve(1));
   if (!h->h_nfail) HIPCHK(hipHostMalloc((void**)&h->h_nfail, sizeof(int)));
   for (int64_t q0 = 0; q0 < nq; q0 += ch) {
     const int64_t n = std::min(ch, nq - q0);
-    const Sq8Search s{h, Qf + q0 * h->dk, h->qhi.p + q0 * h->dpad, h->qlo.p + q0 * h->dpad, n, k, out_s + q0 * k, out_r + q0 * k, st,
-                      pred ? pred + q0 * pred_stride : nullptr, pred_stride};
+    Sq8Search s{h, Qf + q0 * h->dk, h->qhi.p + q0 * h->dpad, h->qlo.p + q0 * h->dpad, n, k, out_s + q0 * k, out_r + q0 * k, st,
+                pred ? pred + q0 * pred_stride : nullptr, pred_stride};
+    if (seen) {
+      ++h->excl_stats[2];
+      launch_xmask(*seen, q_base + q0, n, h->inv_pos, h->N, h->xmask.p, W, 1, st);
+      RCCHK(check_launch("sq8 exclusion mask"));
+      s.xmask = h->xmask.p; s.xW = W;
+    }
     RCCHK(thresholded ? sq8_thresholded(s, g) : sq8_dense(s, g, nullptr));
+    if (seen) {
+      launch_xmask(*seen, q_base + q0, n, h->inv_pos, h->N, h->xmask.p, W, 0, st);
+      RCCHK(check_launch("sq8 exclusion mask clear"));
+    }
   }
+  if (seen) { h->xmask_dirty = false; h->excl_stats[0] += nq; }
   if (pred) h->filt_stats[0] += nq;
   const int64_t tot = nq * k;
   hipLaunchKernelGGL(sq8_decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, out_s, out_r, out_i, nq, k, h->qt.p,
@@ -854,7 +934,8 @@ __global__ __launch_bounds__(128) void sq8_cert_kernel(const float* __restrict__
 }
 
 int sq8_search_refined(Sq8Index* h, const float* Q, int64_t nq, int k, int k_scan, int mode, float* out_s, int64_t* out_r,
-                       uint8_t* out_cert, double* out_bound, hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0) {
+                       uint8_t* out_cert, double* out_bound, hipStream_t st, const uint32_t* pred = nullptr, int pred_stride = 0,
+                       const SeenArgs* seen = nullptr) {
   const int64_t ch = std::max<int64_t>(1, std::min<int64_t>(nq, (1ll << 24) / k_scan));   // stage-1 slots per pass: 2^24
   RCCHK(h->rs.reserve(ch * k_scan)); RCCHK(h->rr.reserve(ch * k_scan)); RCCHK(h->ri.reserve(ch * k_scan));
   RCCHK(h->rkeys.reserve(ch * k_scan)); RCCHK(h->rnv.reserve(ch)); RCCHK(h->rcut.reserve(ch));
@@ -864,7 +945,7 @@ int sq8_search_refined(Sq8Index* h, const float* Q, int64_t nq, int k, int k_sca
     const float* Qc = Q + q0 * h->du;
     h->id_map = nullptr;   // stage 1 hands on rows; the map is applied after the select
     const int rc = sq8_search(h, Qc, n, k_scan, mode, h->rs.p, h->rr.p, h->ri.p, st, pred ? pred + q0 * pred_stride : nullptr,
-                              pred_stride);
+                              pred_stride, seen, q0);
     h->id_map = id_map;
     RCCHK(rc);
     RCCHK(dispatch_d(h->dk, [&](auto D) {
@@ -1078,6 +1159,111 @@ extern "C" int rihip_sq8_refine_search_filtered(void* handle, const float* Q, in
   RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_refine_search_filtered: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
   return sq8_search_refined(h, Q, nq, k, k_scan, mode, out_scores, out_rows, out_cert, out_bound, (hipStream_t)stream, pred_dev,
                             (int)pred_stride);
+}
+
+// ---- seen-item exclusion inside the int8 scan ---------------------------------------------------------------------
+namespace {
+int sq8_check_excluding(const char* who, Sq8Index* h, const float* Q, int64_t nq, const int64_t* seen_offsets, int64_t n_seen_rows,
+                        const int32_t* seen_items, const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev,
+                        int64_t pred_stride, int mode) {
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "%s: index is empty", who);
+  RIHIP_REQUIRE(!pred_dev || h->tags, RIHIP_ERR_STATE, "%s: the index has no tags (rihip_sq8_filter_set_tags)", who);
+  RIHIP_REQUIRE(Q && nq > 0, RIHIP_ERR_ARG, "%s: bad arguments", who);
+  RIHIP_REQUIRE(seen_offsets && seen_items && n_seen_rows >= 0, RIHIP_ERR_ARG, "%s: bad seen lists", who);
+  RIHIP_REQUIRE(row_of && n_ids > 0, RIHIP_ERR_ARG, "%s: no row_of table", who);
+  RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "%s: pred_stride=%lld (0 or 3)", who, (long long)pred_stride);
+  RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "%s: mode=%d (0 auto, 1 dense, 2 thresholded)", who, mode);
+  return RIHIP_OK;
+}
+}  // namespace
+
+extern "C" int rihip_sq8_exclude_search(void* handle, const float* Q, int64_t nq, int k, int mode, const int64_t* user_ids,
+                                        const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items,
+                                        const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev, int64_t pred_stride,
+                                        float* out_scores, int64_t* out_rows, int32_t* out_iscores, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RCCHK(sq8_check_excluding("sq8_exclude_search", h, Q, nq, seen_offsets, n_seen_rows, seen_items, row_of, n_ids, pred_dev,
+                            pred_stride, mode));
+  RIHIP_REQUIRE(out_scores && out_rows, RIHIP_ERR_ARG, "sq8_exclude_search: null output");
+  RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "sq8_exclude_search: k=%d outside [1,%d]", k, K_MAX);
+  const SeenArgs sn{user_ids, seen_offsets, n_seen_rows, seen_items, row_of, n_ids};
+  return sq8_search(h, Q, nq, k, mode, out_scores, out_rows, out_iscores, (hipStream_t)stream, pred_dev, (int)pred_stride, &sn, 0);
+}
+
+extern "C" int rihip_sq8_refine_search_excluding(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode,
+                                                 const int64_t* user_ids, const int64_t* seen_offsets, int64_t n_seen_rows,
+                                                 const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                                                 const uint32_t* pred_dev, int64_t pred_stride, float* out_scores,
+                                                 int64_t* out_rows, uint8_t* out_cert, double* out_bound, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RCCHK(sq8_check_excluding("sq8_refine_search_excluding", h, Q, nq, seen_offsets, n_seen_rows, seen_items, row_of, n_ids, pred_dev,
+                            pred_stride, mode));
+  RIHIP_REQUIRE(h->vec, RIHIP_ERR_STATE, "sq8_refine_search_excluding: no vectors attached (rihip_sq8_refine_attach_vectors)");
+  RIHIP_REQUIRE(out_scores && out_rows && out_cert, RIHIP_ERR_ARG, "sq8_refine_search_excluding: null output");
+  RIHIP_REQUIRE(k >= 1 && k <= k_scan && k_scan <= K_MAX, RIHIP_ERR_ARG,
+                "sq8_refine_search_excluding: k=%d, k_scan=%d (1 <= k <= k_scan <= %d)", k, k_scan, K_MAX);
+  const SeenArgs sn{user_ids, seen_offsets, n_seen_rows, seen_items, row_of, n_ids};
+  return sq8_search_refined(h, Q, nq, k, k_scan, mode, out_scores, out_rows, out_cert, out_bound, (hipStream_t)stream, pred_dev,
+                            (int)pred_stride, &sn);
+}
+
+extern "C" int rihip_sq8_exclude_mask_words(void* handle, int64_t* words_per_query) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0 && words_per_query, RIHIP_ERR_STATE, "sq8_exclude_mask_words: index is empty");
+  *words_per_query = (h->Np + 31) / 32;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_exclude_mask(void* handle, int64_t nq, const int64_t* user_ids, const int64_t* seen_offsets,
+                                      int64_t n_seen_rows, const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                                      uint32_t* out_mask, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_exclude_mask: index is empty");
+  RIHIP_REQUIRE(nq > 0 && seen_offsets && seen_items && n_seen_rows >= 0 && row_of && n_ids > 0 && out_mask, RIHIP_ERR_ARG,
+                "sq8_exclude_mask: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  RCCHK(sq8_ensure_inv_pos(h, st));
+  const int64_t W = (h->Np + 31) / 32;
+  HIPCHK(hipMemsetAsync(out_mask, 0, sizeof(uint32_t) * (size_t)(nq * W), st));
+  const SeenArgs sn{user_ids, seen_offsets, n_seen_rows, seen_items, row_of, n_ids};
+  for (int64_t q0 = 0; q0 < nq; q0 += SQ8_CH) {
+    const int64_t n = std::min(SQ8_CH, nq - q0);
+    launch_xmask(sn, q0, n, h->inv_pos, h->N, out_mask + q0 * W, W, 1, st);
+  }
+  return check_launch("sq8 exclusion mask");
+}
+
+extern "C" int rihip_sq8_exclude_set_exclusion_budget(void* handle, int64_t bytes) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && bytes >= 0, RIHIP_ERR_ARG, "sq8_exclude_set_exclusion_budget: bad arguments");
+  h->xmask_budget = bytes > 0 ? bytes : XMASK_BUDGET;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_exclude_scratch_nonzero(void* handle, int64_t* n_words, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && n_words, RIHIP_ERR_ARG, "sq8_exclude_scratch_nonzero: bad arguments");
+  *n_words = 0;
+  if (!h->xmask.p) return RIHIP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* cnt = nullptr;
+  HIPCHK(hipMalloc((void**)&cnt, sizeof(unsigned long long)));
+  unsigned long long host = 0;
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess) { launch_count_nonzero(h->xmask.p, h->xmask.n, cnt, st); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipFree(cnt);
+  HIPCHK(e);
+  *n_words = (int64_t)host;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_sq8_exclude_exclusion_stats(void* handle, int64_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_exclude_exclusion_stats: bad arguments");
+  for (int i = 0; i < 3; ++i) out[i] = h->excl_stats[i];
+  return RIHIP_OK;
 }
 
 extern "C" int rihip_sq8_refine_attach_vectors(void* handle, void* ip_handle, void* stream) {

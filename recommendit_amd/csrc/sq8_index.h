@@ -28,6 +28,13 @@ struct Sq8Index {
   // filtered search (rihip_sq8_filter_set_tags): one 32-bit tag word per physical row, padding rows 0, or null
   uint32_t* tags = nullptr;          // [Np]
   int64_t filt_stats[2] = {0, 0};    // queries searched filtered, of those re-done dense
+  // seen-item exclusion inside the scan (rihip_sq8_exclude_search): as IpIndex's -- the inverse of row_ids (built on first
+  // use, dropped with the row order), the mask scratch (all zero between calls) and its budget
+  int* inv_pos = nullptr;            // [N] original row -> physical position
+  DevBuf<uint32_t> xmask;
+  bool xmask_dirty = false;
+  int64_t xmask_budget = XMASK_BUDGET;
+  int64_t excl_stats[3] = {0, 0, 0};   // queries searched this way, of those re-done dense, mask chunks
   // refined search (rihip_sq8_refine_attach_vectors): the f32 rows next to the codes, or null
   float* vec = nullptr;              // [N, dk] insertion-row order (stage 1 returns rows: no inverse map)
   double* ref_e = nullptr;           // [dk] e_j = max_i |x_ij - (m_j + s_j c_ij)| over the stored rows

@@ -360,6 +360,7 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
   rihip_bump_generation();
   hipFree(h->codes); hipFree(h->row_ids); hipFree(h->list_poff); hipFree(h->list_len_dev); hipFree(h->tags);
   hipFree(h->vec); hipFree(h->ref_e); hipFree(h->ref_a);
+  hipFree(h->inv_pos); h->inv_pos = nullptr;   // (a new physical order)
   h->codes = o.codes; h->row_ids = o.rid; h->list_poff = o.poff; h->list_len_dev = o.len; h->tags = o.tags;
   h->vec = o.vec; h->ref_e = o.e; h->ref_a = o.a;
   o.codes = nullptr; o.rid = nullptr; o.poff = nullptr; o.len = nullptr; o.tags = nullptr; o.vec = nullptr; o.e = nullptr; o.a = nullptr;

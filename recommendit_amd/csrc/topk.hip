@@ -68,6 +68,13 @@ struct Search {
   // filtered search count the passing rows first and never defer their exactness check.
   const uint32_t* pred;
   int pred_stride;
+  // seen-item exclusion inside the scan (rihip_ip_index_search_excluding), else null: the mask rows of these queries
+  // (row q, or row xrow[q] in the re-do of failed queries), xW words each.  Such a search goes the way a filtered one
+  // goes, with or without predicates.
+  const uint32_t* xmask = nullptr;
+  int64_t xW = 0;
+  const int* xrow = nullptr;
+  bool filt() const { return pred || xmask; }   // rows are tested in the scans: the counted, synchronising paths
 };
 
 void gather_rows(const Search& s, const int* idx, int n, float* out) {
@@ -83,6 +90,7 @@ Search redo_of(const Search& s, const int* slots, int n) {
     launch_gather_pred(s.pred, slots, n, s.h->fpred.p, s.st);
     r.pred = s.h->fpred.p;
   }
+  if (s.xmask) r.xrow = slots;   // (the fail list holds the queries' positions in `s`: their mask rows)
   return r;
 }
 
@@ -98,6 +106,7 @@ int read_fail_count(const Search& s, int* nf) {
   HIPCHK(hipStreamSynchronize(s.st));
   *nf = *s.h->h_nfail;
   if (s.pred) s.h->filt_stats[1] += *nf;
+  if (s.xmask) s.h->excl_stats[1] += *nf;
   return RIHIP_OK;
 }
 
@@ -176,6 +185,7 @@ int ivf_scan(const Search& s, const IvfGeom& g, const float* thr, uint64_t* cand
   x.work_off = h->work_off.p; x.plan = h->plan.p; x.nlist = g.nlist; x.tile_step = tile_step; x.nprobe = g.nprobe;
   x.dense_cap = dense_cap; x.count_stride = CSTRIDE; x.dense_ids = dense_ids;
   if (s.pred) { x.tags = h->tags; x.pred = s.pred; x.pred_stride = s.pred_stride; }
+  if (s.xmask) { x.xmask = s.xmask; x.xW = s.xW; x.xrow = s.xrow; }
   // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
   const int64_t bound = (int64_t)IVF_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
   return launch_ivf_scan(h->d, x, (unsigned)((bound + 3) / 4), s.st);
@@ -241,10 +251,12 @@ int ivf_thresholded(const Search& s, const IvfGeom& g) {
   RCCHK(h->cand.reserve(nq * cap));
   // ---- pass A
   RCCHK(ivf_prepare(s, g, SS, h->scand.p, nq * cap_s));
-  if (s.pred) {   // passing rows of every query's probed lists
+  if (s.filt()) {   // passing (and unmasked) rows of every query's probed lists
     HIPCHK(hipMemsetAsync(h->n_pass.p, 0, sizeof(int) * nq, s.st));
-    launch_count_pass_ivf(h->tags, h->list_poff, h->list_len_dev, h->probe_list.p, nq, g.nprobe, s.pred, s.pred_stride,
-                          h->n_pass.p, s.st);
+    if (s.xmask) launch_count_pass_ivf_x(s.pred ? h->tags : nullptr, h->list_poff, h->list_len_dev, h->probe_list.p, nq, g.nprobe,
+                                         s.pred, s.pred_stride, s.xmask, s.xW, h->n_pass.p, s.st);
+    else launch_count_pass_ivf(h->tags, h->list_poff, h->list_len_dev, h->probe_list.p, nq, g.nprobe, s.pred, s.pred_stride,
+                               h->n_pass.p, s.st);
   }
   RCCHK(ivf_scan(s, g, nullptr, h->scand.p, cap_s, SS, cap_l, true, 0));
   // (the sample's lists are dense: count = null means cap_s keys each; this launch also resets the failed-query counter
@@ -253,7 +265,7 @@ int ivf_thresholded(const Search& s, const IvfGeom& g) {
   fa.cand = h->scand.p; fa.cap = cap_s; fa.mode = 1; fa.rank = rank; fa.thr_out = h->thr.p; fa.count = nullptr;
   fa.zero_me = h->n_fail.p;
   RCCHK(launch_finalize(fa, (unsigned)nq, s.st));
-  if (s.pred) {   // (the sampled share of the passing rows beats the threshold like the sampled share of all rows did: same rank)
+  if (s.filt()) {   // (the sampled share of the passing rows beats the threshold like the sampled share of all rows did: same rank)
     launch_filt_thr(h->thr.p, h->n_pass.p, 1, cap, nq, s.st);
     fa.n_pass = h->n_pass.p; fa.n_pass_stride = 1;
   }
@@ -265,7 +277,7 @@ int ivf_thresholded(const Search& s, const IvfGeom& g) {
   RCCHK(launch_finalize(fa, (unsigned)nq, s.st));
   // ---- exactness check
   HIPCHK(hipMemcpyAsync(h->h_nfail, h->n_fail.p, sizeof(int), hipMemcpyDeviceToHost, s.st));
-  if (h->defer_check && h->defer_ok && !s.pred) {   // the caller checks later (rihip_ip_index_search_finish): no host sync here
+  if (h->defer_check && h->defer_ok && !s.filt()) {   // the caller checks later (rihip_ip_index_search_finish): no host sync here
     // finish then waits for THIS point of the stream only: whatever the caller enqueues behind the search keeps the GPU
     // busy while the host is already back (a capturing stream records no event: replays use _last_fail_count)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -308,6 +320,7 @@ ScanArgs scan_args(const Search& s) {
   memset(&sa, 0, sizeof(sa));
   sa.X = s.h->X; sa.Q = s.Q; sa.nq = s.nq; sa.count = s.h->count.p;
   if (s.pred) { sa.tags = s.h->tags; sa.pred = s.pred; sa.pred_stride = s.pred_stride; }
+  if (s.xmask) { sa.xmask = s.xmask; sa.xW = s.xW; sa.xrow = s.xrow; }
   return sa;
 }
 unsigned f32_qgrid(int64_t nq) { return (unsigned)((nq + QB - 1) / QB); }
@@ -363,7 +376,7 @@ int flat_thresholded(const Search& s) {
   IpIndex* h = s.h;
   const int64_t nq = s.nq;
   const int k = s.k, d = h->d;
-  const bool two_prec = h->two_precision && h->Xb != nullptr && !s.pred;
+  const bool two_prec = h->two_precision && h->Xb != nullptr && !s.filt();
   // the two-precision path samples twice as many rows: the threshold estimate tightens (expected survivors per query
   // 2 200 -> 1 700 at k = 500, N = 1 M), which saves more in the filter's emission and in the re-score than the longer
   // sample pass costs (measured 2.33 -> 2.16 ms per 4 096 queries; 3x, 4x the same, 6x slower again)
@@ -417,10 +430,11 @@ int flat_thresholded(const Search& s) {
   fa.zero_me = h->n_fail.p;            // (reset here: refine_kernel appends the failed queries itself)
   RCCHK(launch_finalize(fa, (unsigned)nq, s.st));
   fa.count = h->count.p; fa.zero_me = nullptr;
-  if (s.pred) {   // exact passing-row counts; queries whose passing rows all fit the candidate list skip the threshold
-    const int np_stride = s.pred_stride == 0 ? 0 : 1;
+  if (s.filt()) {   // exact passing-row counts; queries whose passing rows all fit the candidate list skip the threshold
+    const int np_stride = (s.pred_stride == 0 && !s.xmask) ? 0 : 1;   // (a mask is per query whatever the predicate is)
     HIPCHK(hipMemsetAsync(h->n_pass.p, 0, sizeof(int) * (np_stride ? nq : 1), s.st));
-    launch_count_pass(h->tags, h->N, s.pred, s.pred_stride, nq, h->n_pass.p, s.st);
+    if (s.xmask) launch_count_pass_x(s.pred ? h->tags : nullptr, h->N, s.pred, s.pred_stride, s.xmask, s.xW, nq, h->n_pass.p, s.st);
+    else launch_count_pass(h->tags, h->N, s.pred, s.pred_stride, nq, h->n_pass.p, s.st);
     launch_filt_thr(h->thr.p, h->n_pass.p, np_stride, cap, nq, s.st);
     fa.n_pass = h->n_pass.p; fa.n_pass_stride = np_stride;
   }
@@ -493,11 +507,12 @@ int search_pass(const Search& s) {
   RCCHK(h->thr.reserve(nq));
   RCCHK(h->n_fail.reserve(1));
   if (!h->h_nfail) HIPCHK(hipHostMalloc((void**)&h->h_nfail, sizeof(int)));
+  if (s.filt()) RCCHK(h->n_pass.reserve(nq));
   if (s.pred) {
-    RCCHK(h->n_pass.reserve(nq));
     RCCHK(h->fpred.reserve(64 * 3));
     h->filt_stats[0] += nq;
   }
+  if (s.xmask) h->excl_stats[0] += nq;
   if (h->ivf) {
     IvfGeom g;
     RCCHK(ivf_geom(h, &g));
@@ -566,7 +581,7 @@ extern "C" int rihip_ip_index_destroy(void* handle) {
   IpIndex* h = (IpIndex*)handle;
   if (!h) return RIHIP_OK;
   free_index_arrays(h);
-  h->n_pass.release(); h->fpred.release();
+  h->n_pass.release(); h->fpred.release(); h->xmask.release();
   h->cand.release(); h->scand.release(); h->fcand.release(); h->count.release(); h->fail_flags.release();
   h->fail_list.release(); h->n_fail.release(); h->fcount.release(); h->thr.release(); h->thr2.release(); h->fQ.release();
   h->coarse.release(); h->probe_list.release(); h->list_q.release(); h->list_cnt.release(); h->list_qoff.release();
@@ -696,6 +711,131 @@ extern "C" int rihip_ip_index_search_filtered(void* handle, const float* Q, int6
   hipStream_t st = (hipStream_t)stream;
   RCCHK(kernel_width_queries(h, "ip_index_search_filtered", &Q, nq, st));
   return search_in_chunks(h, Q, nq, k, pred_dev, (int)pred_stride, out_scores, out_rows, st);
+}
+
+// ---- seen-item exclusion inside the scan --------------------------------------------------------------------------
+namespace {
+int check_seen_args(const char* who, int64_t nq, const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items,
+                    const int32_t* row_of, int64_t n_ids) {
+  RIHIP_REQUIRE(nq > 0 && seen_offsets && seen_items && n_seen_rows >= 0, RIHIP_ERR_ARG, "%s: bad seen lists", who);
+  RIHIP_REQUIRE(row_of && n_ids > 0, RIHIP_ERR_ARG, "%s: no row_of table", who);
+  return RIHIP_OK;
+}
+// the handle's inverse of row_ids, made on first use (flat: positions are rows, none needed)
+int ensure_inv_pos(IpIndex* h, hipStream_t st) {
+  if (!h->ivf || h->inv_pos) return RIHIP_OK;
+  int* ip = nullptr;
+  HIPCHK(hipMalloc((void**)&ip, sizeof(int) * (size_t)h->N));
+  launch_inv_pos(h->row_ids, h->Np, ip, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    hipFree(ip); rihip_set_error("ip_index: building the row -> position table failed"); return RIHIP_ERR_HIP;
+  }
+  h->inv_pos = ip;
+  return RIHIP_OK;
+}
+int64_t mask_words_per_query(const IpIndex* h) { return ((h->ivf ? h->Np : h->N) + 31) / 32; }
+}  // namespace
+
+extern "C" int rihip_ip_index_set_exclusion_budget(void* handle, int64_t bytes) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && bytes >= 0, RIHIP_ERR_ARG, "ip_index_set_exclusion_budget: bad arguments");
+  h->xmask_budget = bytes > 0 ? bytes : XMASK_BUDGET;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_exclusion_stats(void* handle, int64_t* out) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "ip_index_exclusion_stats: bad arguments");
+  for (int i = 0; i < 3; ++i) out[i] = h->excl_stats[i];
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_exclusion_mask_words(void* handle, int64_t* words_per_query) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && h->X && h->N > 0 && words_per_query, RIHIP_ERR_STATE, "ip_index_exclusion_mask_words: index is empty");
+  *words_per_query = mask_words_per_query(h);
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_exclusion_mask(void* handle, int64_t nq, const int64_t* user_ids, const int64_t* seen_offsets,
+                                             int64_t n_seen_rows, const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
+                                             uint32_t* out_mask, void* stream) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && h->X && h->N > 0, RIHIP_ERR_STATE, "ip_index_exclusion_mask: index is empty");
+  RCCHK(check_seen_args("ip_index_exclusion_mask", nq, seen_offsets, n_seen_rows, seen_items, row_of, n_ids));
+  RIHIP_REQUIRE(out_mask, RIHIP_ERR_ARG, "ip_index_exclusion_mask: null output");
+  hipStream_t st = (hipStream_t)stream;
+  RCCHK(ensure_inv_pos(h, st));
+  const int64_t W = mask_words_per_query(h);
+  HIPCHK(hipMemsetAsync(out_mask, 0, sizeof(uint32_t) * (size_t)(nq * W), st));
+  const SeenArgs sn{user_ids, seen_offsets, n_seen_rows, seen_items, row_of, n_ids};
+  for (int64_t q0 = 0; q0 < nq; q0 += CH) {
+    const int64_t n = (nq - q0 < CH) ? nq - q0 : CH;
+    launch_xmask(sn, q0, n, h->inv_pos, h->N, out_mask + q0 * W, W, 1, st);
+  }
+  return check_launch("exclusion mask");
+}
+
+extern "C" int rihip_ip_index_exclusion_scratch_nonzero(void* handle, int64_t* n_words, void* stream) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && n_words, RIHIP_ERR_ARG, "ip_index_exclusion_scratch_nonzero: bad arguments");
+  *n_words = 0;
+  if (!h->xmask.p) return RIHIP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* cnt = nullptr;
+  HIPCHK(hipMalloc((void**)&cnt, sizeof(unsigned long long)));
+  unsigned long long host = 0;
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess) { launch_count_nonzero(h->xmask.p, h->xmask.n, cnt, st); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, cnt, sizeof(host), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipFree(cnt);
+  HIPCHK(e);
+  *n_words = (int64_t)host;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_ip_index_search_excluding(void* handle, const float* Q, int64_t nq, int k, const int64_t* user_ids,
+                                               const int64_t* seen_offsets, int64_t n_seen_rows, const int32_t* seen_items,
+                                               const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev, int64_t pred_stride,
+                                               float* out_scores, int64_t* out_rows, void* stream) {
+  IpIndex* h = (IpIndex*)handle;
+  RIHIP_REQUIRE(h && h->X && h->N > 0, RIHIP_ERR_STATE, "ip_index_search_excluding: index is empty");
+  RIHIP_REQUIRE(!pred_dev || h->tags, RIHIP_ERR_STATE, "ip_index_search_excluding: the index has no tags (rihip_ip_index_set_tags)");
+  RIHIP_REQUIRE(!h->pending.active, RIHIP_ERR_STATE, "ip_index_search_excluding: a deferred search is pending (rihip_ip_index_search_finish)");
+  RIHIP_REQUIRE(Q && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "ip_index_search_excluding: bad arguments");
+  RCCHK(check_seen_args("ip_index_search_excluding", nq, seen_offsets, n_seen_rows, seen_items, row_of, n_ids));
+  RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "ip_index_search_excluding: pred_stride=%lld (0 or 3)", (long long)pred_stride);
+  RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "ip_index_search_excluding: k=%d outside [1,%d]", k, K_MAX);
+  hipStream_t st = (hipStream_t)stream;
+  RCCHK(kernel_width_queries(h, "ip_index_search_excluding", &Q, nq, st));
+  RCCHK(ensure_inv_pos(h, st));
+  const int64_t W = mask_words_per_query(h);
+  // queries per mask chunk: what the budget holds (whole 128-query blocks where it holds one), at most an internal pass
+  int64_t per = h->xmask_budget / (int64_t)(sizeof(uint32_t) * W);
+  if (per > CH) per = CH;
+  if (per >= QB) per = per / QB * QB;
+  if (per < 1) per = 1;
+  if (per > nq) per = nq;
+  const bool grown = h->xmask.n < per * W;
+  RCCHK(h->xmask.reserve(per * W));
+  if (grown || h->xmask_dirty) HIPCHK(hipMemsetAsync(h->xmask.p, 0, sizeof(uint32_t) * (size_t)h->xmask.n, st));
+  const SeenArgs sn{user_ids, seen_offsets, n_seen_rows, seen_items, row_of, n_ids};
+  h->xmask_dirty = true;   // (until the last chunk's clear is enqueued: an error return in between leaves bits behind)
+  for (int64_t q0 = 0; q0 < nq; q0 += per) {
+    const int64_t n = (nq - q0 < per) ? nq - q0 : per;
+    ++h->excl_stats[2];
+    launch_xmask(sn, q0, n, h->inv_pos, h->N, h->xmask.p, W, 1, st);
+    RCCHK(check_launch("exclusion mask"));
+    Search s{h, Q + q0 * h->d, n, k, out_scores + q0 * k, out_rows + q0 * k, st,
+             pred_dev ? pred_dev + q0 * pred_stride : nullptr, (int)pred_stride};
+    s.xmask = h->xmask.p; s.xW = W;
+    RCCHK(search_pass(s));
+    launch_xmask(sn, q0, n, h->inv_pos, h->N, h->xmask.p, W, 0, st);
+    RCCHK(check_launch("exclusion mask clear"));
+  }
+  h->xmask_dirty = false;
+  return RIHIP_OK;
 }
 
 // Deferred exactness check (serving chains): with enable = 1 a thresholded IVF search of <= 4 096 queries enqueues its

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .exclusion import ExcludingSearch
+from .exclusion import ExcludingSearch, check_exclusion, seen_user_ids
 
 logger = logging.getLogger(__name__)
 
@@ -136,6 +136,10 @@ def _list_stats(sizes: np.ndarray) -> Dict:
 
 
 class FAISSIndex(ExcludingSearch):
+    _EXCL_ABI = {"mask_words": "rihip_ip_index_exclusion_mask_words", "mask": "rihip_ip_index_exclusion_mask",
+                 "budget": "rihip_ip_index_set_exclusion_budget", "nonzero": "rihip_ip_index_exclusion_scratch_nonzero",
+                 "stats": "rihip_ip_index_exclusion_stats"}
+
     def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
         """exact=True skips the IVF partition (brute-force inner product; not in the reference)."""
         self.embed_dim = embed_dim
@@ -517,10 +521,36 @@ class FAISSIndex(ExcludingSearch):
 
     # -- seen-item exclusion: filter_excluded, exclusion_deficit and _search_excluding come from exclusion.ExcludingSearch
 
-    def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None, item_filter=None
-               ) -> Tuple[np.ndarray, np.ndarray]:
+    def _search_scan_excluding(self, q: torch.Tensor, k: int, seen, uid: Optional[torch.Tensor], item_filter=None,
+                               row_of: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """exclusion="scan": one rihip_ip_index_search_excluding over the batch -> (scores, item ids) [nq, k]"""
+        lib = L.lib()
+        nq = q.shape[0]
+        row_of = self._row_of_device() if row_of is None else self._check_row_of(row_of)
+        pred, stride = None, 0
+        if item_filter is not None:
+            if self._tags is None:
+                raise ValueError("item_filter needs item tags: call set_item_tags() first")
+            pred, stride = _filter_device(item_filter, nq, q.device)
+        if self.search_pending():
+            raise RuntimeError('a deferred search is pending: call finish_search() before an exclusion="scan" search')
+        if k > int(lib.rihip_ip_index_max_k()):
+            raise ValueError(f"k={k} exceeds the device select buffer ({int(lib.rihip_ip_index_max_k())})")
+        L.check(lib.rihip_ip_index_set_id_map(self.index._h, self._item_ids_dev.data_ptr()), "ip_index_set_id_map")
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        L.check(lib.rihip_ip_index_search_excluding(self.index._h, q.data_ptr(), nq, k, L.ptr(uid), seen.offsets.data_ptr(),
+                                                    seen.n_users, seen.items.data_ptr(), row_of.data_ptr(), row_of.shape[0],
+                                                    L.ptr(pred), stride, scores.data_ptr(), ids.data_ptr(), L.stream_ptr()),
+                "ip_index_search_excluding")
+        return scores, ids
+
+    def search(self, query_vector: np.ndarray, k: int = 500, exclude_items=None, item_filter=None,
+               exclusion: str = "overfetch") -> Tuple[np.ndarray, np.ndarray]:
         """exclude_items (not in the reference): item ids that must not be returned; item_filter (not in the reference):
-        (any_of, all_of, none_of) over the items' tag words, as in batch_search_device"""
+        (any_of, all_of, none_of) over the items' tag words, as in batch_search_device; exclusion: how exclude_items are
+        kept out, as in batch_search_device"""
+        check_exclusion(exclusion)
         if self.index is None:
             raise RuntimeError("Index not built. Call build_ivf_index() first.")
         query = np.atleast_2d(query_vector).astype(np.float32)
@@ -532,7 +562,7 @@ class FAISSIndex(ExcludingSearch):
             from .seen import SeenItems
             ex = np.asarray(exclude_items, dtype=np.int64).reshape(-1)
             scores, ids = self._search_excluding(q_dev, k, SeenItems.from_pairs(np.zeros(ex.shape[0], np.int64), ex, 1),
-                                                 None, item_filter)
+                                                 None, item_filter, exclusion=exclusion)
             distances, ids = scores[0].cpu().numpy(), ids[0].cpu().numpy()
             return distances[ids >= 0], ids[ids >= 0]
         scores, rows = self._search_device(q_dev, k, item_filter=item_filter)
@@ -543,9 +573,10 @@ class FAISSIndex(ExcludingSearch):
         faiss_indices = faiss_indices[valid_mask]
         return distances, self.item_ids[faiss_indices]
 
-    def batch_search(self, query_vectors: np.ndarray, k: int = 500, exclude=None, user_ids=None, item_filter=None
-                     ) -> Tuple[np.ndarray, np.ndarray]:
-        """exclude / user_ids / item_filter (not in the reference): as in batch_search_device"""
+    def batch_search(self, query_vectors: np.ndarray, k: int = 500, exclude=None, user_ids=None, item_filter=None,
+                     exclusion: str = "overfetch") -> Tuple[np.ndarray, np.ndarray]:
+        """exclude / user_ids / item_filter / exclusion (not in the reference): as in batch_search_device"""
+        check_exclusion(exclusion)
         if self.index is None:
             raise RuntimeError("Index not built.")
         queries = query_vectors.astype(np.float32)
@@ -554,7 +585,8 @@ class FAISSIndex(ExcludingSearch):
         k = min(k, self.index.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
         if exclude is not None:
-            scores, rows = self._search_excluding(q_dev, k, exclude, self._require_user_ids(user_ids), item_filter)
+            scores, rows = self._search_excluding(q_dev, k, exclude, self._require_user_ids(user_ids), item_filter,
+                                                  exclusion=exclusion)
         else:
             scores, rows = self._search_device(q_dev, k, item_ids=True, item_filter=item_filter)
         return scores.cpu().numpy(), rows.cpu().numpy()
@@ -566,7 +598,8 @@ class FAISSIndex(ExcludingSearch):
         return user_ids
 
     def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, exclude=None,
-                            user_ids=None, item_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                            user_ids=None, item_filter=None, exclusion: str = "overfetch"
+                            ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-resident batch_search (not in the reference): queries f32 [nq,d] on the HIP device;
         returns (scores, item_ids) on device, -1 padded.  This is the QPS benchmark entry.
 
@@ -578,6 +611,13 @@ class FAISSIndex(ExcludingSearch):
         Under set_deferred_check(True) the filtered result is a consumer of the search like any other: when
         finish_search() returns > 0, call this again (it then runs as one group: one search, one finish).
 
+        exclusion="scan" (opt-in; "overfetch", the default, is everything above): the seen items are excluded inside the
+        index scan instead -- one bit per (query, row) of a mask built on the device from the store, tested where the
+        tag predicate is tested.  One search of the whole batch whatever user_ids is, no over-fetch, no groups, nothing
+        added to exclusion_deficit(), and no limit on k plus a user's list.  The same rows and scores bit for bit.  It
+        always synchronises like a filtered search (RuntimeError while a deferred search is pending), a large flat index
+        takes the all-f32 scan, and item ids must lie in [0, 2**31 - 1).  Any other value: ValueError.
+
         item_filter (needs set_item_tags): a 3-tuple of ints (any_of, all_of, none_of) shared by the batch, a uint32
         array [nq,3], or an int32 device tensor [nq,3] read as a bit pattern.  Item i passes iff (any_of == 0 or
         tag[i] & any_of) and tag[i] & all_of == all_of and tag[i] & none_of == 0; the result is the exact top k of the
@@ -585,6 +625,7 @@ class FAISSIndex(ExcludingSearch):
         predicate is tested inside the scan, so a filter that removes 99.9 % of the corpus needs no over-fetch.  With
         exclude the result is filter AND not-seen.  A filtered search always synchronises (no deferred check), and on
         a large flat index it takes the all-f32 scan.  ValueError without tags or on a bad shape."""
+        check_exclusion(exclusion)
         if self.index is None:
             raise RuntimeError("Index not built.")
         q = queries.to(dtype=torch.float32).contiguous()
@@ -592,7 +633,7 @@ class FAISSIndex(ExcludingSearch):
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
         k = min(k, self.index.ntotal)
         if exclude is not None:
-            return self._search_excluding(q, k, exclude, self._require_user_ids(user_ids), item_filter)
+            return self._search_excluding(q, k, exclude, self._require_user_ids(user_ids), item_filter, exclusion=exclusion)
         return self._search_device(q, k, item_ids=True, item_filter=item_filter)
 
     # -- persistence (faiss_index.py:159-205) -------------------------------------------------

@@ -22,6 +22,7 @@ from . import rerank as RR
 from .coldstart import UserHistories, fold_in_users_device
 from .faiss_index import FAISSIndex
 from .ranker import LightGBMRanker
+from .exclusion import check_exclusion
 from .seen import SeenItems, overfetch_k, plan_overfetch
 from .sq8_index import SQ8Index
 from .two_tower import N_GENRES, TwoTowerModel
@@ -186,12 +187,18 @@ class GpuRecommendationPipeline:
     def __init__(self, model: TwoTowerModel, index: FAISSIndex, ranker: LightGBMRanker, store: GpuFeatureStore,
                  top_k_candidates: int = 500, top_k_results: int = 20, feature_log_rows: int = 0,
                  seen: Optional[SeenItems] = None, diversity: Optional[float] = None,
-                 diversity_vectors: Optional[torch.Tensor] = None):
+                 diversity_vectors: Optional[torch.Tensor] = None, exclusion: str = "overfetch"):
         """defaults = settings.TOP_K_CANDIDATES / TOP_K_RESULTS (src/config.py:11-12).
 
         seen (not in the reference, which recommends what the user has already rated: SURVEY.md §3.4 hazard ii): a
         store of excluded item ids per user id; with one attached, retrieval over-fetches and a device filter drops
         each user's items, so features, the feature log, the ranker and the top-k still see top_k_candidates columns.
+        exclusion="scan" (opt-in; "overfetch" is the sentence above): the seen items are excluded inside the index scan
+        instead (FAISSIndex.batch_search_device(exclusion="scan")): recommend_batch, get_recommendations and
+        recommend_cold_batch(exclude_history=True) run ONE chain over the whole batch, host and device ids alike, at
+        top_k_candidates with no over-fetch, no groups, no device filter and no limit on a user's list; the same
+        candidates bit for bit.  That search synchronises the stream, so graph=True then raises ValueError: keep
+        "overfetch" for captured single requests.  Any other value: ValueError.
 
         diversity (not in the reference, whose chain ends in nlargest): None = the last stage is the plain top-k by
         ranker score, as ever.  A number in [0, 1] = greedy MMR re-ranking instead (rerank.py; the definition is at
@@ -213,6 +220,7 @@ class GpuRecommendationPipeline:
         feature_log_rows = R > 0 keeps the ranking-feature rows of the newest R served (user, candidate) pairs in a
         device ring (the "feature DataFrame from serving" of detect_training_serving_skew, metrics.py:234-260):
         serving_features(), detect_skew(), reset_feature_log().  0 leaves the chain as it is."""
+        self.exclusion = check_exclusion(exclusion)
         self.model, self.index, self.ranker, self.store = model, index, ranker, store
         self._sq8 = isinstance(index, SQ8Index)
         if self._sq8:
@@ -292,6 +300,13 @@ class GpuRecommendationPipeline:
         div = self._diversity_stage(diversity, k)
         if exclude_seen and self.seen is None:
             raise ValueError("exclude_seen=True without a seen store (set_seen)")
+        if self.exclusion == "scan" and self.seen is not None and exclude_seen is not False:
+            if graph:
+                raise ValueError('graph=True cannot serve exclusion="scan": the excluded search synchronises the stream '
+                                 '(keep exclusion="overfetch" for captured requests)')
+            if self._sq8 and item_filter is not None and self.index._tags is None:
+                raise ValueError("item_filter on an SQ8 index needs item tags: call SQ8Index.set_item_tags() first")
+            return self._chain(self._ids_to_device(user_ids), k, item_filter=item_filter, div=div, scan_seen=self.seen)
         if item_filter is not None:
             if graph:
                 raise ValueError("graph=True cannot serve an item_filter: the filtered search synchronises the stream")
@@ -453,16 +468,20 @@ class GpuRecommendationPipeline:
 
     def _chain(self, uid: torch.Tensor, k: int, log: bool = True, k_eff: Optional[int] = None, item_filter=None,
                div=None, q: Optional[torch.Tensor] = None, user_tab: Optional[torch.Tensor] = None,
-               seen: Optional[SeenItems] = None, log_uid: Optional[torch.Tensor] = None
-               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+               seen: Optional[SeenItems] = None, log_uid: Optional[torch.Tensor] = None,
+               scan_seen: Optional[SeenItems] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """q, user_tab, seen, log_uid (the cold-start chain): precomputed normalised queries instead of the user tower,
         a table uid indexes instead of the store's user table, the exclusion store uid indexes instead of the attached
-        one, and the user ids the feature log records instead of uid"""
+        one, and the user ids the feature log records instead of uid.  scan_seen (exclusion="scan"): the store whose
+        row uid[q] retrieval excludes inside its scan; k_eff is then None and nothing is filtered behind the search"""
         if q is None:
             q = self.model.get_user_embeddings(uid, as_tensor=True)
         # tower outputs are already L2-normalised (two_tower.py:42): the wrapper's re-normalisation (faiss_index.py:108-110)
         # would divide by 1 +- 1e-7 and cost three tensor ops per request
-        if item_filter is None:
+        if scan_seen is not None:
+            rs, cand = self.index.batch_search_device(q, k=self.top_k_candidates, normalized=True, exclude=scan_seen,
+                                                      user_ids=uid, item_filter=item_filter, exclusion="scan")
+        elif item_filter is None:
             rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True)
         else:
             rs, cand = self.index.batch_search_device(q, k=k_eff or self.top_k_candidates, normalized=True,
@@ -616,14 +635,15 @@ class GpuRecommendationPipeline:
         if warm.shape[0]:
             whole = warm.shape[0] == nq
             most = int(histories.counts[warm].max()) if exclude_history else 0
-            k_eff = overfetch_k(kc, most, ntotal, int(L.lib().rihip_ip_index_max_k())) if most else None
+            scan = self.exclusion == "scan" and most > 0
+            k_eff = overfetch_k(kc, most, ntotal, int(L.lib().rihip_ip_index_max_k())) if most and not scan else None
             uid = torch.arange(nq, dtype=torch.int64, device=dev) if whole else torch.from_numpy(warm).to(dev)
             log_uid = torch.full((warm.shape[0],), -1, dtype=torch.int64, device=dev) if labels is None \
                 else labels[torch.from_numpy(warm)].to(dev)
             from .faiss_index import _sub_filter
             out = self._chain(uid, k, k_eff=k_eff, div=div, q=q if whole else q[uid].contiguous(), user_tab=rows,
                               item_filter=item_filter if item_filter is None or whole else _sub_filter(item_filter, uid),
-                              seen=histories.as_seen(), log_uid=log_uid)
+                              seen=histories.as_seen(), log_uid=log_uid, scan_seen=histories.as_seen() if scan else None)
             if whole:
                 ids, sc, rs = out
             else:

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .exclusion import ExcludingSearch
+from .exclusion import ExcludingSearch, check_exclusion, seen_user_ids
 from .faiss_index import FAISSIndex, _filter_device, _sub_filter
 
 logger = logging.getLogger(__name__)
@@ -119,6 +119,10 @@ def _tag_words(tags, n: int) -> np.ndarray:
 
 
 class SQ8Index(ExcludingSearch):
+    _EXCL_ABI = {"mask_words": "rihip_sq8_exclude_mask_words", "mask": "rihip_sq8_exclude_mask",
+                 "budget": "rihip_sq8_exclude_set_exclusion_budget", "nonzero": "rihip_sq8_exclude_scratch_nonzero",
+                 "stats": "rihip_sq8_exclude_exclusion_stats"}
+
     def __init__(self, embed_dim: int = 64, n_lists: int = 100, n_probe: int = 10, exact: bool = False):
         if not 1 <= int(embed_dim) <= 128:
             raise ValueError(f"SQ8Index: embed_dim={embed_dim} outside 1..128")
@@ -523,11 +527,53 @@ class SQ8Index(ExcludingSearch):
                                            L.ptr(ints), L.stream_ptr()), "sq8_index_search")
         return (scores, rows, ints) if return_int else (scores, rows)
 
+    def _scan_excluding(self, q: torch.Tensor, k: int, seen, uid: Optional[torch.Tensor], item_filter, mode: int,
+                        return_int: bool, refine, return_cert: bool, row_of: Optional[torch.Tensor] = None,
+                        k_scan: Optional[int] = None):
+        """exclusion="scan": one rihip_sq8_exclude_search (with a refine factor: rihip_sq8_refine_search_excluding at
+        k_scan = ceil(factor * k)) over the whole batch; the outputs of _search_device, item ids in place of rows"""
+        h = self._built()
+        lib = L.lib()
+        factor = self._refine if refine is _DEFAULT else _factor(refine)
+        if k < 1:
+            raise ValueError(f"SQ8Index: k={k} must be at least 1")
+        if k > int(lib.rihip_ip_index_max_k()):
+            raise ValueError(f"k={k} exceeds the device select buffer ({int(lib.rihip_ip_index_max_k())})")
+        if factor is not None and return_int:
+            raise ValueError("SQ8Index: return_int gives the 8-bit search's integer scores; a refined search has none")
+        if factor is None and return_cert:
+            raise ValueError("SQ8Index: return_cert needs a refined search (refine= or set_refine)")
+        if factor is not None and not self.has_vectors:
+            raise RuntimeError("SQ8Index: refine needs the f32 vectors (from_index(keep_vectors=True) or attach_vectors)")
+        nq = q.shape[0]
+        row_of = self._row_of_device() if row_of is None else self._check_row_of(row_of)
+        pred = (None, 0) if item_filter is None else self._pred(item_filter, nq, q.device)
+        L.check(lib.rihip_sq8_index_set_id_map(h._h, self._item_ids_dev.data_ptr()), "sq8_index_set_id_map")
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        seen_args = (L.ptr(uid), seen.offsets.data_ptr(), seen.n_users, seen.items.data_ptr(), row_of.data_ptr(),
+                     row_of.shape[0], L.ptr(pred[0]), pred[1])
+        if factor is not None:
+            cert = torch.empty((nq,), dtype=torch.uint8, device=q.device)
+            bound = torch.empty((nq,), dtype=torch.float64, device=q.device)
+            ks = self._k_scan(k, factor) if k_scan is None else k_scan
+            L.check(lib.rihip_sq8_refine_search_excluding(h._h, q.data_ptr(), nq, k, ks, mode, *seen_args, scores.data_ptr(),
+                                                          ids.data_ptr(), cert.data_ptr(), bound.data_ptr(), L.stream_ptr()),
+                    "sq8_refine_search_excluding")
+            return (scores, ids, cert, bound) if return_cert else (scores, ids)
+        ints = torch.empty((nq, k), dtype=torch.int32, device=q.device) if return_int else None
+        L.check(lib.rihip_sq8_exclude_search(h._h, q.data_ptr(), nq, k, mode, *seen_args, scores.data_ptr(), ids.data_ptr(),
+                                             L.ptr(ints), L.stream_ptr()), "sq8_exclude_search")
+        return (scores, ids, ints) if return_int else (scores, ids)
+
     def _excluding(self, q: torch.Tensor, k: int, seen, user_ids, item_filter, mode: int, return_int: bool, refine,
-                   return_cert: bool):
+                   return_cert: bool, exclusion: str = "overfetch"):
         """the search without each query's seen items: the over-fetched k_eff of seen.plan_overfetch is what is searched
         (and, with a refine factor, refined: k_scan = ceil(factor * k_eff)); a certificate then speaks of the over-fetched
-        list, whose first k unseen entries are the result"""
+        list, whose first k unseen entries are the result.  exclusion="scan": _scan_excluding instead"""
+        if check_exclusion(exclusion) == "scan":
+            return self._scan_excluding(q, k, seen, seen_user_ids(user_ids, q.shape[0], q.device), item_filter, mode,
+                                        return_int, refine, return_cert)
         if return_int:
             raise ValueError("SQ8Index: return_int is not available with exclude (the device filter moves scores and ids only)")
 
@@ -535,10 +581,11 @@ class SQ8Index(ExcludingSearch):
             return self._search_device(qq, kk, True, mode, False, refine, return_cert, flt)
         return self._search_excluding(q, k, seen, user_ids, item_filter, search=run)
 
-    def search(self, query_vector: np.ndarray, k: int = 500, refine=_DEFAULT, exclude_items=None, item_filter=None
-               ) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, query_vector: np.ndarray, k: int = 500, refine=_DEFAULT, exclude_items=None, item_filter=None,
+               exclusion: str = "overfetch") -> Tuple[np.ndarray, np.ndarray]:
         """exclude_items: item ids that must not be returned; item_filter: (any_of, all_of, none_of) over the items' tag
-        words, as in batch_search_device"""
+        words; exclusion: how exclude_items are kept out -- all as in batch_search_device"""
+        check_exclusion(exclusion)
         h = self._built()
         query = np.atleast_2d(query_vector).astype(np.float32)
         if query.shape[1] != self.embed_dim:
@@ -550,6 +597,10 @@ class SQ8Index(ExcludingSearch):
             from .seen import SeenItems
             ex = np.asarray(exclude_items, dtype=np.int64).reshape(-1)
             seen = SeenItems.from_pairs(np.zeros(ex.shape[0], np.int64), ex, 1)
+            if exclusion == "scan":
+                scores, ids = self._scan_excluding(q_dev, k, seen, None, item_filter, 0, False, refine, False)
+                distances, ids = scores[0].cpu().numpy(), ids[0].cpu().numpy()
+                return distances[ids >= 0], ids[ids >= 0]
             scores, ids = self._search_excluding(
                 q_dev, k, seen, None, item_filter,
                 search=lambda qq, kk, flt: self._search_device(qq, kk, True, 0, False, refine, False, flt))
@@ -561,9 +612,10 @@ class SQ8Index(ExcludingSearch):
         return distances[valid], self.item_ids[idx[valid]]
 
     def batch_search(self, query_vectors: np.ndarray, k: int = 500, refine=_DEFAULT, return_cert: bool = False,
-                     exclude=None, user_ids=None, item_filter=None):
+                     exclude=None, user_ids=None, item_filter=None, exclusion: str = "overfetch"):
         """(scores, item ids) as NumPy arrays; return_cert=True appends (cert u8 [nq], bound f64 [nq]); exclude /
-        user_ids / item_filter as in batch_search_device"""
+        user_ids / item_filter / exclusion as in batch_search_device"""
+        check_exclusion(exclusion)
         h = self._built()
         queries = np.asarray(query_vectors).astype(np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.embed_dim:
@@ -572,14 +624,15 @@ class SQ8Index(ExcludingSearch):
         k = min(k, h.ntotal)
         q_dev = torch.from_numpy(np.ascontiguousarray(queries)).to(L.device())
         if exclude is not None:
-            out = self._excluding(self._queries(q_dev), k, exclude, user_ids, item_filter, 0, False, refine, return_cert)
+            out = self._excluding(self._queries(q_dev), k, exclude, user_ids, item_filter, 0, False, refine, return_cert,
+                                  exclusion)
         else:
             out = self._search_device(self._queries(q_dev), k, True, 0, False, refine, return_cert, item_filter)
         return tuple(t.cpu().numpy() for t in out)
 
     def batch_search_device(self, queries: torch.Tensor, k: int = 500, normalized: bool = False, mode: str = "auto",
                             return_int: bool = False, refine=_DEFAULT, return_cert: bool = False, exclude=None,
-                            user_ids=None, item_filter=None):
+                            user_ids=None, item_filter=None, exclusion: str = "overfetch"):
         """queries f32 [nq, embed_dim] on the device -> (scores f32, item ids i64) [nq, k] on the device, -1 padded;
         return_int=True appends the integer scores i32 [nq, k].  mode: "auto", "dense" or "thresholded" (the same bytes
         from each; "thresholded" synchronises the stream for its completeness check).
@@ -599,14 +652,24 @@ class SQ8Index(ExcludingSearch):
         exclude (a seen.SeenItems) with user_ids [nq]: query q never returns an item of row user_ids[q] of the store
         (user_ids None: of row q); host user ids are searched in groups by how far each has to over-fetch (seen.plan_overfetch), a device tensor as
         one group at the store's longest list.  The over-fetched k_eff is what is searched and, with refine, refined.
-        With item_filter the result is filter AND not-seen.  Not with return_int."""
+        With item_filter the result is filter AND not-seen.  Not with return_int.
+
+        exclusion="scan" (opt-in; "overfetch", the default, is the paragraph above): the seen items are excluded inside
+        the int8 scan -- one bit per (query, row) of a mask built on the device from the store, tested where the tag
+        predicate is tested.  One search of the whole batch in every mode, no over-fetch and no limit on k plus a user's
+        list; the result is the first k of the probed rows by (S descending, row ascending) that are not seen (and
+        pass), bit for bit the scores the plain search reports for those rows; return_int works.  With refine the
+        excluded search at k_scan = ceil(factor * k) is stage 1, and cert = 1 proves the exact top k of the probed rows
+        that are not seen (and pass).  Item ids must lie in [0, 2**31 - 1).  Any other value: ValueError."""
+        check_exclusion(exclusion)
         h = self._built()
         m = _mode(mode)
         q = self._queries(queries)
         if not normalized:
             q = q / torch.clamp(torch.linalg.norm(q, dim=1, keepdim=True), min=1e-8)
         if exclude is not None:
-            return self._excluding(q, min(k, h.ntotal), exclude, user_ids, item_filter, m, return_int, refine, return_cert)
+            return self._excluding(q, min(k, h.ntotal), exclude, user_ids, item_filter, m, return_int, refine, return_cert,
+                                   exclusion)
         return self._search_device(q, min(k, h.ntotal), True, m, return_int, refine, return_cert, item_filter)
 
     def search_rows_device(self, queries: torch.Tensor, k: int, mode: str = "auto", return_int: bool = False, refine=_DEFAULT,
@@ -616,11 +679,16 @@ class SQ8Index(ExcludingSearch):
         return self._search_device(self._queries(queries), k, False, _mode(mode), return_int, refine, return_cert, item_filter)
 
     def search_certified(self, queries: torch.Tensor, k: int = 500, start: float = 2.0, normalized: bool = False,
-                         item_filter=None):
+                         item_filter=None, exclude=None, user_ids=None, exclusion: str = "overfetch"):
         """Refine at factor `start`, then repeat only the queries without a certificate with k_scan doubled until they
         have one or k_scan reaches the select buffer's size.  -> (scores f32 [nq, k], item ids i64 [nq, k], cert u8 [nq])
         on the device; a query whose flag is still 0 is reported as it is, not repaired.  item_filter: as in
-        batch_search_device; a repeat carries the predicates of the queries it repeats."""
+        batch_search_device; a repeat carries the predicates of the queries it repeats.  exclude / user_ids with
+        exclusion="scan": every stage 1 is the excluded search, so a certificate speaks of the probed rows the user has
+        not seen (the over-fetch route has no certified form: ValueError)."""
+        check_exclusion(exclusion)
+        if exclude is not None and exclusion != "scan":
+            raise ValueError('SQ8Index.search_certified: exclude needs exclusion="scan"')
         h = self._built()
         f = _factor(start)
         if f is None:
@@ -633,14 +701,22 @@ class SQ8Index(ExcludingSearch):
         if k < 1 or k > max_k:
             raise ValueError(f"SQ8Index: k={k} outside 1..{max_k}")
         k_scan = self._k_scan(k, f)
-        scores, ids, cert, _ = self._refined_device(q, k, k_scan, True, 0, item_filter)
+        uid = None if exclude is None else seen_user_ids(np.arange(q.shape[0]) if user_ids is None else user_ids,
+                                                         q.shape[0], q.device)
+
+        def refined(qq, ks, flt, sel=None):
+            if exclude is None:
+                return self._refined_device(qq, k, ks, True, 0, flt)
+            return self._scan_excluding(qq, k, exclude, uid if sel is None else uid[sel].contiguous(), flt, 0, False, 1.0,
+                                        True, k_scan=ks)
+        scores, ids, cert, _ = refined(q, k_scan, item_filter)
         while k_scan < max_k:
             todo = torch.nonzero(cert == 0).flatten()
             if todo.numel() == 0:
                 break
             k_scan = min(2 * k_scan, max_k)
-            s2, i2, c2, _ = self._refined_device(q[todo].contiguous(), k, k_scan, True, 0,
-                                                 None if item_filter is None else _sub_filter(item_filter, todo))
+            s2, i2, c2, _ = refined(q[todo].contiguous(), k_scan,
+                                    None if item_filter is None else _sub_filter(item_filter, todo), todo)
             scores[todo], ids[todo], cert[todo] = s2, i2, c2
         return scores, ids, cert
 
