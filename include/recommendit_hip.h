@@ -818,6 +818,41 @@ int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, const int64_t*
 int rihip_sq8_update_assign(void* handle, const float* X, int64_t n, int32_t* assign_out, void* stream);
 int rihip_sq8_update_stats(void* handle, int64_t* out);     /* out: int64[4] */
 
+/* ---- Product-quantised index (faiss IndexPQ / IndexIVFPQ; the reference's FAISSIndex has none) -------------------
+ * An sq8_index handle whose storage is one byte per sub-space and row plus int8 codebooks: dpad / dsub bytes per row
+ * (dsub = 8 or 16 dimensions per sub-space) instead of dpad.  The quantiser works on the rows' SQ8 codes
+ * c[i][j] = the SQ8 code of x_ij under (centre, scale) (trained as above, or injected; padding columns 0), in integers:
+ *   sub-space m = columns m dsub .. + dsub - 1, M = dpad / dsub (one lying in the padding columns is treated like any other);
+ *   book[m][e][j] int8 in [-127, 127], 256 entries per sub-space;
+ *   D(i, m, e) = sum_j (c[i][m dsub + j] - book[m][e][j])^2 (i32); a row's byte is the e of the smallest D, lowest e on ties;
+ *   init: book[m][e] = the sub-vector of original row (e N) / 256 (int64; N < 256 repeats rows, the repeats stay empty);
+ *   one Lloyd step: assign every stored row, book[m][e][j] = clamp(rint((double)sum / (double)cnt), -127, 127) (half to
+ *   even) over the rows assigned to e, exact integer sums; an entry with cnt = 0 keeps its value;
+ *   n_iter steps, then the final assignment, which is stored.  The sum of the smallest D of every assignment pass is the
+ *   distortion trace (n_iter + 1 values).  Nothing depends on the physical row order: a flat and an IVF build of the same
+ *   rows under the same (centre, scale) give the same codebooks and the same byte for every original row.
+ *   Decoded code c^[i][m dsub + j] = book[m][byte[i][m]][j].
+ * No residual encoding against the IVF centroids: one integer score per row, comparable across lists.
+ * from_ip_index: as the SQ8 call; book host int8 [M,256,dsub] injects the codebooks and skips training (no byte -128).
+ * The build holds the SQ8 codes transiently (train_stats: peak_bytes) and frees them before it returns.
+ * Every rihip_sq8_* search, filter, exclude, refine, stats and id-map call takes the handle and returns what it returns
+ * on the SQ8 index whose code matrix is the decoded one; rihip_sq8_index_get_codes / _reconstruct return that decoded
+ * matrix (a transient N * dpad bytes on the device, as rihip_sq8_refine_attach_vectors takes for e_j / a_j).
+ * rihip_sq8_update_apply returns RIHIP_ERR_STATE and changes nothing; rihip_sq8_index_save refuses the handle.
+ * get_codes: host uint8 [N,M] in original row order; get_codebooks: host int8 [M,256,dsub]; dims: dsub and M.
+ * train_stats: trace (up to cap values; *n_trace = how many the build recorded: n_iter + 1, 1 with injected codebooks, 0
+ * after load), peak_bytes, ms[3] = host time of {range pass + SQ8 encode, training, final assignment}; any may be NULL.
+ * save / load: own format ("RIHIPPQ1", version word, range-checked header); each of the two loaders refuses the other's
+ * file.  faiss PQ files are not read or written. */
+int rihip_pq_index_from_ip_index(void* ip_handle, const float* centre, const float* scale, int dsub, int n_iter,
+                                 const int8_t* book, void** handle, void* stream);
+int rihip_pq_index_dims(void* handle, int* dsub, int* M);
+int rihip_pq_index_get_codes(void* handle, uint8_t* out);          /* synchronous */
+int rihip_pq_index_get_codebooks(void* handle, int8_t* out);       /* synchronous */
+int rihip_pq_index_train_stats(void* handle, int64_t* trace, int cap, int* n_trace, int64_t* peak_bytes, double* ms);
+int rihip_pq_index_save(void* handle, const char* path);           /* host path; synchronous */
+int rihip_pq_index_load(const char* path, void** handle);          /* host path; synchronous */
+
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict
  * (ranker.py:174): raw score = sum over trees of the reached leaf value, float64.

@@ -181,6 +181,13 @@ SIGNATURES = {
                                          C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_int), vp]),
     "rihip_sq8_update_assign": (C.c_int, [vp, vp, c_i64, vp, vp]),
     "rihip_sq8_update_stats": (C.c_int, [vp, vp]),
+    "rihip_pq_index_from_ip_index": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp), vp]),
+    "rihip_pq_index_dims": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rihip_pq_index_get_codes": (C.c_int, [vp, vp]),
+    "rihip_pq_index_get_codebooks": (C.c_int, [vp, vp]),
+    "rihip_pq_index_train_stats": (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(c_i64), vp]),
+    "rihip_pq_index_save": (C.c_int, [vp, C.c_char_p]),
+    "rihip_pq_index_load": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

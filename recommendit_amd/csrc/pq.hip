@@ -1,0 +1,429 @@
+// Product-quantised inner-product index: the training, encoding and decoding kernels, the build and the C ABI.
+//
+// A PQ index is an Sq8Index handle whose code storage is one byte per sub-space and row (pq_codes) plus int8 codebooks
+// (pq_book) in place of the int8 matrix: the row's SQ8 code is, per sub-space, the codebook entry its byte names.  The
+// search is sq8.hip's, whose scan gathers the operand bytes from the codebooks in LDS (sq8_scan_lm_kernel<DP, FM, PQ>);
+// nothing else of the search knows the difference, so a PQ index is the SQ8 index of its own reconstruction.
+//
+// The quantiser works on the rows' SQ8 codes c (int8, padding columns 0), in integers only (recommendit_hip.h at
+// rihip_pq_index_*): sub-space m covers columns m dsub .. + dsub - 1; D(i, m, e) = sum_j (c[i][m dsub + j] - book[m][e][j])^2
+// in i32; a row's byte is the e of the smallest D, the lowest e on a tie; a Lloyd step replaces an entry by
+// clamp(rint((double)sum / (double)cnt), +-127) of the rows assigned to it (exact integer sums) and leaves an entry without
+// rows as it is.  The sums are integer atomics, privatised in LDS per workgroup and then added to i64 words in global
+// memory: exact in any order, so the result does not depend on the physical row order.
+//
+// D is evaluated as |c|^2 + |b|^2 - 2 <c, b> with the packed int8 dot product (v_dot4_i32_i8): the same integer.
+#pragma clang fp contract(off)
+#include "common.h"
+#include "recommendit_hip.h"
+
+#include <algorithm>
+#include <chrono>
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+#include "search_kernels.h"
+#include "sq8_index.h"
+
+using namespace rihip_index;
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64;
+
+constexpr int PQ_RPT = 8;                 // rows per thread of the assignment kernel
+constexpr int PQ_RPB = 256 * PQ_RPT;      // rows per workgroup: an LDS sum stays below 2048 * 127 < 2^18
+
+__device__ __forceinline__ int dot4(uint32_t a, uint32_t b, int acc) {   // four signed bytes each, exact in i32
+  return __builtin_amdgcn_sdot4((int)a, (int)b, acc, false);
+}
+
+// book[m][e][:] = the SQ8 sub-vectors of ORIGINAL row (e N) / 256 (int64).  One thread per physical row: the entries that
+// name its row are e = ceil(256 row / N) .. while (e N) / 256 == row (none for most rows; several where N < 256)
+__global__ void pq_init_book_kernel(const int8_t* __restrict__ codes, const int64_t* __restrict__ row_ids, int64_t N, int64_t Np,
+                                    int dpad, int dsub, int8_t* book) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= Np) return;
+  const int64_t row = row_ids[p];
+  if (row < 0) return;
+  for (int64_t e = (row * 256 + N - 1) / N; e < 256 && (e * N) / 256 == row; ++e)
+    for (int j = 0; j < dpad; ++j) book[((size_t)(j / dsub) * 256 + e) * dsub + (j % dsub)] = codes[(size_t)p * dpad + j];
+}
+
+// One assignment pass of sub-space blockIdx.y over the physical rows [blockIdx.x * PQ_RPB, + PQ_RPB).  The sub-space's 256
+// entries lie in LDS as packed words next to their squared norms and are read as a broadcast (every lane the same
+// address); a thread holds its row's DSUB bytes in registers.  ACC: the row is added to the sums of its entry, first in
+// LDS (i32), then once per workgroup and non-zero word in global memory (i64).  Padding rows (row_ids < 0) get byte 0 and
+// take no part.  *distortion += the pass's sum of the smallest D.
+template <int DSUB, bool ACC>
+__global__ __launch_bounds__(256) void pq_assign_kernel(const int8_t* __restrict__ codes, const int64_t* __restrict__ row_ids,
+                                                        int64_t Np, int dpad, const int8_t* __restrict__ book, uint8_t* pq_codes,
+                                                        u64* gsum, u64* gcnt, u64* distortion) {
+  constexpr int W = DSUB / 4;
+  __shared__ uint32_t s_b[256 * W];
+  __shared__ int s_n[256];
+  __shared__ int s_sum[ACC ? 256 * DSUB : 1];
+  __shared__ int s_cnt[ACC ? 256 : 1];
+  const int tid = threadIdx.x, m = blockIdx.y, M = dpad / DSUB;
+  {
+    const uint32_t* gb = reinterpret_cast<const uint32_t*>(book + ((size_t)m * 256 + tid) * DSUB);
+    int nn = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const uint32_t v = gb[w];
+      s_b[tid * W + w] = v;
+      nn = dot4(v, v, nn);
+    }
+    s_n[tid] = nn;
+    if constexpr (ACC) {
+#pragma unroll
+      for (int j = 0; j < DSUB; ++j) s_sum[tid * DSUB + j] = 0;
+      s_cnt[tid] = 0;
+    }
+  }
+  __syncthreads();
+  long long dist = 0;
+  const int64_t base = (int64_t)blockIdx.x * PQ_RPB;
+  for (int it = 0; it < PQ_RPT; ++it) {
+    const int64_t p = base + it * 256 + tid;
+    if (p >= Np) continue;
+    int best = 0;
+    if (row_ids[p] >= 0) {
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (size_t)p * dpad + m * DSUB);
+      uint32_t c[W];
+      int cn = 0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) { c[w] = src[w]; cn = dot4(c[w], c[w], cn); }
+      int bd = INT_MAX;
+#pragma unroll 4
+      for (int e = 0; e < 256; ++e) {
+        int dp = 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) dp = dot4(c[w], s_b[e * W + w], dp);
+        const int d = s_n[e] - 2 * dp;
+        if (d < bd) { bd = d; best = e; }   // strictly smaller: the lowest e keeps a tie
+      }
+      dist += cn + bd;
+      if constexpr (ACC) {
+#pragma unroll
+        for (int j = 0; j < DSUB; ++j) {
+          const int v = (int)(int8_t)(c[j >> 2] >> (8 * (j & 3)));
+          if (v != 0) atomicAdd(&s_sum[best * DSUB + j], v);
+        }
+        atomicAdd(&s_cnt[best], 1);
+      }
+    }
+    pq_codes[(size_t)p * M + m] = (uint8_t)best;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dist += __shfl_xor(dist, o, 64);
+  if ((tid & 63) == 0 && dist != 0) atomicAdd(distortion, (u64)dist);
+  if constexpr (ACC) {
+    __syncthreads();
+    for (int i = tid; i < 256 * DSUB; i += 256) {
+      const int v = s_sum[i];
+      if (v != 0) atomicAdd(&gsum[(size_t)m * 256 * DSUB + i], (u64)(long long)v);   // two's complement: a signed i64 sum
+    }
+    if (s_cnt[tid] != 0) atomicAdd(&gcnt[m * 256 + tid], (u64)s_cnt[tid]);
+  }
+}
+
+// the Lloyd step's division, one thread per codebook byte; an entry without rows keeps its value
+__global__ void pq_update_book_kernel(const u64* __restrict__ gsum, const u64* __restrict__ gcnt, int n, int dsub, int8_t* book) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u64 cnt = gcnt[i / dsub];
+  if (cnt == 0) return;
+  double v = rint((double)(long long)gsum[i] / (double)cnt);   // one correctly rounded division, half to even
+  v = fmin(fmax(v, -127.0), 127.0);
+  book[i] = (int8_t)(int)v;
+}
+
+// pq_decode_rows: entry numbers + codebooks -> int8 [rows, dpad], one thread per (row, sub-space); padding rows are zeros
+template <int DSUB>
+__global__ void pq_decode_rows_kernel(const uint8_t* __restrict__ pq_codes, const int8_t* __restrict__ book,
+                                      const int64_t* __restrict__ row_ids, int64_t rows, int dpad, int8_t* out) {
+  typedef typename std::conditional<DSUB == 8, uint2, i32x4>::type V;
+  const int M = dpad / DSUB;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * M) return;
+  const int64_t p = i / M;
+  const int m = (int)(i % M);
+  V v{};
+  if (row_ids[p] >= 0) v = *reinterpret_cast<const V*>(book + ((size_t)m * 256 + pq_codes[i]) * DSUB);
+  *reinterpret_cast<V*>(out + (size_t)p * dpad + m * DSUB) = v;
+}
+
+// the entry numbers in original row order
+__global__ void pq_codes_by_row_kernel(const uint8_t* __restrict__ pq_codes, const int64_t* __restrict__ row_ids, int64_t Np, int M,
+                                       uint8_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Np * M) return;
+  const int64_t row = row_ids[i / M];
+  if (row >= 0) out[(size_t)row * M + (i % M)] = pq_codes[i];
+}
+
+template <bool ACC>
+void launch_assign_pass(const Sq8Index* h, const int8_t* codes, int dsub, u64* gsum, u64* gcnt, u64* dist, hipStream_t st) {
+  const dim3 grid((unsigned)((h->Np + PQ_RPB - 1) / PQ_RPB), (unsigned)(h->dpad / dsub));
+  if (dsub == 8)
+    hipLaunchKernelGGL((pq_assign_kernel<8, ACC>), grid, dim3(256), 0, st, codes, h->row_ids, h->Np, h->dpad, h->pq_book, h->pq_codes, gsum, gcnt, dist);
+  else
+    hipLaunchKernelGGL((pq_assign_kernel<16, ACC>), grid, dim3(256), 0, st, codes, h->row_ids, h->Np, h->dpad, h->pq_book, h->pq_codes, gsum, gcnt, dist);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct PqTimes { double sq8 = 0, train = 0, encode = 0; };
+
+// h: a fresh handle.  The SQ8 build first (layout, row ids, quantiser and, transiently, the int8 codes), then the
+// codebooks (injected, or trained in n_iter Lloyd steps) and the final assignment; the int8 codes are freed before the
+// call returns.
+int pq_build(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, int dsub, int n_iter, const int8_t* book_host,
+             PqTimes* tm, hipStream_t st) {
+  auto t0 = std::chrono::steady_clock::now();
+  RCCHK(sq8_build_handle(h, src, centre, scale, st));   // (synchronises)
+  tm->sq8 = ms_since(t0);
+  const int M = h->dpad / dsub;
+  const size_t book_bytes = (size_t)h->dpad * 256;
+  int8_t* sq8_codes = h->codes;
+  u64* gsum = nullptr; u64* gcnt = nullptr; u64* dist = nullptr;
+  const int64_t sq8_bytes = sq8_held_bytes(h);
+  auto work = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&h->pq_codes, (size_t)h->Np * M));
+    HIPCHK(hipMalloc((void**)&h->pq_book, book_bytes));
+    HIPCHK(hipMalloc((void**)&dist, sizeof(u64) * (size_t)(n_iter + 1)));
+    HIPCHK(hipMemsetAsync(dist, 0, sizeof(u64) * (size_t)(n_iter + 1), st));
+    h->pq_dsub = dsub;
+    h->pq_peak_bytes = sq8_bytes + h->Np * M + (int64_t)book_bytes + 8 * (int64_t)(n_iter + 1);
+    auto t1 = std::chrono::steady_clock::now();
+    int passes = 1;
+    if (book_host) {
+      HIPCHK(hipMemcpyAsync(h->pq_book, book_host, book_bytes, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    } else {
+      passes = n_iter + 1;
+      HIPCHK(hipMalloc((void**)&gsum, sizeof(u64) * book_bytes));
+      HIPCHK(hipMalloc((void**)&gcnt, sizeof(u64) * (size_t)M * 256));
+      h->pq_peak_bytes += 8 * (int64_t)book_bytes + 8 * (int64_t)M * 256;
+      hipLaunchKernelGGL(pq_init_book_kernel, dim3((unsigned)((h->Np + 255) / 256)), dim3(256), 0, st, sq8_codes, h->row_ids, h->N, h->Np,
+                         h->dpad, dsub, h->pq_book);
+      for (int it = 0; it < n_iter; ++it) {
+        HIPCHK(hipMemsetAsync(gsum, 0, sizeof(u64) * book_bytes, st));
+        HIPCHK(hipMemsetAsync(gcnt, 0, sizeof(u64) * (size_t)M * 256, st));
+        launch_assign_pass<true>(h, sq8_codes, dsub, gsum, gcnt, dist + it, st);
+        hipLaunchKernelGGL(pq_update_book_kernel, dim3((unsigned)((book_bytes + 255) / 256)), dim3(256), 0, st, gsum, gcnt, (int)book_bytes,
+                           dsub, h->pq_book);
+      }
+      RCCHK(check_launch("pq train"));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    tm->train = ms_since(t1);
+    auto t2 = std::chrono::steady_clock::now();
+    launch_assign_pass<false>(h, sq8_codes, dsub, nullptr, nullptr, dist + (passes - 1), st);
+    RCCHK(check_launch("pq encode"));
+    std::vector<u64> tr(passes);
+    HIPCHK(hipMemcpyAsync(tr.data(), dist, sizeof(u64) * passes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    tm->encode = ms_since(t2);
+    h->pq_trace.assign(tr.begin(), tr.end());
+    return RIHIP_OK;
+  };
+  const int rc = work();
+  hipFree(gsum); hipFree(gcnt); hipFree(dist);
+  if (rc) return rc;   // (the caller frees the handle and with it whatever was allocated)
+  hipFree(h->codes);
+  h->codes = nullptr;
+  return RIHIP_OK;
+}
+
+}  // namespace
+
+namespace rihip_index {
+int pq_decode_all(const Sq8Index* h, int8_t** out_dev, hipStream_t st) {
+  RIHIP_REQUIRE(h && h->pq_codes && h->pq_book && out_dev, RIHIP_ERR_STATE, "pq_decode_rows: not a PQ index");
+  int8_t* out = nullptr;
+  HIPCHK(hipMalloc((void**)&out, (size_t)h->Np * h->dpad));
+  const int64_t tot = h->Np * (h->dpad / h->pq_dsub);
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (h->pq_dsub == 8) hipLaunchKernelGGL(pq_decode_rows_kernel<8>, grid, dim3(256), 0, st, h->pq_codes, h->pq_book, h->row_ids, h->Np, h->dpad, out);
+  else hipLaunchKernelGGL(pq_decode_rows_kernel<16>, grid, dim3(256), 0, st, h->pq_codes, h->pq_book, h->row_ids, h->Np, h->dpad, out);
+  const int rc = check_launch("pq decode rows");
+  if (rc) { hipFree(out); return rc; }
+  *out_dev = out;
+  return RIHIP_OK;
+}
+}  // namespace rihip_index
+
+// ------------------------------------------------ C ABI --------------------------------------------------------------
+extern "C" int rihip_pq_index_from_ip_index(void* ip_handle, const float* centre, const float* scale, int dsub, int n_iter,
+                                            const int8_t* book, void** handle, void* stream) {
+  const IpIndex* src = (const IpIndex*)ip_handle;
+  RIHIP_REQUIRE(src && handle, RIHIP_ERR_ARG, "pq_index_from_ip_index: null handle");
+  RIHIP_REQUIRE(src->X && src->N > 0, RIHIP_ERR_STATE, "pq_index_from_ip_index: the source index is empty");
+  RIHIP_REQUIRE((centre == nullptr) == (scale == nullptr), RIHIP_ERR_ARG, "pq_index_from_ip_index: give both centre and scale, or neither");
+  RIHIP_REQUIRE(dsub == 8 || dsub == 16, RIHIP_ERR_ARG, "pq_index_from_ip_index: dsub=%d (8 or 16)", dsub);
+  RIHIP_REQUIRE(n_iter >= 0 && n_iter <= 1000, RIHIP_ERR_ARG, "pq_index_from_ip_index: n_iter=%d outside [0, 1000]", n_iter);
+  if (book) {
+    const size_t nb = (size_t)(src->d <= 64 ? 64 : 128) * 256;
+    for (size_t i = 0; i < nb; ++i)
+      RIHIP_REQUIRE(book[i] != -128, RIHIP_ERR_ARG, "pq_index_from_ip_index: codebook byte %lld is -128 (entries lie in [-127, 127])", (long long)i);
+  }
+  Sq8Index* h = new Sq8Index();
+  PqTimes tm;
+  const int rc = pq_build(h, src, centre, scale, dsub, n_iter, book, &tm, (hipStream_t)stream);
+  if (rc) { sq8_free_handle(h); return rc; }
+  h->pq_ms[0] = tm.sq8; h->pq_ms[1] = tm.train; h->pq_ms[2] = tm.encode;
+  *handle = h;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_pq_index_dims(void* handle, int* dsub, int* M) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->pq_codes && dsub && M, RIHIP_ERR_STATE, "pq_index_dims: not a PQ index");
+  *dsub = h->pq_dsub; *M = h->dpad / h->pq_dsub;
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_pq_index_get_codes(void* handle, uint8_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->pq_codes && out, RIHIP_ERR_STATE, "pq_index_get_codes: not a PQ index");
+  const int M = h->dpad / h->pq_dsub;
+  uint8_t* d = nullptr;
+  HIPCHK(hipMalloc((void**)&d, (size_t)h->N * M));
+  const int64_t tot = h->Np * M;
+  hipLaunchKernelGGL(pq_codes_by_row_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, h->pq_codes, h->row_ids, h->Np, M, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)h->N * M, hipMemcpyDeviceToHost);
+  hipFree(d);
+  HIPCHK(e);
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_pq_index_get_codebooks(void* handle, int8_t* out) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->pq_codes && out, RIHIP_ERR_STATE, "pq_index_get_codebooks: not a PQ index");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, h->pq_book, (size_t)h->dpad * 256, hipMemcpyDeviceToHost));
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_pq_index_train_stats(void* handle, int64_t* trace, int cap, int* n_trace, int64_t* peak_bytes, double* ms) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && h->pq_codes && n_trace, RIHIP_ERR_STATE, "pq_index_train_stats: not a PQ index");
+  *n_trace = (int)h->pq_trace.size();
+  if (trace) for (int i = 0; i < cap && i < *n_trace; ++i) trace[i] = h->pq_trace[i];
+  if (peak_bytes) *peak_bytes = h->pq_peak_bytes;
+  if (ms) for (int i = 0; i < 3; ++i) ms[i] = h->pq_ms[i];
+  return RIHIP_OK;
+}
+
+// File: "RIHIPPQ1", int64 header {version 1, du, dk, dpad, N, Np, nlist, nprobe, dsub, M}, centre f32[dpad], scale
+// f32[dpad], centroids f32[nlist, dk], list lengths int64[nlist], row ids int64[Np], codebooks int8[M, 256, dsub],
+// entry numbers uint8[Np, M]
+extern "C" int rihip_pq_index_save(void* handle, const char* path) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(h && path, RIHIP_ERR_ARG, "pq_index_save: bad arguments");
+  RIHIP_REQUIRE(h->pq_codes, RIHIP_ERR_STATE, "pq_index_save: not a PQ index (an SQ8 index is saved by rihip_sq8_index_save)");
+  const int M = h->dpad / h->pq_dsub;
+  std::vector<float> m(h->dpad), s(h->dpad), C((size_t)h->nlist * h->dk);
+  std::vector<int64_t> rid((size_t)h->Np);
+  std::vector<int8_t> book((size_t)h->dpad * 256);
+  std::vector<uint8_t> codes((size_t)h->Np * M);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(m.data(), h->centre, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(s.data(), h->scale, sizeof(float) * s.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(C.data(), h->C, sizeof(float) * C.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rid.data(), h->row_ids, sizeof(int64_t) * rid.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(book.data(), h->pq_book, book.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(codes.data(), h->pq_codes, codes.size(), hipMemcpyDeviceToHost));
+  FILE* f = fopen(path, "wb");
+  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "pq_index_save: cannot open %s", path);
+  const int64_t hdr[10] = {1, h->du, h->dk, h->dpad, h->N, h->Np, h->nlist, h->nprobe, h->pq_dsub, M};
+  bool ok = fwrite("RIHIPPQ1", 1, 8, f) == 8 && fwrite(hdr, sizeof(int64_t), 10, f) == 10 &&
+            fwrite(m.data(), sizeof(float), m.size(), f) == m.size() && fwrite(s.data(), sizeof(float), s.size(), f) == s.size() &&
+            fwrite(C.data(), sizeof(float), C.size(), f) == C.size() &&
+            fwrite(h->list_len.data(), sizeof(int64_t), h->nlist, f) == (size_t)h->nlist &&
+            fwrite(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fwrite(book.data(), 1, book.size(), f) == book.size() &&
+            fwrite(codes.data(), 1, codes.size(), f) == codes.size();
+  ok = (fclose(f) == 0) && ok;
+  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "pq_index_save: short write to %s", path);
+  return RIHIP_OK;
+}
+
+extern "C" int rihip_pq_index_load(const char* path, void** handle) {
+  RIHIP_REQUIRE(path && handle, RIHIP_ERR_ARG, "pq_index_load: bad arguments");
+  FILE* f = fopen(path, "rb");
+  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "pq_index_load: cannot open %s", path);
+  char magic[8]; int64_t hdr[10];
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "RIHIPPQ1", 8) != 0 || fread(hdr, sizeof(int64_t), 10, f) != 10 || hdr[0] != 1) {
+    fclose(f); rihip_set_error("pq_index_load: %s is not a PQ index file (magic / version)", path); return RIHIP_ERR_IO;
+  }
+  const int64_t du = hdr[1], dk = hdr[2], dpad = hdr[3], N = hdr[4], Np = hdr[5], nlist = hdr[6], nprobe = hdr[7], dsub = hdr[8], M = hdr[9];
+  const bool hdr_ok = du >= 1 && du <= 128 && dk == (du <= 32 ? 32 : (du <= 64 ? 64 : 128)) && dpad == (dk <= 64 ? 64 : 128) &&
+                      N >= 1 && N < (1ll << 31) && nlist >= 1 && nlist <= NLIST_MAX && nprobe >= 1 && nprobe < (1ll << 31) &&
+                      Np >= N && Np % TR == 0 && Np <= N + (int64_t)TR * nlist && (dsub == 8 || dsub == 16) && M * dsub == dpad;
+  int64_t expect = 0, have = -1;
+  if (hdr_ok) {
+    expect = 8 + 80 + 8 * dpad + 4 * nlist * dk + 8 * nlist + 8 * Np + 256 * dpad + Np * M;
+    if (fseek(f, 0, SEEK_END) == 0) have = (int64_t)ftell(f);
+    if (fseek(f, 88, SEEK_SET) != 0) have = -1;
+  }
+  if (!hdr_ok || have != expect) {
+    fclose(f);
+    rihip_set_error("pq_index_load: %s: %s", path, hdr_ok ? "file size does not match its header (truncated?)" : "header field out of range");
+    return RIHIP_ERR_IO;
+  }
+  std::vector<float> m(dpad), s(dpad), C((size_t)nlist * dk);
+  std::vector<int64_t> ll(nlist), rid((size_t)Np);
+  std::vector<int8_t> book((size_t)dpad * 256);
+  std::vector<uint8_t> codes((size_t)Np * M);
+  bool ok = fread(m.data(), sizeof(float), m.size(), f) == m.size() && fread(s.data(), sizeof(float), s.size(), f) == s.size() &&
+            fread(C.data(), sizeof(float), C.size(), f) == C.size() && fread(ll.data(), sizeof(int64_t), nlist, f) == (size_t)nlist &&
+            fread(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fread(book.data(), 1, book.size(), f) == book.size() &&
+            fread(codes.data(), 1, codes.size(), f) == codes.size();
+  fclose(f);
+  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "pq_index_load: short read from %s", path);
+  int64_t tot = 0, ptot = 0;
+  for (int64_t c = 0; c < nlist; ++c) {
+    RIHIP_REQUIRE(ll[c] >= 0 && ll[c] <= N, RIHIP_ERR_IO, "pq_index_load: %s: list %lld has length %lld", path, (long long)c, (long long)ll[c]);
+    tot += ll[c]; ptot += (ll[c] + TR - 1) / TR * TR;
+  }
+  RIHIP_REQUIRE(tot == N && ptot == Np, RIHIP_ERR_IO, "pq_index_load: %s: list lengths do not add up to the header's row counts", path);
+  for (int64_t p = 0; p < Np; ++p)
+    RIHIP_REQUIRE(rid[p] >= -1 && rid[p] < N, RIHIP_ERR_IO, "pq_index_load: %s: row id %lld out of range", path, (long long)rid[p]);
+  for (int64_t j = 0; j < dpad; ++j)
+    RIHIP_REQUIRE(isfinite(m[j]) && isfinite(s[j]) && s[j] > 0.f, RIHIP_ERR_IO, "pq_index_load: %s: quantiser column %lld is not finite", path, (long long)j);
+  for (size_t i = 0; i < book.size(); ++i)
+    RIHIP_REQUIRE(book[i] != -128, RIHIP_ERR_IO, "pq_index_load: %s: codebook byte %lld is -128", path, (long long)i);
+  Sq8Index* h = new Sq8Index();
+  h->du = (int)du; h->dk = (int)dk; h->dpad = (int)dpad; h->N = N; h->Np = Np; h->nlist = (int)nlist; h->nprobe = (int)nprobe;
+  h->list_len = ll;
+  h->pq_dsub = (int)dsub;
+  auto fill = [&]() -> int {
+    RCCHK(sq8_upload_list_layout(h, 0));
+    HIPCHK(hipMalloc((void**)&h->row_ids, sizeof(int64_t) * rid.size()));
+    HIPCHK(hipMalloc((void**)&h->C, sizeof(float) * C.size()));
+    HIPCHK(hipMalloc((void**)&h->pq_codes, codes.size()));
+    HIPCHK(hipMalloc((void**)&h->pq_book, book.size()));
+    HIPCHK(hipMalloc((void**)&h->centre, sizeof(float) * dpad));
+    HIPCHK(hipMalloc((void**)&h->scale, sizeof(float) * dpad));
+    HIPCHK(hipMemcpy(h->row_ids, rid.data(), sizeof(int64_t) * rid.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->C, C.data(), sizeof(float) * C.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->pq_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->pq_book, book.data(), book.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->centre, m.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->scale, s.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
+    return RIHIP_OK;
+  };
+  const int rc = fill();
+  if (rc) { sq8_free_handle(h); return rc; }
+  h->pq_peak_bytes = sq8_held_bytes(h);
+  *handle = h;
+  return RIHIP_OK;
+}

@@ -15,6 +15,10 @@
 //
 // Opt-in on top of that (the "refined search" section): the source's f32 rows attached next to the codes, an exact f32
 // re-score of the search's best k_scan candidates, and a per-query certificate that the re-ranked list is the exact one.
+//
+// A handle may hold product-quantised storage instead of the int8 matrix (pq.hip builds it: one byte per sub-space and row
+// plus int8 codebooks).  sq8_scan picks the source; the PQ instantiations of the scan gather the operand bytes from the
+// codebooks in LDS, and everything else in this file is the same code for both.
 #pragma clang fp contract(off)   // the quantiser is specified operation by operation: no fused multiply-add
 #include "common.h"
 #include "recommendit_hip.h"
@@ -44,7 +48,9 @@ constexpr int SQ8_SS = 16;                      // threshold sample: every 16th 
 constexpr int64_t SQ8_CH = 4096;                // queries per internal pass at most
 
 int64_t held_bytes(const Sq8Index* h) {
-  return (int64_t)h->Np * h->dpad + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
+  // the code storage: the int8 matrix, or (a PQ handle) one byte per sub-space and row plus the codebooks
+  const int64_t rows = h->pq_codes ? h->Np * (h->dpad / h->pq_dsub) + 256 * (int64_t)h->dpad : h->Np * h->dpad;
+  return rows + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
          4 * (int64_t)h->nlist + 8 * h->Np + (h->vec ? 4 * h->N * h->dk + 2 * 8 * (int64_t)h->dk : 0) + (h->tags ? 4 * h->Np : 0);
 }
 
@@ -69,7 +75,7 @@ void free_sq8(Sq8Index* h) {
   h->fpred.release(); h->xmask.release();
   hipFree(h->inv_pos);
   h->rs.release(); h->rr.release(); h->ri.release(); h->rnv.release(); h->rcut.release(); h->rkeys.release();
-  hipFree(h->codes); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
+  hipFree(h->codes); hipFree(h->pq_codes); hipFree(h->pq_book); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
   hipFree(h->row_ids);
   h->qhi.release(); h->qlo.release(); h->fhi.release(); h->flo.release(); h->qt.release(); h->qpad.release(); h->fQ.release();
   h->coarse.release(); h->thr.release(); h->qb.release(); h->cand.release(); h->scand.release(); h->fcand.release();
@@ -221,6 +227,8 @@ struct Sq8LmArgs {
   const uint32_t* xmask;
   int64_t xW;
   const int* xrow;
+  // product-quantised source (the PQ instantiations): codes is then the [Np, DP / PQ] matrix of entry numbers
+  const int8_t* pq_book;     // [DP / PQ, 256, PQ]
 };
 
 __device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
@@ -241,10 +249,27 @@ __device__ __forceinline__ int sq8_score_of_word(uint32_t hw) { return (int)(hw 
 // FM (search_keys.h): FM_TAGS is the above; FM_TAGS_MASK / FM_MASK add the seen-item mask: the tile is one aligned word of
 // the lane's query, loaded one tile ahead with the code and tag loads; FM_MASK compiles the tag test out (an untagged
 // index).  FM_NONE and FM_TAGS are the kernels as they were.
-template <int DP, int FM = FM_NONE>
+//
+// PQ = 8 / 16 (0: the int8 matrix as above): the source is product-quantised with PQ dimensions per sub-space.  The
+// workgroup copies the codebooks [DP / PQ, 256, PQ] to LDS once (DP * 256 bytes: two workgroups per CU still fit) and
+// meets at one barrier before any wave leaves.  What is loaded one tile ahead is the row's DP / PQ entry numbers; the 16
+// operand bytes of lane (r, h) at k-step ks are then gathered from LDS when the tile's chain starts: columns
+// 32 ks + 16 h .. + 15 are sub-spaces 4 ks + 2 h and + 1 (PQ = 8: two 8-byte reads) or sub-space 2 ks + h (PQ = 16: one
+// 16-byte read).  An entry lies in LDS in column order, so the lane holds the bytes the int8 matrix of the decoded rows
+// would have given it, in the same order: the B side does not change.  A row beyond its list's length decodes to entry 0
+// of every sub-space, not to zeros; n_ok keeps it out of every emission, as before.
+template <int DP, int FM = FM_NONE, int PQ = 0>
 __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
   constexpr bool FILT = FM == FM_TAGS || FM == FM_TAGS_MASK, XM = FM == FM_TAGS_MASK || FM == FM_MASK;
   constexpr int KS = DP / 32;
+  constexpr int CW = PQ ? DP / PQ / 4 : 1;   // 32-bit words of entry numbers per row
+  __shared__ i32x4 s_book[PQ ? DP * 16 : 1];
+  if constexpr (PQ != 0) {
+    if (blockIdx.x * 4 >= a.plan[0]) return;   // workgroup-uniform: no wave of it has work
+    const i32x4* gb = reinterpret_cast<const i32x4*>(a.pq_book);
+    for (int i = threadIdx.x; i < DP * 16; i += 256) s_book[i] = gb[i];
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r31 = lane & 31, hh = lane >> 5;
   const int wi = blockIdx.x * 4 + w;
@@ -290,6 +315,29 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) dst[ks] = src[ks * 2];
   };
+  // PQ: the entry numbers of the lane's row (both lanes of a row load all of them: 4 to 16 bytes), and the gather
+  uint32_t cw[CW], cn[CW];
+  auto load_words = [&](int64_t i, uint32_t* dst) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.codes) + (size_t)(p0 + i * tstep * TRS + r31) * CW;
+#pragma unroll
+    for (int c = 0; c < CW; ++c) dst[c] = src[c];
+  };
+  auto gather = [&](const uint32_t* words, i32x4* dst) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if constexpr (PQ == 8) {
+        const uint32_t two = words[ks] >> (16 * hh);   // sub-spaces 4 ks + 2 hh and + 1 are bytes 2 hh and 2 hh + 1 of word ks
+        const int m0 = 4 * ks + 2 * hh;
+        const uint2* lb = reinterpret_cast<const uint2*>(s_book);
+        const uint2 x = lb[m0 * 256 + (int)(two & 255u)];
+        const uint2 y = lb[(m0 + 1) * 256 + (int)((two >> 8) & 255u)];
+        dst[ks] = i32x4{(int)x.x, (int)x.y, (int)y.x, (int)y.y};
+      } else {
+        const uint32_t e = (words[ks >> 1] >> (8 * (2 * (ks & 1) + hh))) & 255u;   // sub-space 2 ks + hh
+        dst[ks] = s_book[(2 * ks + hh) * 256 + (int)e];
+      }
+    }
+  };
   Pred pr{0u, 0u, 0u};
   uint4 tw[4], tn[4];
   auto load_tags = [&](int64_t i, uint4* dst) {   // rows 4 hh + 8 g .. + 3 of tile i: the lane's accumulator rows 4 g .. 4 g + 3
@@ -313,12 +361,15 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     if constexpr (XM) ok = ok && !((mw >> acc_row(r, lane)) & 1u);
     return ok;
   };
-  load_tile(i0, av);
+  if constexpr (PQ != 0) load_words(i0, cw);
+  else load_tile(i0, av);
 #pragma unroll 1
   for (int64_t i = i0; i < i1; ++i) {
     const bool more = i + 1 < i1;
+    if constexpr (PQ != 0) gather(cw, av);
     if (more) {
-      load_tile(i + 1, nx);
+      if constexpr (PQ != 0) load_words(i + 1, cn);
+      else load_tile(i + 1, nx);
       if constexpr (FILT) load_tags(i + 1, tn);
       if constexpr (XM) mn = my_mask[(p0 + (i + 1) * tstep * TRS) >> 5];
     }
@@ -361,8 +412,13 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
       }
     }
     if (more) {
+      if constexpr (PQ != 0) {
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) av[ks] = nx[ks];
+        for (int c = 0; c < CW; ++c) cw[c] = cn[c];
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) av[ks] = nx[ks];
+      }
       if constexpr (FILT) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) tw[g] = tn[g];
@@ -459,6 +515,19 @@ int sq8_prepare(const Sq8Search& s, const Sq8Geom& g, int first_tile_step, uint6
   return check_launch("sq8 prepare");
 }
 
+template <int PQ>
+void sq8_launch_scan(int dpad, int fm, dim3 grid, hipStream_t st, const Sq8LmArgs& x) {
+  auto go = [&](auto FMv) {
+    constexpr int FM = decltype(FMv)::value;
+    if (dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM, PQ>), grid, dim3(256), 0, st, x);
+    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM, PQ>), grid, dim3(256), 0, st, x);
+  };
+  if (fm == FM_TAGS_MASK) go(std::integral_constant<int, FM_TAGS_MASK>{});
+  else if (fm == FM_MASK) go(std::integral_constant<int, FM_MASK>{});
+  else if (fm == FM_TAGS) go(std::integral_constant<int, FM_TAGS>{});
+  else go(std::integral_constant<int, FM_NONE>{});
+}
+
 int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* cand, int64_t cap, int tile_step,
              int64_t dense_cap, bool planned, int dense_ids) {
   Sq8Index* h = s.h;
@@ -476,24 +545,16 @@ int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* c
   // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
   const int64_t bound = (int64_t)SQ8_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
   const dim3 grid((unsigned)((bound + 3) / 4));
-  if (x.xmask && x.tags) {
-    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_TAGS_MASK>), grid, dim3(256), 0, s.st, x);
-    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_TAGS_MASK>), grid, dim3(256), 0, s.st, x);
-    return check_launch("masked filtered sq8 scan");
+  const int fm = x.xmask ? (x.tags ? FM_TAGS_MASK : FM_MASK) : (x.tags ? FM_TAGS : FM_NONE);
+  const char* what = fm == FM_TAGS_MASK ? "masked filtered sq8 scan" : fm == FM_MASK ? "masked sq8 scan" : fm == FM_TAGS ? "filtered sq8 scan" : "sq8 scan";
+  if (h->pq_codes) {   // the product-quantised source: entry numbers and the codebooks
+    x.codes = reinterpret_cast<const int8_t*>(h->pq_codes); x.pq_book = h->pq_book;
+    if (h->pq_dsub == 8) sq8_launch_scan<8>(h->dpad, fm, grid, s.st, x);
+    else sq8_launch_scan<16>(h->dpad, fm, grid, s.st, x);
+    return check_launch(what);
   }
-  if (x.xmask) {
-    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_MASK>), grid, dim3(256), 0, s.st, x);
-    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_MASK>), grid, dim3(256), 0, s.st, x);
-    return check_launch("masked sq8 scan");
-  }
-  if (x.tags) {
-    if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM_TAGS>), grid, dim3(256), 0, s.st, x);
-    else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM_TAGS>), grid, dim3(256), 0, s.st, x);
-    return check_launch("filtered sq8 scan");
-  }
-  if (h->dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64>), grid, dim3(256), 0, s.st, x);
-  else hipLaunchKernelGGL((sq8_scan_lm_kernel<128>), grid, dim3(256), 0, s.st, x);
-  return check_launch("sq8 scan");
+  sq8_launch_scan<0>(h->dpad, fm, grid, s.st, x);
+  return check_launch(what);
 }
 
 // dense emission: every (query, probed list) pair owns a slot per row of the longest list, then the two-level select
@@ -982,7 +1043,10 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
   const int dk = h->dk;
   const int nb = (int)std::min<int64_t>(1024, (n_src + 255) / 256);
   int* flag = nullptr; float* vec = nullptr; double* e = nullptr; double* a = nullptr; double* part = nullptr;
+  int8_t* decoded = nullptr;   // a PQ handle: its decoded code matrix, a transient Np * dpad bytes
   auto work = [&]() -> int {
+    if (!h->codes) RCCHK(pq_decode_all(h, &decoded, st));
+    const int8_t* codes = h->codes ? h->codes : decoded;
     HIPCHK(hipMalloc((void**)&flag, sizeof(int)));
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), st));
     hipLaunchKernelGGL(sq8_rows_differ_kernel, dim3((unsigned)((h->Np + 255) / 256)), dim3(256), 0, st, h->row_ids,
@@ -997,7 +1061,7 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
     HIPCHK(hipMalloc((void**)&part, sizeof(double) * (size_t)nb * 2 * dk));
     const int64_t nthr = n_src * (dk / 4);
     hipLaunchKernelGGL(sq8_scatter_rows_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, src->X, h->row_ids, n_src, dk, vec);
-    hipLaunchKernelGGL(sq8_refine_range_part_kernel, dim3(nb), dim3(256), 0, st, src->X, h->codes, h->row_ids, n_src, dk, h->dpad,
+    hipLaunchKernelGGL(sq8_refine_range_part_kernel, dim3(nb), dim3(256), 0, st, src->X, codes, h->row_ids, n_src, dk, h->dpad,
                        h->centre, h->scale, part);
     hipLaunchKernelGGL(sq8_refine_range_final_kernel, dim3(1), dim3(128), 0, st, part, nb, dk, e, a);
     RCCHK(check_launch("sq8 attach vectors"));
@@ -1005,7 +1069,7 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
     return RIHIP_OK;
   };
   const int rc = work();
-  hipFree(flag); hipFree(part);
+  hipFree(flag); hipFree(part); hipFree(decoded);
   if (rc) { hipFree(vec); hipFree(e); hipFree(a); return rc; }   // the handle is as it was
   drop_vectors(h);
   h->vec = vec; h->ref_e = e; h->ref_a = a;
@@ -1063,17 +1127,29 @@ int sq8_rows_out(Sq8Index* h, float* out_x, int8_t* out_c) {
   const size_t n = (size_t)h->N * h->du;
   if (out_x) HIPCHK(hipMalloc((void**)&dx, sizeof(float) * n));
   if (out_c && hipMalloc((void**)&dc, n) != hipSuccess) { hipFree(dx); rihip_set_error("sq8_index: device allocation failed"); return RIHIP_ERR_HIP; }
+  int8_t* decoded = nullptr;   // a PQ handle: its decoded code matrix, a transient Np * dpad bytes
+  if (!h->codes && pq_decode_all(h, &decoded, 0) != RIHIP_OK) { hipFree(dx); hipFree(dc); return RIHIP_ERR_HIP; }
   const int64_t tot = h->Np * h->du;
-  hipLaunchKernelGGL(sq8_reconstruct_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, h->codes, h->row_ids, h->Np, h->du,
+  hipLaunchKernelGGL(sq8_reconstruct_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, h->codes ? h->codes : decoded, h->row_ids, h->Np, h->du,
                      h->dpad, h->centre, h->scale, dx, dc);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && out_x) e = hipMemcpy(out_x, dx, sizeof(float) * n, hipMemcpyDeviceToHost);
   if (e == hipSuccess && out_c) e = hipMemcpy(out_c, dc, n, hipMemcpyDeviceToHost);
-  hipFree(dx); hipFree(dc);
+  hipFree(dx); hipFree(dc); hipFree(decoded);
   HIPCHK(e);
   return RIHIP_OK;
 }
 }  // namespace
+
+// ---- what pq.hip builds on (sq8_index.h) ------------------------------------------------------------------------------
+namespace rihip_index {
+int sq8_build_handle(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, hipStream_t st) {
+  return sq8_build(h, src, centre, scale, st);
+}
+int sq8_upload_list_layout(Sq8Index* h, hipStream_t st) { return sq8_upload_layout(h, st); }
+int64_t sq8_held_bytes(const Sq8Index* h) { return held_bytes(h); }
+void sq8_free_handle(Sq8Index* h) { free_sq8(h); }
+}  // namespace rihip_index
 
 extern "C" int rihip_sq8_index_get_codes(void* handle, int8_t* out) {
   Sq8Index* h = (Sq8Index*)handle;
@@ -1097,7 +1173,7 @@ extern "C" int rihip_sq8_index_encode_queries(void* handle, const float* Q, int6
 extern "C" int rihip_sq8_index_search(void* handle, const float* Q, int64_t nq, int k, int mode, float* out_scores, int64_t* out_rows,
                                       int32_t* out_iscores, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_index_search: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_index_search: index is empty");
   RIHIP_REQUIRE(Q && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "sq8_index_search: bad arguments");
   RIHIP_REQUIRE(k >= 1 && k <= K_MAX, RIHIP_ERR_ARG, "sq8_index_search: k=%d outside [1,%d]", k, K_MAX);
   RIHIP_REQUIRE(mode >= 0 && mode <= 2, RIHIP_ERR_ARG, "sq8_index_search: mode=%d (0 auto, 1 dense, 2 thresholded)", mode);
@@ -1107,7 +1183,7 @@ extern "C" int rihip_sq8_index_search(void* handle, const float* Q, int64_t nq, 
 // ---- filtered search: per-query tag predicates inside the int8 scan ---------------------------------------------------
 extern "C" int rihip_sq8_filter_set_tags(void* handle, const uint32_t* tags_by_row_dev, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_set_tags: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_set_tags: index is empty");
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(st));   // (searches in flight still read the old copy)
   drop_tags(h);
@@ -1136,7 +1212,7 @@ extern "C" int rihip_sq8_filter_search(void* handle, const float* Q, int64_t nq,
                                        int64_t pred_stride, float* out_scores, int64_t* out_rows, int32_t* out_iscores,
                                        void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_search: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_filter_search: index is empty");
   RIHIP_REQUIRE(h->tags, RIHIP_ERR_STATE, "sq8_filter_search: the index has no tags (rihip_sq8_filter_set_tags)");
   RIHIP_REQUIRE(Q && pred_dev && out_scores && out_rows && nq > 0, RIHIP_ERR_ARG, "sq8_filter_search: bad arguments");
   RIHIP_REQUIRE(pred_stride == 0 || pred_stride == 3, RIHIP_ERR_ARG, "sq8_filter_search: pred_stride=%lld (0 or 3)", (long long)pred_stride);
@@ -1149,7 +1225,7 @@ extern "C" int rihip_sq8_refine_search_filtered(void* handle, const float* Q, in
                                                 const uint32_t* pred_dev, int64_t pred_stride, float* out_scores, int64_t* out_rows,
                                                 uint8_t* out_cert, double* out_bound, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_search_filtered: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_search_filtered: index is empty");
   RIHIP_REQUIRE(h->vec, RIHIP_ERR_STATE, "sq8_refine_search_filtered: no vectors attached (rihip_sq8_refine_attach_vectors)");
   RIHIP_REQUIRE(h->tags, RIHIP_ERR_STATE, "sq8_refine_search_filtered: the index has no tags (rihip_sq8_filter_set_tags)");
   RIHIP_REQUIRE(Q && pred_dev && out_scores && out_rows && out_cert && nq > 0, RIHIP_ERR_ARG, "sq8_refine_search_filtered: bad arguments");
@@ -1166,7 +1242,7 @@ namespace {
 int sq8_check_excluding(const char* who, Sq8Index* h, const float* Q, int64_t nq, const int64_t* seen_offsets, int64_t n_seen_rows,
                         const int32_t* seen_items, const int32_t* row_of, int64_t n_ids, const uint32_t* pred_dev,
                         int64_t pred_stride, int mode) {
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "%s: index is empty", who);
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "%s: index is empty", who);
   RIHIP_REQUIRE(!pred_dev || h->tags, RIHIP_ERR_STATE, "%s: the index has no tags (rihip_sq8_filter_set_tags)", who);
   RIHIP_REQUIRE(Q && nq > 0, RIHIP_ERR_ARG, "%s: bad arguments", who);
   RIHIP_REQUIRE(seen_offsets && seen_items && n_seen_rows >= 0, RIHIP_ERR_ARG, "%s: bad seen lists", who);
@@ -1209,7 +1285,7 @@ extern "C" int rihip_sq8_refine_search_excluding(void* handle, const float* Q, i
 
 extern "C" int rihip_sq8_exclude_mask_words(void* handle, int64_t* words_per_query) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0 && words_per_query, RIHIP_ERR_STATE, "sq8_exclude_mask_words: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0 && words_per_query, RIHIP_ERR_STATE, "sq8_exclude_mask_words: index is empty");
   *words_per_query = (h->Np + 31) / 32;
   return RIHIP_OK;
 }
@@ -1218,7 +1294,7 @@ extern "C" int rihip_sq8_exclude_mask(void* handle, int64_t nq, const int64_t* u
                                       int64_t n_seen_rows, const int32_t* seen_items, const int32_t* row_of, int64_t n_ids,
                                       uint32_t* out_mask, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_exclude_mask: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_exclude_mask: index is empty");
   RIHIP_REQUIRE(nq > 0 && seen_offsets && seen_items && n_seen_rows >= 0 && row_of && n_ids > 0 && out_mask, RIHIP_ERR_ARG,
                 "sq8_exclude_mask: bad arguments");
   hipStream_t st = (hipStream_t)stream;
@@ -1270,7 +1346,7 @@ extern "C" int rihip_sq8_refine_attach_vectors(void* handle, void* ip_handle, vo
   Sq8Index* h = (Sq8Index*)handle;
   const IpIndex* src = (const IpIndex*)ip_handle;
   RIHIP_REQUIRE(h && src, RIHIP_ERR_ARG, "sq8_refine_attach_vectors: null handle");
-  RIHIP_REQUIRE(h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_attach_vectors: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_attach_vectors: index is empty");
   RIHIP_REQUIRE(src->X && src->N > 0, RIHIP_ERR_STATE, "sq8_refine_attach_vectors: the source index is empty");
   return sq8_attach(h, src, (hipStream_t)stream);
 }
@@ -1297,7 +1373,7 @@ extern "C" int rihip_sq8_refine_get_ranges(void* handle, double* e, double* a) {
 extern "C" int rihip_sq8_refine_search(void* handle, const float* Q, int64_t nq, int k, int k_scan, int mode, float* out_scores,
                                               int64_t* out_rows, uint8_t* out_cert, double* out_bound, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_search: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_refine_search: index is empty");
   RIHIP_REQUIRE(h->vec, RIHIP_ERR_STATE, "sq8_refine_search: no vectors attached (rihip_sq8_refine_attach_vectors)");
   RIHIP_REQUIRE(Q && out_scores && out_rows && out_cert && nq > 0, RIHIP_ERR_ARG, "sq8_refine_search: bad arguments");
   RIHIP_REQUIRE(k >= 1 && k <= k_scan && k_scan <= K_MAX, RIHIP_ERR_ARG, "sq8_refine_search: k=%d, k_scan=%d (1 <= k <= k_scan <= %d)",
@@ -1318,6 +1394,8 @@ extern "C" int rihip_sq8_index_stats(void* handle, int64_t* out) {
 extern "C" int rihip_sq8_index_save(void* handle, const char* path) {
   Sq8Index* h = (Sq8Index*)handle;
   RIHIP_REQUIRE(h && path, RIHIP_ERR_ARG, "sq8_index_save: bad arguments");
+  RIHIP_REQUIRE(!h->pq_codes, RIHIP_ERR_STATE, "sq8_index_save: a PQ index has a file format of its own (rihip_pq_index_save)");
+  RIHIP_REQUIRE(h->codes, RIHIP_ERR_STATE, "sq8_index_save: index is empty");
   std::vector<float> m(h->dpad), s(h->dpad), C((size_t)h->nlist * h->dk);
   std::vector<int64_t> rid((size_t)h->Np);
   std::vector<int8_t> codes((size_t)h->Np * h->dpad);

@@ -1,6 +1,7 @@
-// Handle of the 8-bit scalar-quantised index, shared by sq8.hip (build, search, refine, filter, state I/O) and
-// sq8_update.hip (add / remove / replace), and the one function that makes a code.  Both files compile with
-// `#pragma clang fp contract(off)` at their top: the quantiser is specified operation by operation.
+// Handle of the 8-bit scalar-quantised index, shared by sq8.hip (build, search, refine, filter, state I/O),
+// sq8_update.hip (add / remove / replace) and pq.hip (the product-quantised storage of the same handle: training,
+// encoding, decoding, state I/O), and the one function that makes a code.  All three compile with
+// `#pragma clang fp contract(off)` at their top: the quantisers are specified operation by operation.
 #pragma once
 #include "common.h"
 #include "ip_index.h"
@@ -15,8 +16,15 @@ struct Sq8Index {
   int dpad = 0;      // bytes per code row: 64 / 128
   int64_t N = 0, Np = 0;
   int nlist = 0, nprobe = 1;
-  int8_t* codes = nullptr;        // [Np, dpad] physical order, padding rows and columns 0
-  float* centre = nullptr;        // [dpad] (columns >= du: 0)
+  int8_t* codes = nullptr;        // [Np, dpad] physical order, padding rows and columns 0 (null on a PQ handle)
+  // product-quantised storage (pq.hip) in place of `codes`: the row's SQ8 code is book[m][pq_codes[p][m]][:] per sub-space
+  uint8_t* pq_codes = nullptr;    // [Np, M] physical order, M = dpad / pq_dsub; padding rows 0
+  int8_t* pq_book = nullptr;      // [M, 256, pq_dsub], entries in [-127, 127]
+  int pq_dsub = 0;                // 8 / 16 (0: an SQ8 handle)
+  std::vector<int64_t> pq_trace;  // distortion of every assignment pass of the build (empty: injected codebooks, loaded)
+  int64_t pq_peak_bytes = 0;      // device bytes at the build's peak (the transient SQ8 codes included)
+  double pq_ms[3] = {0, 0, 0};    // host time of the build: range pass + SQ8 encode, codebook training, final assignment
+  float* centre = nullptr;       // [dpad] (columns >= du: 0)
   float* scale = nullptr;         // [dpad] (columns >= du: 1)
   float* C = nullptr;             // [nlist, dk]
   int64_t* list_poff = nullptr;   // [nlist+1]
@@ -55,6 +63,18 @@ struct Sq8Index {
   DevBuf<int> count, probe_list, list_q, list_cnt, list_qoff, list_cur, work_off, plan, fail_flags, fail_list, n_fail;
   int* h_nfail = nullptr;   // pinned
 };
+
+inline bool sq8_has_storage(const Sq8Index* h) { return h && (h->codes || h->pq_codes); }
+
+// what pq.hip needs of sq8.hip: the SQ8 build (layout, row ids, quantiser, codes), the layout upload, the bytes a handle
+// holds and its destructor
+int sq8_build_handle(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, hipStream_t st);
+int sq8_upload_list_layout(Sq8Index* h, hipStream_t st);
+int64_t sq8_held_bytes(const Sq8Index* h);
+void sq8_free_handle(Sq8Index* h);
+// and what sq8.hip needs of pq.hip: the decoded code matrix [Np, dpad] of a PQ handle in a fresh device allocation the
+// caller frees (a transient Np * dpad bytes)
+int pq_decode_all(const Sq8Index* h, int8_t** out_dev, hipStream_t st);
 
 __device__ __forceinline__ int sq8_code(float x, float m, float s) {
   float v = rintf((x - m) / s);            // one f32 subtraction, one correctly rounded f32 division, round to nearest even

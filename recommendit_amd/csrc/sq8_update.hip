@@ -206,6 +206,8 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
                                       int64_t* item_ids_out, int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped,
                                       int64_t* bad_id, int* bad_kind, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(!h || !h->pq_codes, RIHIP_ERR_STATE,
+                "sq8_update_apply: a PQ index is not updated in place (its codebooks are trained on the corpus): rebuild it");
   RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_update_apply: index is empty");
   RIHIP_REQUIRE(item_ids && item_ids_out && n_total && n_dropped && n_clamped && bad_id && bad_kind && n_drop >= 0 && n_add >= 0 &&
                 (n_drop == 0 || drop_ids) && (n_add == 0 || (X_add && add_ids)), RIHIP_ERR_ARG, "sq8_update_apply: bad arguments");
@@ -372,7 +374,7 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
 
 extern "C" int rihip_sq8_update_assign(void* handle, const float* X, int64_t n, int32_t* assign_out, void* stream) {
   Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_update_assign: index is empty");
+  RIHIP_REQUIRE(sq8_has_storage(h) && h->N > 0, RIHIP_ERR_STATE, "sq8_update_assign: index is empty");
   RIHIP_REQUIRE(X && assign_out && n > 0, RIHIP_ERR_ARG, "sq8_update_assign: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (h->nlist == 1) {   // a flat-built handle: its one list

@@ -1,0 +1,142 @@
+"""PQIndex: a product-quantised inner-product index (flat and IVF) next to SQ8Index (not in the reference; faiss has it
+as IndexPQ / IndexIVFPQ).
+
+A row takes ``dpad / dsub`` bytes (d = 128: 16 bytes at ``dsub=8``, 8 at ``dsub=16``) instead of SQ8's 128: one byte per
+sub-space of ``dsub`` dimensions, naming one of 256 int8 codebook entries.  The quantiser works on the rows' SQ8 codes in
+integers only and is specified at ``rihip_pq_index_*`` in recommendit_hip.h; the scan is SQ8's, gathering its operand
+bytes from the codebooks in LDS.  A PQIndex is therefore the SQ8Index of its own reconstruction: every search of
+SQ8Index -- ``mode=``, ``item_filter=``, ``exclude=`` on both ``exclusion=`` routes, ``refine=`` / ``return_cert=`` /
+``search_certified``, serving through GpuRecommendationPipeline -- returns what that SQ8Index would return, integer
+scores included, and ``codes()`` / ``reconstruct()`` return the decoded matrix those scores are stated over.
+
+Deviations from faiss: an own quantiser over SQ8 codes with int8 codebooks, no residual encoding
+against the IVF centroids (one integer score per row, comparable across lists), no faiss PQ file interop.
+
+``codes()``, ``reconstruct()`` and ``attach_vectors()`` decode the whole index on the device: a transient
+N * dpad bytes.  ``save`` / ``load`` are SQ8Index's on the PQ file format (``_SAVE`` / ``_LOAD``); each loader refuses the
+other's file.  A PQ index is not updated in place (its codebooks are trained on the corpus): ``add_items``,
+``remove_items`` and ``update_items`` raise NotImplementedError -- rebuild with ``from_index``.
+
+There is no NumPy or torch path for training, encoding or search: everything runs in csrc/pq.hip and csrc/sq8.hip.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+
+from . import _lib as L
+from .faiss_index import FAISSIndex
+from .sq8_index import SQ8Index, _check_ranges, _check_source
+
+_REBUILD = "a PQIndex is not updated in place (its codebooks are trained on the corpus): rebuild it with PQIndex.from_index"
+
+
+class PQIndex(SQ8Index):
+    _KIND = "PQ"
+    _SAVE, _LOAD = "rihip_pq_index_save", "rihip_pq_index_load"    # save() / load(): SQ8Index's, on the PQ file format
+
+    # -- build ----------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_index(cls, faiss_index: FAISSIndex, dsub: int = 8, n_iter: int = 10,
+                   ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None, codebooks: Optional[np.ndarray] = None,
+                   keep_vectors: bool = False) -> "PQIndex":
+        """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  dsub: 8 or 16
+        dimensions per sub-space; n_iter: Lloyd steps of the codebook training; ranges: (centre, scale) of the SQ8 stage,
+        as SQ8Index.from_index; codebooks: int8 [M, 256, dsub] with M = dpad / dsub (dpad = 64 up to 64 dimensions, else
+        128), entries in [-127, 127] -- injected codebooks skip the training, as ranges= skips the range pass.
+        keep_vectors / item tags: as SQ8Index.from_index."""
+        _check_source("PQIndex", faiss_index)
+        if dsub not in (8, 16):
+            raise ValueError(f"PQIndex: dsub={dsub!r} (8 or 16)")
+        if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= int(n_iter) <= 1000:
+            raise ValueError(f"PQIndex: n_iter={n_iter!r} outside 0..1000")
+        d = faiss_index.embed_dim
+        dpad = 64 if d <= 64 else 128
+        m, s = _check_ranges("PQIndex", ranges, d)
+        book = None
+        if codebooks is not None:
+            book = np.asarray(codebooks)
+            if book.dtype != np.int8 or book.shape != (dpad // dsub, 256, dsub):
+                raise ValueError(f"PQIndex: codebooks must be int8 [{dpad // dsub}, 256, {dsub}], got {book.dtype} {book.shape}")
+            if (book == -128).any():
+                raise ValueError("PQIndex: codebook entries lie in [-127, 127]")
+            book = np.ascontiguousarray(book)
+        h = C.c_void_p()
+        L.check(L.lib().rihip_pq_index_from_ip_index(faiss_index.index._h, None if m is None else m.ctypes.data,
+                                                     None if s is None else s.ctypes.data, int(dsub), int(n_iter),
+                                                     None if book is None else book.ctypes.data, C.byref(h), L.stream_ptr()),
+                "pq_index_from_ip_index")
+        return cls._adopt(h.value, faiss_index, keep_vectors)
+
+    # -- no live updates ------------------------------------------------------------------------------------------
+    def add_items(self, embeddings, item_ids, tags=None):
+        raise NotImplementedError(_REBUILD)
+
+    def add_items_device(self, x_dev, item_ids, tags=None):
+        raise NotImplementedError(_REBUILD)
+
+    def remove_items(self, item_ids):
+        raise NotImplementedError(_REBUILD)
+
+    def update_items(self, embeddings, item_ids, tags=None):
+        raise NotImplementedError(_REBUILD)
+
+    # -- trained state ----------------------------------------------------------------------------------------------
+    def _dims(self) -> Tuple[int, int]:
+        dsub, m = C.c_int(0), C.c_int(0)
+        L.check(L.lib().rihip_pq_index_dims(self._built()._h, C.byref(dsub), C.byref(m)), "pq_index_dims")
+        return int(dsub.value), int(m.value)
+
+    @property
+    def dsub(self) -> int:
+        return self._dims()[0]
+
+    def pq_codes(self) -> np.ndarray:
+        """uint8 [N, M]: the stored entry numbers in insertion order"""
+        h = self._built()
+        out = np.empty((h.ntotal, self._dims()[1]), dtype=np.uint8)
+        L.check(L.lib().rihip_pq_index_get_codes(h._h, out.ctypes.data), "pq_index_get_codes")
+        return out
+
+    def codebooks(self) -> np.ndarray:
+        """int8 [M, 256, dsub]"""
+        h = self._built()
+        dsub, m = self._dims()
+        out = np.empty((m, 256, dsub), dtype=np.int8)
+        L.check(L.lib().rihip_pq_index_get_codebooks(h._h, out.ctypes.data), "pq_index_get_codebooks")
+        return out
+
+    def train_stats(self) -> Dict:
+        """distortion: int64 [passes], the summed smallest distance of every assignment pass of the build (n_iter + 1
+        values; one with injected codebooks; none after load); peak_bytes: device bytes at the build's peak, the
+        transient SQ8 codes included; *_ms: host time of the build's stages"""
+        h = self._built()
+        n = C.c_int(0)
+        peak = L.c_i64(0)
+        ms = (C.c_double * 3)()
+        trace = (L.c_i64 * 1001)()
+        L.check(L.lib().rihip_pq_index_train_stats(h._h, trace, 1001, C.byref(n), C.byref(peak), ms), "pq_index_train_stats")
+        return {"distortion": np.array(trace[:n.value], dtype=np.int64), "peak_bytes": int(peak.value),
+                "range_encode_ms": float(ms[0]), "train_ms": float(ms[1]), "assign_ms": float(ms[2])}
+
+    def codes(self) -> np.ndarray:
+        """int8 [N, embed_dim]: the DECODED codes (codebook entries) in insertion order -- the matrix the search contract
+        is stated over.  Decodes the whole index on the device: a transient N * dpad bytes."""
+        return super().codes()
+
+    def reconstruct(self) -> np.ndarray:
+        """f32 [N, embed_dim]: centre + scale * decoded code in insertion order (a transient N * dpad bytes on the device)"""
+        return super().reconstruct()
+
+    # -- utilities --------------------------------------------------------------------------------------------------
+    def stats(self) -> Dict:
+        st = super().stats()
+        if self.index is None:
+            return st
+        dsub, m = self._dims()
+        f32_row = 4 * (32 if self.embed_dim <= 32 else (64 if self.embed_dim <= 64 else 128))
+        st.update({"bytes_per_vector": m, "compression": f32_row / m, "dsub": dsub, "n_subspaces": m,
+                   "codebook_bytes": m * 256 * dsub, "peak_build_bytes": self.train_stats()["peak_bytes"]})
+        return st

@@ -118,7 +118,34 @@ def _tag_words(tags, n: int) -> np.ndarray:
     return a
 
 
+def _check_source(cls_name: str, faiss_index) -> None:
+    """what from_index asks of its source"""
+    if not isinstance(faiss_index, FAISSIndex):
+        raise ValueError(f"{cls_name}.from_index needs a FAISSIndex, got {type(faiss_index).__name__}")
+    if faiss_index.index is None:
+        raise RuntimeError("Index not built.")
+    if faiss_index.search_pending():
+        raise RuntimeError("a deferred search is pending: call finish_search() before encoding the index")
+
+
+def _check_ranges(cls_name: str, ranges, d: int):
+    """ranges= as given -> (centre, scale) f32 [d] contiguous, or (None, None)"""
+    if ranges is None:
+        return None, None
+    if len(ranges) != 2:
+        raise ValueError(f"{cls_name}: ranges must be (centre, scale)")
+    m = np.ascontiguousarray(ranges[0], dtype=np.float32)
+    s = np.ascontiguousarray(ranges[1], dtype=np.float32)
+    if m.shape != (d,) or s.shape != (d,):
+        raise ValueError(f"{cls_name}: ranges must be two [{d}] arrays, got {m.shape} and {s.shape}")
+    if not (np.isfinite(m).all() and np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError(f"{cls_name}: ranges must be finite with scale > 0")
+    return m, s
+
+
 class SQ8Index(ExcludingSearch):
+    _KIND = "SQ8"                                  # in messages; PQIndex: "PQ"
+    _SAVE, _LOAD = "rihip_sq8_index_save", "rihip_sq8_index_load"
     _EXCL_ABI = {"mask_words": "rihip_sq8_exclude_mask_words", "mask": "rihip_sq8_exclude_mask",
                  "budget": "rihip_sq8_exclude_set_exclusion_budget", "nonzero": "rihip_sq8_exclude_scratch_nonzero",
                  "stats": "rihip_sq8_exclude_exclusion_stats"}
@@ -163,35 +190,26 @@ class SQ8Index(ExcludingSearch):
         scale), two f32 [embed_dim] arrays that replace the trained per-dimension quantiser; scale > 0.
         keep_vectors=True also copies the f32 vectors (attach_vectors), which a refined search needs.  A source with item
         tags hands them on (set_item_tags); one without leaves the new index untagged."""
-        if not isinstance(faiss_index, FAISSIndex):
-            raise ValueError(f"SQ8Index.from_index needs a FAISSIndex, got {type(faiss_index).__name__}")
-        if faiss_index.index is None:
-            raise RuntimeError("Index not built.")
-        if faiss_index.search_pending():
-            raise RuntimeError("a deferred search is pending: call finish_search() before encoding the index")
-        d = faiss_index.embed_dim
-        m = s = None
-        if ranges is not None:
-            if len(ranges) != 2:
-                raise ValueError("SQ8Index: ranges must be (centre, scale)")
-            m = np.ascontiguousarray(ranges[0], dtype=np.float32)
-            s = np.ascontiguousarray(ranges[1], dtype=np.float32)
-            if m.shape != (d,) or s.shape != (d,):
-                raise ValueError(f"SQ8Index: ranges must be two [{d}] arrays, got {m.shape} and {s.shape}")
-            if not (np.isfinite(m).all() and np.isfinite(s).all() and (s > 0).all()):
-                raise ValueError("SQ8Index: ranges must be finite with scale > 0")
-        ivf = bool(faiss_index.index.is_ivf)
-        # a flat source becomes one list probed once: that is what the handle holds and what load() must hand back to it
-        obj = cls(embed_dim=d, n_lists=faiss_index.n_lists, n_probe=faiss_index.n_probe if ivf else 1, exact=not ivf)
+        _check_source("SQ8Index", faiss_index)
+        m, s = _check_ranges("SQ8Index", ranges, faiss_index.embed_dim)
         h = C.c_void_p()
         L.check(L.lib().rihip_sq8_index_from_ip_index(faiss_index.index._h, None if m is None else m.ctypes.data,
                                                       None if s is None else s.ctypes.data, C.byref(h), L.stream_ptr()),
                 "sq8_index_from_ip_index")
-        obj.index = _SQ8Handle(h.value, obj)
+        return cls._adopt(h.value, faiss_index, keep_vectors)
+
+    @classmethod
+    def _adopt(cls, handle: int, faiss_index: FAISSIndex, keep_vectors: bool):
+        """the wrapper around a handle just built from faiss_index: its ids, and on request its vectors and tags"""
+        ivf = bool(faiss_index.index.is_ivf)
+        # a flat source becomes one list probed once: that is what the handle holds and what load() must hand back to it
+        obj = cls(embed_dim=faiss_index.embed_dim, n_lists=faiss_index.n_lists, n_probe=faiss_index.n_probe if ivf else 1,
+                  exact=not ivf)
+        obj.index = _SQ8Handle(handle, obj)
         obj.item_ids = np.array(faiss_index.item_ids, dtype=np.int64)
         obj._item_ids_dev = torch.from_numpy(obj.item_ids).to(L.device())
         obj._item_id_to_faiss_idx = dict(faiss_index._item_id_to_faiss_idx)
-        logger.info("SQ8 index built: %d vectors, %d lists, probe=%d", obj.index.ntotal, obj.index.nlist, obj.n_probe)
+        logger.info("%s index built: %d vectors, %d lists, probe=%d", cls._KIND, obj.index.ntotal, obj.index.nlist, obj.n_probe)
         if keep_vectors:
             obj.attach_vectors(faiss_index)
         if faiss_index._tags is not None:
@@ -738,7 +756,7 @@ class SQ8Index(ExcludingSearch):
         h = self._built()
         save_path = Path(path)
         save_path.parent.mkdir(parents=True, exist_ok=True)
-        L.check(L.lib().rihip_sq8_index_save(h._h, str(save_path).encode()), "sq8_index_save")
+        L.check(getattr(L.lib(), self._SAVE)(h._h, str(save_path).encode()), self._SAVE[6:])
         meta = {
             "item_ids": self.item_ids,
             "item_id_to_faiss_idx": self._item_id_to_faiss_idx,
@@ -748,18 +766,18 @@ class SQ8Index(ExcludingSearch):
         }
         with open(save_path.with_suffix(".meta.pkl"), "wb") as f:
             pickle.dump(meta, f)
-        logger.info("Saved SQ8 index to %s", save_path)
+        logger.info("Saved %s index to %s", self._KIND, save_path)
 
     @classmethod
     def load(cls, path: str) -> "SQ8Index":
         load_path = Path(path)
         if not load_path.exists():
-            raise FileNotFoundError(f"SQ8 index not found at {load_path}")
+            raise FileNotFoundError(f"{cls._KIND} index not found at {load_path}")
         with open(load_path.with_suffix(".meta.pkl"), "rb") as f:
             meta = pickle.load(f)  # sidecar written by save() above
         obj = cls(embed_dim=meta["embed_dim"], n_lists=meta["n_lists"], n_probe=meta["n_probe"])
         h = C.c_void_p()
-        L.check(L.lib().rihip_sq8_index_load(str(load_path).encode(), C.byref(h)), "sq8_index_load")
+        L.check(getattr(L.lib(), cls._LOAD)(str(load_path).encode(), C.byref(h)), cls._LOAD[6:])
         obj.index = _SQ8Handle(h.value, obj)
         obj.index.nprobe = meta["n_probe"]
         obj.item_ids = np.asarray(meta["item_ids"], dtype=np.int64)
