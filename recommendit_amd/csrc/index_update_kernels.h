@@ -1,4 +1,4 @@
-// The id side of an index update, shared by index_update.hip (f32 index) and sq8.hip (8-bit index): sorted drop / add
+// The id side of an index update, shared by index_update.hip (f32 index) and sq8_update.hip (8-bit index): sorted drop / add
 // ids, keep flags of the stored rows in insertion and in physical order, the id checks, the kept rows per list and the
 // ids of the result.  What is moved (f32 rows or int8 codes) is each file's own repack kernel.  Everything here has
 // internal linkage: each file that includes it compiles its own copy.

@@ -2,7 +2,7 @@
 //
 // A PQ index is an Sq8Index handle whose code storage is one byte per sub-space and row (pq_codes) plus int8 codebooks
 // (pq_book) in place of the int8 matrix: the row's SQ8 code is, per sub-space, the codebook entry its byte names.  The
-// search is sq8.hip's, whose scan gathers the operand bytes from the codebooks in LDS (sq8_scan_lm_kernel<DP, FM, PQ>);
+// search is sq8.hip's, whose scan (sq8_scan.hip, sq8_scan_lm_kernel<DP, FM, PQ>) gathers the operand bytes from the codebooks in LDS;
 // nothing else of the search knows the difference, so a PQ index is the SQ8 index of its own reconstruction.
 //
 // The quantiser works on the rows' SQ8 codes c (int8, padding columns 0), in integers only (recommendit_hip.h at
@@ -187,7 +187,7 @@ struct PqTimes { double sq8 = 0, train = 0, encode = 0; };
 int pq_build(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, int dsub, int n_iter, const int8_t* book_host,
              PqTimes* tm, hipStream_t st) {
   auto t0 = std::chrono::steady_clock::now();
-  RCCHK(sq8_build_handle(h, src, centre, scale, st));   // (synchronises)
+  RCCHK(sq8_build(h, src, centre, scale, st));   // (synchronises)
   tm->sq8 = ms_since(t0);
   const int M = h->dpad / dsub;
   const size_t book_bytes = (size_t)h->dpad * 256;
@@ -277,7 +277,7 @@ extern "C" int rihip_pq_index_from_ip_index(void* ip_handle, const float* centre
   Sq8Index* h = new Sq8Index();
   PqTimes tm;
   const int rc = pq_build(h, src, centre, scale, dsub, n_iter, book, &tm, (hipStream_t)stream);
-  if (rc) { sq8_free_handle(h); return rc; }
+  if (rc) { sq8_free(h); return rc; }
   h->pq_ms[0] = tm.sq8; h->pq_ms[1] = tm.train; h->pq_ms[2] = tm.encode;
   *handle = h;
   return RIHIP_OK;
@@ -325,105 +325,40 @@ extern "C" int rihip_pq_index_train_stats(void* handle, int64_t* trace, int cap,
 
 // File: "RIHIPPQ1", int64 header {version 1, du, dk, dpad, N, Np, nlist, nprobe, dsub, M}, centre f32[dpad], scale
 // f32[dpad], centroids f32[nlist, dk], list lengths int64[nlist], row ids int64[Np], codebooks int8[M, 256, dsub],
-// entry numbers uint8[Np, M]
+// entry numbers uint8[Np, M].  The codec is sq8_state.hip's; the format adds its two header words and its payload.
+namespace {
+
+int pq_fill(Sq8Index* h, const int64_t* x, const int8_t* payload, const char* path) {
+  const size_t book_bytes = (size_t)h->dpad * 256, code_bytes = (size_t)h->Np * x[1];
+  for (size_t i = 0; i < book_bytes; ++i)
+    RIHIP_REQUIRE(payload[i] != -128, RIHIP_ERR_IO, "pq_index_load: %s: codebook byte %lld is -128", path, (long long)i);
+  h->pq_dsub = (int)x[0];
+  HIPCHK(hipMalloc((void**)&h->pq_codes, code_bytes));
+  HIPCHK(hipMalloc((void**)&h->pq_book, book_bytes));
+  HIPCHK(hipMemcpy(h->pq_codes, payload + book_bytes, code_bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->pq_book, payload, book_bytes, hipMemcpyHostToDevice));
+  h->pq_peak_bytes = sq8_held_bytes(h);
+  return RIHIP_OK;
+}
+
+const Sq8StateFormat PQ_FORMAT = {
+    "RIHIPPQ1", "pq_index", "a PQ", 2,
+    [](const int64_t* x, int64_t dpad) { return (x[0] == 8 || x[0] == 16) && x[1] * x[0] == dpad; },
+    [](const int64_t* x, int64_t Np, int64_t dpad) { return 256 * dpad + Np * x[1]; },
+    pq_fill,
+};
+
+}  // namespace
+
 extern "C" int rihip_pq_index_save(void* handle, const char* path) {
   Sq8Index* h = (Sq8Index*)handle;
   RIHIP_REQUIRE(h && path, RIHIP_ERR_ARG, "pq_index_save: bad arguments");
   RIHIP_REQUIRE(h->pq_codes, RIHIP_ERR_STATE, "pq_index_save: not a PQ index (an SQ8 index is saved by rihip_sq8_index_save)");
-  const int M = h->dpad / h->pq_dsub;
-  std::vector<float> m(h->dpad), s(h->dpad), C((size_t)h->nlist * h->dk);
-  std::vector<int64_t> rid((size_t)h->Np);
-  std::vector<int8_t> book((size_t)h->dpad * 256);
-  std::vector<uint8_t> codes((size_t)h->Np * M);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(m.data(), h->centre, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(s.data(), h->scale, sizeof(float) * s.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(C.data(), h->C, sizeof(float) * C.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rid.data(), h->row_ids, sizeof(int64_t) * rid.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(book.data(), h->pq_book, book.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(codes.data(), h->pq_codes, codes.size(), hipMemcpyDeviceToHost));
-  FILE* f = fopen(path, "wb");
-  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "pq_index_save: cannot open %s", path);
-  const int64_t hdr[10] = {1, h->du, h->dk, h->dpad, h->N, h->Np, h->nlist, h->nprobe, h->pq_dsub, M};
-  bool ok = fwrite("RIHIPPQ1", 1, 8, f) == 8 && fwrite(hdr, sizeof(int64_t), 10, f) == 10 &&
-            fwrite(m.data(), sizeof(float), m.size(), f) == m.size() && fwrite(s.data(), sizeof(float), s.size(), f) == s.size() &&
-            fwrite(C.data(), sizeof(float), C.size(), f) == C.size() &&
-            fwrite(h->list_len.data(), sizeof(int64_t), h->nlist, f) == (size_t)h->nlist &&
-            fwrite(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fwrite(book.data(), 1, book.size(), f) == book.size() &&
-            fwrite(codes.data(), 1, codes.size(), f) == codes.size();
-  ok = (fclose(f) == 0) && ok;
-  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "pq_index_save: short write to %s", path);
-  return RIHIP_OK;
+  const int64_t M = h->dpad / h->pq_dsub;
+  const int64_t x[2] = {h->pq_dsub, M};
+  const Sq8StateBlock blocks[2] = {{h->pq_book, (size_t)h->dpad * 256}, {h->pq_codes, (size_t)h->Np * M}};
+  return sq8_state_save(h, path, PQ_FORMAT, x, blocks, 2);
 }
 
-extern "C" int rihip_pq_index_load(const char* path, void** handle) {
-  RIHIP_REQUIRE(path && handle, RIHIP_ERR_ARG, "pq_index_load: bad arguments");
-  FILE* f = fopen(path, "rb");
-  RIHIP_REQUIRE(f, RIHIP_ERR_IO, "pq_index_load: cannot open %s", path);
-  char magic[8]; int64_t hdr[10];
-  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "RIHIPPQ1", 8) != 0 || fread(hdr, sizeof(int64_t), 10, f) != 10 || hdr[0] != 1) {
-    fclose(f); rihip_set_error("pq_index_load: %s is not a PQ index file (magic / version)", path); return RIHIP_ERR_IO;
-  }
-  const int64_t du = hdr[1], dk = hdr[2], dpad = hdr[3], N = hdr[4], Np = hdr[5], nlist = hdr[6], nprobe = hdr[7], dsub = hdr[8], M = hdr[9];
-  const bool hdr_ok = du >= 1 && du <= 128 && dk == (du <= 32 ? 32 : (du <= 64 ? 64 : 128)) && dpad == (dk <= 64 ? 64 : 128) &&
-                      N >= 1 && N < (1ll << 31) && nlist >= 1 && nlist <= NLIST_MAX && nprobe >= 1 && nprobe < (1ll << 31) &&
-                      Np >= N && Np % TR == 0 && Np <= N + (int64_t)TR * nlist && (dsub == 8 || dsub == 16) && M * dsub == dpad;
-  int64_t expect = 0, have = -1;
-  if (hdr_ok) {
-    expect = 8 + 80 + 8 * dpad + 4 * nlist * dk + 8 * nlist + 8 * Np + 256 * dpad + Np * M;
-    if (fseek(f, 0, SEEK_END) == 0) have = (int64_t)ftell(f);
-    if (fseek(f, 88, SEEK_SET) != 0) have = -1;
-  }
-  if (!hdr_ok || have != expect) {
-    fclose(f);
-    rihip_set_error("pq_index_load: %s: %s", path, hdr_ok ? "file size does not match its header (truncated?)" : "header field out of range");
-    return RIHIP_ERR_IO;
-  }
-  std::vector<float> m(dpad), s(dpad), C((size_t)nlist * dk);
-  std::vector<int64_t> ll(nlist), rid((size_t)Np);
-  std::vector<int8_t> book((size_t)dpad * 256);
-  std::vector<uint8_t> codes((size_t)Np * M);
-  bool ok = fread(m.data(), sizeof(float), m.size(), f) == m.size() && fread(s.data(), sizeof(float), s.size(), f) == s.size() &&
-            fread(C.data(), sizeof(float), C.size(), f) == C.size() && fread(ll.data(), sizeof(int64_t), nlist, f) == (size_t)nlist &&
-            fread(rid.data(), sizeof(int64_t), rid.size(), f) == rid.size() && fread(book.data(), 1, book.size(), f) == book.size() &&
-            fread(codes.data(), 1, codes.size(), f) == codes.size();
-  fclose(f);
-  RIHIP_REQUIRE(ok, RIHIP_ERR_IO, "pq_index_load: short read from %s", path);
-  int64_t tot = 0, ptot = 0;
-  for (int64_t c = 0; c < nlist; ++c) {
-    RIHIP_REQUIRE(ll[c] >= 0 && ll[c] <= N, RIHIP_ERR_IO, "pq_index_load: %s: list %lld has length %lld", path, (long long)c, (long long)ll[c]);
-    tot += ll[c]; ptot += (ll[c] + TR - 1) / TR * TR;
-  }
-  RIHIP_REQUIRE(tot == N && ptot == Np, RIHIP_ERR_IO, "pq_index_load: %s: list lengths do not add up to the header's row counts", path);
-  for (int64_t p = 0; p < Np; ++p)
-    RIHIP_REQUIRE(rid[p] >= -1 && rid[p] < N, RIHIP_ERR_IO, "pq_index_load: %s: row id %lld out of range", path, (long long)rid[p]);
-  for (int64_t j = 0; j < dpad; ++j)
-    RIHIP_REQUIRE(isfinite(m[j]) && isfinite(s[j]) && s[j] > 0.f, RIHIP_ERR_IO, "pq_index_load: %s: quantiser column %lld is not finite", path, (long long)j);
-  for (size_t i = 0; i < book.size(); ++i)
-    RIHIP_REQUIRE(book[i] != -128, RIHIP_ERR_IO, "pq_index_load: %s: codebook byte %lld is -128", path, (long long)i);
-  Sq8Index* h = new Sq8Index();
-  h->du = (int)du; h->dk = (int)dk; h->dpad = (int)dpad; h->N = N; h->Np = Np; h->nlist = (int)nlist; h->nprobe = (int)nprobe;
-  h->list_len = ll;
-  h->pq_dsub = (int)dsub;
-  auto fill = [&]() -> int {
-    RCCHK(sq8_upload_list_layout(h, 0));
-    HIPCHK(hipMalloc((void**)&h->row_ids, sizeof(int64_t) * rid.size()));
-    HIPCHK(hipMalloc((void**)&h->C, sizeof(float) * C.size()));
-    HIPCHK(hipMalloc((void**)&h->pq_codes, codes.size()));
-    HIPCHK(hipMalloc((void**)&h->pq_book, book.size()));
-    HIPCHK(hipMalloc((void**)&h->centre, sizeof(float) * dpad));
-    HIPCHK(hipMalloc((void**)&h->scale, sizeof(float) * dpad));
-    HIPCHK(hipMemcpy(h->row_ids, rid.data(), sizeof(int64_t) * rid.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->C, C.data(), sizeof(float) * C.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->pq_codes, codes.data(), codes.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->pq_book, book.data(), book.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->centre, m.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->scale, s.data(), sizeof(float) * dpad, hipMemcpyHostToDevice));
-    return RIHIP_OK;
-  };
-  const int rc = fill();
-  if (rc) { sq8_free_handle(h); return rc; }
-  h->pq_peak_bytes = sq8_held_bytes(h);
-  *handle = h;
-  return RIHIP_OK;
-}
+extern "C" int rihip_pq_index_load(const char* path, void** handle) { return sq8_state_load(path, PQ_FORMAT, handle); }
+

@@ -1,10 +1,13 @@
-// Handle of the 8-bit scalar-quantised index, shared by sq8.hip (build, search, refine, filter, state I/O),
-// sq8_update.hip (add / remove / replace) and pq.hip (the product-quantised storage of the same handle: training,
-// encoding, decoding, state I/O), and the one function that makes a code.  All three compile with
-// `#pragma clang fp contract(off)` at their top: the quantisers are specified operation by operation.
+// Handle of the 8-bit scalar-quantised index, the one function that makes a code, and what its units call of each other:
+// sq8_build.hip (quantiser, build, handle lifetime, accessors), sq8_scan.hip (the int8 scan), sq8.hip (search driver; plain,
+// filtered and excluding search), sq8_refine.hip (attached f32 rows, refined search, certificate), sq8_state.hip (state
+// files), sq8_update.hip (add / remove / replace) and pq.hip (the product-quantised storage of the same handle: training,
+// encoding, decoding).  All seven compile with `#pragma clang fp contract(off)` at their top: the quantisers, the query
+// transform, the decode, the refine and the certificate are specified operation by operation.
 #pragma once
 #include "common.h"
 #include "ip_index.h"
+#include "search_kernels.h"
 
 #include <vector>
 
@@ -66,14 +69,71 @@ struct Sq8Index {
 
 inline bool sq8_has_storage(const Sq8Index* h) { return h && (h->codes || h->pq_codes); }
 
-// what pq.hip needs of sq8.hip: the SQ8 build (layout, row ids, quantiser, codes), the layout upload, the bytes a handle
-// holds and its destructor
-int sq8_build_handle(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, hipStream_t st);
-int sq8_upload_list_layout(Sq8Index* h, hipStream_t st);
+// ---- sq8_build.hip: the SQ8 build of a fresh handle (layout, row ids, quantiser, codes), the list offsets / lengths on the
+// device from the host copy list_len, the bytes a handle holds, its destructor and those of its two optional parts
+int sq8_build(Sq8Index* h, const IpIndex* src, const float* centre, const float* scale, hipStream_t st);
+int sq8_upload_layout(Sq8Index* h, hipStream_t st);
 int64_t sq8_held_bytes(const Sq8Index* h);
-void sq8_free_handle(Sq8Index* h);
-// and what sq8.hip needs of pq.hip: the decoded code matrix [Np, dpad] of a PQ handle in a fresh device allocation the
-// caller frees (a transient Np * dpad bytes)
+void sq8_free(Sq8Index* h);
+void sq8_drop_vectors(Sq8Index* h);
+void sq8_drop_tags(Sq8Index* h);
+
+// ---- sq8.hip: the search driver
+// what a search adds to the plain one: tag predicates (query q's at pred[q * pred_stride]), seen lists (the queries are
+// query q_base .. of the batch the lists describe), and whether the result holds mapped ids (h->id_map) or rows
+struct Sq8SearchOpts {
+  const uint32_t* pred = nullptr;
+  int pred_stride = 0;
+  const SeenArgs* seen = nullptr;
+  int64_t q_base = 0;
+  bool map_ids = true;
+};
+int sq8_search(Sq8Index* h, const float* Q, int64_t nq, int k, int mode, float* out_s, int64_t* out_r, int* out_i, hipStream_t st,
+               const Sq8SearchOpts& o);
+// what a search entry point was given and what it needs: the argument check of all six (`who` leads every message)
+struct Sq8SearchCall {
+  const char* who;
+  const float* Q; int64_t nq;
+  int k, k_scan, mode;          // k_scan > 0: a refined search (vectors attached, 1 <= k <= k_scan <= K_MAX)
+  bool outputs;                 // every mandatory output is there
+  bool filtered;                // predicates are mandatory (given ones always need a tagged index)
+  const uint32_t* pred; int64_t pred_stride;
+  const SeenArgs* seen;         // an excluding search: its lists, or null
+};
+int sq8_check_search(const Sq8Index* h, const Sq8SearchCall& c);
+// limb rows, t and b of the queries into the handle's scratch (t_out / b_out null) or the caller's arrays
+int sq8_transform_queries(Sq8Index* h, const float* Q, int64_t nq, int16_t* n16, float* t_out, double* b_out, hipStream_t st);
+int sq8_ensure_inv_pos(Sq8Index* h, hipStream_t st);   // the handle's inverse of row_ids, made on first use
+// X [n, du] device rows -> the same rows at the f32 side's width dk (through the handle's qpad when du != dk); a result
+// that is not 16-byte aligned is refused with `misaligned`
+int sq8_rows_at_dk(Sq8Index* h, const float*& X, int64_t n, const char* misaligned, hipStream_t st);
+
+// ---- sq8_refine.hip: e_j = max |x_ij - (m_j + s_j c_ij)| and a_j = max |x_ij| over the n_rows physical rows that hold a
+// row, in f64.  by_row: the f32 row of physical row r is X[row_ids[r]] (insertion order), else X[r].  part: nb * 2 * dk
+// doubles of scratch.  Maxima: the same bits for every nb.
+void sq8_launch_ranges(bool by_row, const float* X, const int8_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
+                       const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st);
+
+// ---- sq8_state.hip: one writer and one reader for the SQ8 and the PQ state file.  Both are magic[8], n_hdr int64 header
+// words {version 1, du, dk, dpad, N, Np, nlist, nprobe, format's own ...}, centre f32[dpad], scale f32[dpad], centroids
+// f32[nlist, dk], list lengths int64[nlist], row ids int64[Np], and the format's payload
+struct Sq8StateFormat {
+  const char* magic;     // 8 characters
+  const char* name;      // leads every message: "sq8_index" / "pq_index"
+  const char* kind;      // "an SQ8" / "a PQ"
+  int n_extra;           // header words of its own behind the common eight (x: those words)
+  bool (*extra_ok)(const int64_t* x, int64_t dpad);
+  int64_t (*payload_bytes)(const int64_t* x, int64_t Np, int64_t dpad);
+  // checks the payload and uploads it into the fresh handle (its sizes are set, nothing else is)
+  int (*fill)(Sq8Index* h, const int64_t* x, const int8_t* payload, const char* path);
+};
+struct Sq8StateBlock { const void* dev; size_t bytes; };   // a piece of the payload on the device
+int sq8_state_save(const Sq8Index* h, const char* path, const Sq8StateFormat& f, const int64_t* x, const Sq8StateBlock* blocks,
+                   int n_blocks);
+int sq8_state_load(const char* path, const Sq8StateFormat& f, void** handle);
+
+// ---- pq.hip: the decoded code matrix [Np, dpad] of a PQ handle in a fresh device allocation the caller frees (a
+// transient Np * dpad bytes)
 int pq_decode_all(const Sq8Index* h, int8_t** out_dev, hipStream_t st);
 
 __device__ __forceinline__ int sq8_code(float x, float m, float s) {

@@ -16,7 +16,8 @@
 //              row id and the tag word travel with lane 0.  ~2*Np*(dpad + 8 + 4) bytes.
 //   vectors  : the attached f32 rows are compacted in insertion order (index_update_compact_kernel), then e_j and a_j
 //              are recomputed in f64 over the final rows against the final stored codes (a removed row can shrink a
-//              maximum), in the fixed order of sq8_refine_range_part_kernel, without atomics.
+//              maximum), by the range pass that attached them (sq8_launch_ranges in sq8_refine.hip, reading the f32 row
+//              of a physical row through its row id), without atomics.
 // Flat handles (nlist == 1) take the same kernels.  The new arrays are built next to the old ones and swapped in at the
 // end (peak device memory = old + new); a call that is refused or fails leaves the old index searchable.
 #pragma clang fp contract(off)   // the quantiser is specified operation by operation: no fused multiply-add
@@ -134,50 +135,6 @@ __global__ __launch_bounds__(256) void sq8_update_repack_kernel(const Sq8RepackA
   }
 }
 
-// e_j and a_j over the final rows: sq8_refine_range_part_kernel with the f32 row of physical row r read from the
-// insertion-order copy (vec[row_ids[r]]) instead of a physical-order source.  Block b takes a contiguous range of
-// physical rows, thread (rr, c) every rpp-th row of column c; f64, no atomics, fixed order.
-__global__ __launch_bounds__(256) void sq8_update_range_part_kernel(const float* __restrict__ vec, const int8_t* __restrict__ codes,
-                                                                    const int64_t* __restrict__ row_ids, int64_t n_rows, int dk,
-                                                                    int dpad, const float* __restrict__ centre,
-                                                                    const float* __restrict__ scale, double* part) {
-  __shared__ double se[256], sa[256];
-  const int tid = threadIdx.x, rpp = 256 / dk, rr = tid / dk, c = tid % dk;
-  const int64_t per = (n_rows + gridDim.x - 1) / gridDim.x;
-  const int64_t r0 = (int64_t)blockIdx.x * per, r1 = (r0 + per < n_rows) ? r0 + per : n_rows;
-  const double m = (double)centre[c], s = (double)scale[c];
-  double e = 0.0, a = 0.0;
-  for (int64_t r = r0 + rr; r < r1; r += rpp) {
-    const int64_t row = row_ids[r];
-    if (row < 0) continue;
-    const double x = (double)vec[(size_t)row * dk + c];
-    const double prod = s * (double)codes[(size_t)r * dpad + c];   // exact: 24 x 8 bits
-    const double dec = m + prod;
-    e = fmax(e, fabs(x - dec));
-    a = fmax(a, fabs(x));
-  }
-  se[tid] = e; sa[tid] = a;
-  __syncthreads();
-  if (rr == 0) {
-    for (int k = 1; k < rpp; ++k) { e = fmax(e, se[k * dk + c]); a = fmax(a, sa[k * dk + c]); }
-    part[((size_t)blockIdx.x * 2 + 0) * dk + c] = e;
-    part[((size_t)blockIdx.x * 2 + 1) * dk + c] = a;
-  }
-}
-// one workgroup of 256 threads per column: thread t takes the blocks t, t + 256, ..., then thread 0 the 256 results in order
-__global__ __launch_bounds__(256) void sq8_update_range_final_kernel(const double* __restrict__ part, int nb, int dk, double* e_out,
-                                                                     double* a_out) {
-  __shared__ double se[256], sa[256];
-  const int j = blockIdx.x, tid = threadIdx.x;
-  double e = 0.0, a = 0.0;
-  for (int b = tid; b < nb; b += 256) { e = fmax(e, part[((size_t)b * 2 + 0) * dk + j]); a = fmax(a, part[((size_t)b * 2 + 1) * dk + j]); }
-  se[tid] = e; sa[tid] = a;
-  __syncthreads();
-  if (tid != 0) return;
-  for (int k = 1; k < 256; ++k) { e = fmax(e, se[k]); a = fmax(a, sa[k]); }
-  e_out[j] = e; a_out[j] = a;
-}
-
 struct Owned {   // everything the call must free on every way out
   UpdateScratch s; Grouper g;
   int8_t* codes = nullptr; int64_t* rid = nullptr; uint32_t* tags = nullptr; int64_t* poff = nullptr; int* len = nullptr;
@@ -187,17 +144,6 @@ struct Owned {   // everything the call must free on every way out
     hipFree(codes); hipFree(rid); hipFree(tags); hipFree(poff); hipFree(len); hipFree(vec); hipFree(e); hipFree(a); hipFree(part);
   }
 };
-
-// X [n, du] device rows -> the same rows at the f32 side's width dk (through the handle's qpad when du != dk)
-int rows_at_dk(Sq8Index* h, const float*& X, int64_t n, const char* who, hipStream_t st) {
-  if (h->du != h->dk) {
-    RCCHK(h->qpad.reserve(n * h->dk));
-    RCCHK(pad_rows(X, n, h->du, h->dk, h->qpad.p, st));
-    X = h->qpad.p;
-  }
-  RIHIP_REQUIRE((reinterpret_cast<uintptr_t>(X) & 15) == 0, RIHIP_ERR_ARG, "%s: the rows must be 16-byte aligned", who);
-  return RIHIP_OK;
-}
 
 }  // namespace
 
@@ -218,7 +164,8 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
   RIHIP_REQUIRE(N + n_add + (int64_t)TR * (nlist + 1) < (1ll << 31) && n_drop < (1ll << 31), RIHIP_ERR_ARG,
                 "sq8_update_apply: %lld + %lld rows exceed the 2^31 row limit", (long long)N, (long long)n_add);
   hipStream_t st = (hipStream_t)stream;
-  if (n_add > 0) RCCHK(rows_at_dk(h, X_add, n_add, "sq8_update_apply", st));   // zero-padded to dk, as the source index held them
+  // zero-padded to dk, as the source index held them
+  if (n_add > 0) RCCHK(sq8_rows_at_dk(h, X_add, n_add, "sq8_update_apply: the rows must be 16-byte aligned", st));
 
   Owned o;
   UpdateScratch& s = o.s;
@@ -351,9 +298,7 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
     const int64_t tv = (N + n_add) * d4;
     hipLaunchKernelGGL(index_update_compact_kernel, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, st, h->vec, N, keep, rscan, X_add,
                        n_add, n_keep, d4, o.vec);
-    hipLaunchKernelGGL(sq8_update_range_part_kernel, dim3(nb), dim3(256), 0, st, o.vec, o.codes, o.rid, Np_n, dk, dpad, h->centre,
-                       h->scale, o.part);
-    hipLaunchKernelGGL(sq8_update_range_final_kernel, dim3(dk), dim3(256), 0, st, o.part, nb, dk, o.e, o.a);
+    sq8_launch_ranges(true, o.vec, o.codes, o.rid, Np_n, dk, dpad, h->centre, h->scale, o.part, nb, o.e, o.a, st);
     RIHIP_CHECK_LAUNCH();
   }
   HIPCHK(hipStreamSynchronize(st));   // (the host vectors go away; the caller's rows may go away after the call)
@@ -381,7 +326,7 @@ extern "C" int rihip_sq8_update_assign(void* handle, const float* X, int64_t n, 
     HIPCHK(hipMemsetAsync(assign_out, 0, sizeof(int32_t) * (size_t)n, st));
     return RIHIP_OK;
   }
-  RCCHK(rows_at_dk(h, X, n, "sq8_update_assign", st));
+  RCCHK(sq8_rows_at_dk(h, X, n, "sq8_update_assign: the rows must be 16-byte aligned", st));
   return launch_assign(h->dk, X, n, h->C, h->nlist, assign_out, st);
 }
 

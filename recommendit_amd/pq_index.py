@@ -17,7 +17,8 @@ N * dpad bytes.  ``save`` / ``load`` are SQ8Index's on the PQ file format (``_SA
 other's file.  A PQ index is not updated in place (its codebooks are trained on the corpus): ``add_items``,
 ``remove_items`` and ``update_items`` raise NotImplementedError -- rebuild with ``from_index``.
 
-There is no NumPy or torch path for training, encoding or search: everything runs in csrc/pq.hip and csrc/sq8.hip.
+There is no NumPy or torch path for training, encoding or search: everything runs in csrc/pq.hip and the SQ8 index's
+units (csrc/sq8.hip over csrc/sq8_scan.hip for the search).
 """
 from __future__ import annotations
 

@@ -25,7 +25,9 @@ attached vectors travel along, and the handle ends bit for bit where ``from_inde
 ``ranges=quantizer()`` would leave it.  Neither centroids nor quantiser are retrained: ``update_stats()["clamped"]``
 counts the code values of added rows that fell outside the quantiser's range.
 
-There is no NumPy or torch path for encode, search or repack: everything runs in csrc/sq8.hip and csrc/sq8_update.hip.
+There is no NumPy or torch path for encode, search or repack: everything runs in csrc/sq8_build.hip (encode),
+csrc/sq8.hip over csrc/sq8_scan.hip (search), csrc/sq8_refine.hip (refined search), csrc/sq8_state.hip (save / load) and
+csrc/sq8_update.hip (repack).
 """
 from __future__ import annotations
 

@@ -392,6 +392,43 @@ def test_save_load_save_and_the_refusals(trained_case, tmp_path):
     _same_bytes(want, [t.cpu().numpy() for t in pq.batch_search_device(c["qd"], k=k, normalized=True, return_int=True)])
 
 
+def test_the_loader_refuses_a_damaged_file_field_by_field(trained_case, tmp_path):
+    """as test_gpu_sq8_index.py's refusals, over the PQ format: ten header words, one more payload block"""
+    from recommendit_amd import PQIndex
+    from recommendit_amd._lib import RihipError
+    p = tmp_path / "a.pq"
+    trained_case["pq"].save(str(p))
+    raw = p.read_bytes()
+    meta = p.with_suffix(".meta.pkl").read_bytes()
+    assert isinstance(PQIndex.load(str(p)), PQIndex)           # the undamaged file loads
+
+    def try_load(name, data):
+        f = tmp_path / name
+        f.write_bytes(data)
+        f.with_suffix(".meta.pkl").write_bytes(meta)
+        with pytest.raises(RihipError):
+            PQIndex.load(str(f))
+
+    try_load("short_header.pq", raw[:40])
+    try_load("truncated.pq", raw[:len(raw) // 2])
+    hdr = np.frombuffer(raw[8:88], dtype=np.int64)
+    dk, dpad, Np, nlist, M = (int(hdr[i]) for i in (2, 3, 5, 6, 9))
+    assert hdr.tolist() == [1, E_D, 64, 64, E_N, Np, E_NLIST, E_NPROBE, E_DSUB, 64 // E_DSUB]
+    for field, value in ((0, 2), (1, 200), (2, 96), (3, 32), (4, -5), (4, 2 ** 40), (5, hdr[5] + 6400), (6, 0), (6, 10 ** 6), (7, 0),
+                         (8, 12), (9, hdr[9] + 1)):
+        h2 = hdr.copy()
+        h2[field] = value
+        try_load(f"field{field}_{abs(int(value))}.pq", raw[:8] + h2.tobytes() + raw[88:])
+    lens_at = 88 + 8 * dpad + 4 * nlist * dk                   # list lengths: behind quantiser and centroids
+    ll = np.frombuffer(raw[lens_at:lens_at + 8 * nlist], dtype=np.int64).copy()
+    assert ll.sum() == E_N
+    ll[0] += 1
+    try_load("lists.pq", raw[:lens_at] + ll.tobytes() + raw[lens_at + 8 * nlist:])
+    book_at = lens_at + 8 * nlist + 8 * Np                     # codebooks: behind list lengths and row ids
+    assert len(raw) == book_at + 256 * dpad + Np * M
+    try_load("book.pq", raw[:book_at + 5] + b"\x80" + raw[book_at + 6:])
+
+
 # ---- 5. serving ------------------------------------------------------------------------------------------------------------
 def test_pipeline_over_a_pq_index_equals_its_stages_run_by_hand(tmp_path):
     from oracle import fixtures as fx

@@ -1,5 +1,5 @@
 """GPU: seen-item exclusion inside the index scan (exclusion="scan"; csrc/search_exclude.hip, the masked instantiations of
-scan_kernel, ivf_scan_lm_kernel and sq8_scan_lm_kernel, the drivers in csrc/topk.hip and csrc/sq8.hip).
+scan_kernel, ivf_scan_lm_kernel and sq8_scan_lm_kernel (csrc/sq8_scan.hip), the drivers in csrc/topk.hip and csrc/sq8.hip).
 
 Every comparison is EQUALITY of ids and score bits on every query.  Vectors, queries and injected centroids are small
 integers searched with normalized=True, so every f32 inner product is exact and the expected rows and scores come from
