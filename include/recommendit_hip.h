@@ -714,6 +714,7 @@ int rihip_sq8_filter_stats(void* handle, int64_t* out);     /* out: int64[2] */
  *   Certificate: out_cert u8 [nq], out_bound f64 [nq] or NULL, all f64 on the device, sums in ascending j over j < d:
  *     E1 = sum_j |q_j| * e_j          the codes' error
  *     E2 = 127 * sum_j | q_j * s_j - t * n_j |     the query's 16-bit rounding (both products exact in f64), |c_ij| <= 127
+ *                                                  (a residual PQ handle: 254 here and in W, the bound on its int16 codes)
  *     A  = sum_j |q_j| * a_j,   E3 = g * A,   g = u / (1 - u),  u = dk * 2^-24      f's own rounding: at most dk roundings on
  *                                                                                   any path from a product to f
  *     M  = sum_j |q_j * m_j|,   W = 127 * sum_j |t * n_j|       (magnitudes of b and of any t * S)
@@ -832,7 +833,8 @@ int rihip_sq8_update_stats(void* handle, int64_t* out);     /* out: int64[4] */
  *   distortion trace (n_iter + 1 values).  Nothing depends on the physical row order: a flat and an IVF build of the same
  *   rows under the same (centre, scale) give the same codebooks and the same byte for every original row.
  *   Decoded code c^[i][m dsub + j] = book[m][byte[i][m]][j].
- * No residual encoding against the IVF centroids: one integer score per row, comparable across lists.
+ * No residual encoding against the IVF centroids by default: one integer score per row, comparable across lists (the
+ * opt-in residual form follows below at rihip_pq_index_from_ip_index_residual).
  * from_ip_index: as the SQ8 call; book host int8 [M,256,dsub] injects the codebooks and skips training (no byte -128).
  * The build holds the SQ8 codes transiently (train_stats: peak_bytes) and frees them before it returns.
  * Every rihip_sq8_* search, filter, exclude, refine, stats and id-map call takes the handle and returns what it returns
@@ -852,6 +854,48 @@ int rihip_pq_index_get_codebooks(void* handle, int8_t* out);       /* synchronou
 int rihip_pq_index_train_stats(void* handle, int64_t* trace, int cap, int* n_trace, int64_t* peak_bytes, double* ms);
 int rihip_pq_index_save(void* handle, const char* path);           /* host path; synchronous */
 int rihip_pq_index_load(const char* path, void** handle);          /* host path; synchronous */
+
+/* ---- Product-quantised index: residual codes against the IVF centroids (faiss IndexIVFPQ's by_residual) -----------
+ * Opt-in (by_residual != 0); without it every call above does what it did, bit for bit.  The source must be an IVF
+ * ip_index (a flat one has one list and no centroids: RIHIP_ERR_ARG).  m, s: the handle's SQ8 quantiser, computed over the
+ * rows or injected as above; c_i: row i's SQ8 code, int8 [dpad], padding columns 0; l(i): the list that holds row i;
+ * C_l: the handle's centroid, f32 [nlist, dk].
+ *   1. List codes   K_l[j] = clamp(rintf((C_l[j] - m_j) / s_j), -127, 127) for j < d, 0 in the padding columns: int8
+ *      [nlist, dpad].  An empty list has a centroid and so a K_l.
+ *   2. Residual     r_i[j] = clamp((int)c_i[j] - (int)K_l(i)[j], -127, 127), int8.  The clamp is part of the definition; the
+ *      values it changed are counted (residual_clamped) and are never a reason to refuse.
+ *   3. Quantiser    the quantiser above, unchanged, with r in place of c: seeds from original rows (e N) / 256, n_iter
+ *      Lloyd steps with exact integer sums, one f64 division per codebook byte, ties to the lowest entry, entries in
+ *      [-127, 127].  The distortion trace is over r.  Injected codebooks are residual codebooks and skip the training.
+ *   4. Decoded code c^_i[j] = K_l(i)[j] + book[m][byte[i][m]][j mod dsub]: an int16 in [-254, 254], NOT clamped.  The
+ *      reconstruction is x^_ij = m_j + s_j * c^_ij (f32: (float)c^, one product, one sum).
+ *   5. Score        S_i = sum_j n_j c^_ij = T[q, l(i)] + sum_j n_j book[..][j],  T[q, l] = sum_j n_j K_l[j] an exact i32.
+ *      |n_j| <= 32512, |c^| <= 254, dpad <= 128: |S| <= 32512 * 254 * 128 = 1 057 030 144 < 2^30, so the candidate key, the
+ *      i32 threshold, out_iscores and S_cut are used as they are.  T is computed per (query, probed list) pair after the
+ *      query transform; the scan adds it to the gathered dot product wherever it forms a score.
+ *      A residual PQ index is thereby the exact-integer-score index of its own int16 reconstruction: everything the
+ *      rihip_sq8_* searches promise holds with "the decoded matrix" read as c^ -- ranking by (S descending, row ascending),
+ *      the reported score (float)(b + t S), the same bytes from all three modes, the integer completeness argument of the
+ *      thresholded pass and its re-do, tag filters, both exclusion routes.
+ *   6. Refine       stage 2 reads only the attached f32 rows and does not change.  e_j is taken over the int16 decoded
+ *      codes (s_j * c^_ij is still exact in f64).  In the certificate of rihip_sq8_refine_search the factor 127 in E2 and W
+ *      is the bound on |c_ij|; on a residual handle it is 254, on every other handle it stays 127 with the same bits.  The
+ *      proof reads as before: the integer score is within E2 / t of the decoded row's product with q because each of the d
+ *      terms |q_j s_j - t n_j| is multiplied by a code of magnitude at most 254, and W bounds |t S| the same way.
+ *   7. rihip_sq8_index_get_codes (int8) returns RIHIP_ERR_STATE on a residual handle; get_decoded16 returns the decoded
+ *      matrix, host int16 [N, d] in original row order.  rihip_sq8_index_reconstruct works.  Live updates stay refused.
+ * is_residual: 1 / 0.  get_list_codes: host int8 [nlist, dpad].  residual_clamped: the count of step 2 (0 after load, and
+ * on a handle that is not residual).
+ * save: rihip_pq_index_save writes a residual handle in a format of its own: "RIHIPPR1", the PQ header with a third
+ * word of its own {dsub, M, nlist * dpad}, and the payload list codes int8[nlist, dpad], codebooks, entry numbers.
+ * load_residual reads it; rihip_sq8_index_load, rihip_pq_index_load and load_residual refuse each other's files. */
+int rihip_pq_index_from_ip_index_residual(void* ip_handle, const float* centre, const float* scale, int dsub, int n_iter,
+                                          const int8_t* book, int by_residual, void** handle, void* stream);
+int rihip_pq_index_is_residual(void* handle);
+int rihip_pq_index_get_list_codes(void* handle, int8_t* out);      /* synchronous */
+int rihip_pq_index_get_decoded16(void* handle, int16_t* out);      /* synchronous */
+int rihip_pq_index_residual_clamped(void* handle, int64_t* out);
+int rihip_pq_index_load_residual(const char* path, void** handle); /* host path; synchronous */
 
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict

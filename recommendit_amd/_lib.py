@@ -188,6 +188,12 @@ SIGNATURES = {
     "rihip_pq_index_train_stats": (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(c_i64), vp]),
     "rihip_pq_index_save": (C.c_int, [vp, C.c_char_p]),
     "rihip_pq_index_load": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
+    "rihip_pq_index_from_ip_index_residual": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp), vp]),
+    "rihip_pq_index_is_residual": (C.c_int, [vp]),
+    "rihip_pq_index_get_list_codes": (C.c_int, [vp, vp]),
+    "rihip_pq_index_get_decoded16": (C.c_int, [vp, vp]),
+    "rihip_pq_index_residual_clamped": (C.c_int, [vp, C.POINTER(c_i64)]),
+    "rihip_pq_index_load_residual": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

@@ -15,7 +15,8 @@
 //
 // A handle may hold product-quantised storage instead of the int8 matrix.  sq8_scan picks the source; the PQ
 // instantiations of the scan gather the operand bytes from the codebooks in LDS, and everything else in this file is the
-// same code for both.
+// same code for both.  A residual PQ handle adds one kernel: T of every (query, probed list) pair, filled in sq8_prepare
+// once the probes are known and added to the gathered dot product by the residual instantiations of the scan.
 #pragma clang fp contract(off)   // the query transform and the decode are specified operation by operation: no fused multiply-add
 #include "common.h"
 #include "recommendit_hip.h"
@@ -114,6 +115,36 @@ __global__ void sq8_gather_kernel(const int8_t* __restrict__ hi, const int8_t* _
   if (j < dk) oQ[r * dk + j] = Qf[src * dk + j];
 }
 
+// Residual PQ: T[pair] = sum_j n_j K_l[j] of every (query, probed list) pair, l = probe_list[pair], pair = q * nprobe +
+// probe rank (what list_q holds and the scan reads).  dpad / 16 lanes per pair, 16 columns each: eight packed int8 dot
+// products on the limbs (v_dot4_i32_i8), T = 256 <hi, K> + <lo, K>, |T| <= 32512 * 127 * 128 < 2^30: exact in i32.
+__global__ __launch_bounds__(256) void sq8_pair_offset_kernel(const int8_t* __restrict__ qhi, const int8_t* __restrict__ qlo,
+                                                              const int* __restrict__ probe_list, const int8_t* __restrict__ K,
+                                                              int64_t n_pairs, int nprobe, int dpad, int* pair_t) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  const int lpp = dpad / 16;   // 4 or 8 lanes per pair
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t pair = i / lpp;
+  const int part = (int)(i % lpp);
+  int sh = 0, sl = 0;
+  int c = -1;
+  if (pair < n_pairs) c = probe_list[pair];
+  if (c >= 0) {
+    const int64_t q = pair / nprobe;
+    const i32x4 vh = *reinterpret_cast<const i32x4*>(qhi + (size_t)q * dpad + 16 * part);
+    const i32x4 vl = *reinterpret_cast<const i32x4*>(qlo + (size_t)q * dpad + 16 * part);
+    const i32x4 vk = *reinterpret_cast<const i32x4*>(K + (size_t)c * dpad + 16 * part);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      sh = __builtin_amdgcn_sdot4(vh[u], vk[u], sh, false);
+      sl = __builtin_amdgcn_sdot4(vl[u], vk[u], sl, false);
+    }
+  }
+  int t = sh * 256 + sl;
+  for (int o = lpp >> 1; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);   // (the lanes of a pair are aligned: 256 % lpp == 0)
+  if (part == 0 && pair < n_pairs) pair_t[pair] = t;
+}
+
 // ------------------------------------------------ search driver ------------------------------------------------------
 // one internal pass: the queries [0, nq) of the pointers below
 struct Sq8Search {
@@ -167,6 +198,12 @@ int sq8_prepare(const Sq8Search& s, const Sq8Geom& g, int first_tile_step, uint6
   launch_ivf_plan(h->list_cnt.p, h->list_poff, g.nlist, first_tile_step, SQ8_TARGET, h->list_qoff.p, h->list_cur.p, h->work_off.p,
                   h->plan.p, h->count.p, n * CSTRIDE, s.st);
   launch_ivf_scatter(h->probe_list.p, n * g.nprobe, g.nprobe, h->list_cur.p, h->list_q.p, s.st);
+  if (h->pq_residual) {   // T of this pass's pairs (the re-do's renumbered queries come through here with their own limbs)
+    const int64_t n_pairs = n * g.nprobe, nthr = n_pairs * (h->dpad / 16);
+    RCCHK(h->pair_t.reserve(n_pairs));
+    hipLaunchKernelGGL(sq8_pair_offset_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s.st, s.qhi, s.qlo, h->probe_list.p,
+                       h->pq_list_codes, n_pairs, g.nprobe, h->dpad, h->pair_t.p);
+  }
   return check_launch("sq8 prepare");
 }
 
@@ -186,12 +223,13 @@ int sq8_scan(const Sq8Search& s, const Sq8Geom& g, const float* thr, uint64_t* c
   x.nprobe = g.nprobe; x.count_stride = CSTRIDE; x.dense_cap = dense_cap; x.dense_ids = dense_ids;
   x.tags = s.pred ? h->tags : nullptr; x.pred = s.pred; x.pred_stride = s.pred_stride;
   x.xmask = s.xmask; x.xW = s.xW; x.xrow = s.xrow;
+  x.pair_t = h->pq_residual ? h->pair_t.p : nullptr;
   // n_work <= sum over (list, group) of (tiles/tpi + 1) <= target + #(list, query group) pairs
   const int64_t bound = (int64_t)SQ8_TARGET + g.nlist + (s.nq * g.nprobe + 31) / 32 + 4;
   const dim3 grid((unsigned)((bound + 3) / 4));
   const int fm = x.xmask ? (x.tags ? FM_TAGS_MASK : FM_MASK) : (x.tags ? FM_TAGS : FM_NONE);
   const char* what = fm == FM_TAGS_MASK ? "masked filtered sq8 scan" : fm == FM_MASK ? "masked sq8 scan" : fm == FM_TAGS ? "filtered sq8 scan" : "sq8 scan";
-  sq8_launch_scan(h->dpad, fm, h->pq_codes ? h->pq_dsub : 0, grid, s.st, x);
+  sq8_launch_scan(h->dpad, fm, h->pq_codes ? h->pq_dsub : 0, h->pq_residual, grid, s.st, x);
   return check_launch(what);
 }
 

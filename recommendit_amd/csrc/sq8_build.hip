@@ -81,17 +81,19 @@ __global__ void sq8_identity_rows_kernel(int64_t* row_ids, int64_t N, int64_t Np
   if (i < Np) row_ids[i] = i < N ? i : -1;
 }
 
-// decoded rows in original row order: out[row, j] = m_j + s_j c (two roundings)
-__global__ void sq8_reconstruct_kernel(const int8_t* __restrict__ codes, const int64_t* __restrict__ row_ids, int64_t Np, int du,
+// decoded rows in original row order: out[row, j] = m_j + s_j c (two roundings).  CT: int8, or the int16 decoded codes of
+// a residual PQ handle (|c| <= 254: (float)c and s_j * c round as for int8)
+template <typename CT>
+__global__ void sq8_reconstruct_kernel(const CT* __restrict__ codes, const int64_t* __restrict__ row_ids, int64_t Np, int du,
                                        int dpad, const float* __restrict__ centre, const float* __restrict__ scale, float* out,
-                                       int8_t* out_codes) {
+                                       CT* out_codes) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Np * du) return;
   const int64_t p = i / du;
   const int j = (int)(i % du);
   const int64_t row = row_ids[p];
   if (row < 0) return;
-  const int8_t c = codes[(size_t)p * dpad + j];
+  const CT c = codes[(size_t)p * dpad + j];
   if (out_codes) out_codes[(size_t)row * du + j] = c;
   if (out) {
     const float prod = scale[j] * (float)c;
@@ -99,32 +101,42 @@ __global__ void sq8_reconstruct_kernel(const int8_t* __restrict__ codes, const i
   }
 }
 
-int sq8_rows_out(Sq8Index* h, float* out_x, int8_t* out_c) {
-  float* dx = nullptr; int8_t* dc = nullptr;
-  const size_t n = (size_t)h->N * h->du;
-  if (out_x) HIPCHK(hipMalloc((void**)&dx, sizeof(float) * n));
-  if (out_c && hipMalloc((void**)&dc, n) != hipSuccess) { hipFree(dx); rihip_set_error("sq8_index: device allocation failed"); return RIHIP_ERR_HIP; }
-  int8_t* decoded = nullptr;   // a PQ handle: its decoded code matrix, a transient Np * dpad bytes
-  if (!h->codes && pq_decode_all(h, &decoded, 0) != RIHIP_OK) { hipFree(dx); hipFree(dc); return RIHIP_ERR_HIP; }
-  const int64_t tot = h->Np * h->du;
-  hipLaunchKernelGGL(sq8_reconstruct_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, h->codes ? h->codes : decoded, h->row_ids, h->Np, h->du,
-                     h->dpad, h->centre, h->scale, dx, dc);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && out_x) e = hipMemcpy(out_x, dx, sizeof(float) * n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out_c) e = hipMemcpy(out_c, dc, n, hipMemcpyDeviceToHost);
-  hipFree(dx); hipFree(dc); hipFree(decoded);
-  HIPCHK(e);
-  return RIHIP_OK;
-}
-
 }  // namespace
 
 namespace rihip_index {
 
+// out_c: int8 [N, du], or int16 [N, du] on a residual PQ handle
+int sq8_rows_out(Sq8Index* h, float* out_x, void* out_c) {
+  const bool wide = h->pq_residual;
+  const size_t n = (size_t)h->N * h->du, cb = wide ? 2 * n : n;
+  float* dx = nullptr; void* dc = nullptr;
+  if (out_x) HIPCHK(hipMalloc((void**)&dx, sizeof(float) * n));
+  if (out_c && hipMalloc(&dc, cb) != hipSuccess) { hipFree(dx); rihip_set_error("sq8_index: device allocation failed"); return RIHIP_ERR_HIP; }
+  int8_t* decoded = nullptr;     // a PQ handle: its decoded code matrix, a transient Np * dpad bytes
+  int16_t* decoded16 = nullptr;  // (a residual one: twice that)
+  if (wide ? pq_decode_all16(h, &decoded16, 0) != RIHIP_OK : (!h->codes && pq_decode_all(h, &decoded, 0) != RIHIP_OK)) {
+    hipFree(dx); hipFree(dc); return RIHIP_ERR_HIP;
+  }
+  const int64_t tot = h->Np * h->du;
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (wide)
+    hipLaunchKernelGGL(sq8_reconstruct_kernel<int16_t>, grid, dim3(256), 0, 0, decoded16, h->row_ids, h->Np, h->du, h->dpad, h->centre,
+                       h->scale, dx, (int16_t*)dc);
+  else
+    hipLaunchKernelGGL(sq8_reconstruct_kernel<int8_t>, grid, dim3(256), 0, 0, h->codes ? h->codes : decoded, h->row_ids, h->Np, h->du,
+                       h->dpad, h->centre, h->scale, dx, (int8_t*)dc);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && out_x) e = hipMemcpy(out_x, dx, sizeof(float) * n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out_c) e = hipMemcpy(out_c, dc, cb, hipMemcpyDeviceToHost);
+  hipFree(dx); hipFree(dc); hipFree(decoded); hipFree(decoded16);
+  HIPCHK(e);
+  return RIHIP_OK;
+}
+
 int64_t sq8_held_bytes(const Sq8Index* h) {
   // the code storage: the int8 matrix, or (a PQ handle) one byte per sub-space and row plus the codebooks
   const int64_t rows = h->pq_codes ? h->Np * (h->dpad / h->pq_dsub) + 256 * (int64_t)h->dpad : h->Np * h->dpad;
-  return rows + 2 * 4 * (int64_t)h->dpad + 4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
+  return rows + (h->pq_list_codes ? (int64_t)h->nlist * h->dpad : 0) + 2 * 4 * (int64_t)h->dpad +4 * (int64_t)h->nlist * h->dk + 8 * (int64_t)(h->nlist + 1) +
          4 * (int64_t)h->nlist + 8 * h->Np + (h->vec ? 4 * h->N * h->dk + 2 * 8 * (int64_t)h->dk : 0) + (h->tags ? 4 * h->Np : 0);
 }
 
@@ -149,13 +161,13 @@ void sq8_free(Sq8Index* h) {
   h->fpred.release(); h->xmask.release();
   hipFree(h->inv_pos);
   h->rs.release(); h->rr.release(); h->ri.release(); h->rnv.release(); h->rcut.release(); h->rkeys.release();
-  hipFree(h->codes); hipFree(h->pq_codes); hipFree(h->pq_book); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
+  hipFree(h->codes); hipFree(h->pq_codes); hipFree(h->pq_book); hipFree(h->pq_list_codes); hipFree(h->centre); hipFree(h->scale); hipFree(h->C); hipFree(h->list_poff); hipFree(h->list_len_dev);
   hipFree(h->row_ids);
   h->qhi.release(); h->qlo.release(); h->fhi.release(); h->flo.release(); h->qt.release(); h->qpad.release(); h->fQ.release();
   h->coarse.release(); h->thr.release(); h->qb.release(); h->cand.release(); h->scand.release(); h->fcand.release();
   h->count.release(); h->probe_list.release(); h->list_q.release(); h->list_cnt.release(); h->list_qoff.release();
   h->list_cur.release(); h->work_off.release(); h->plan.release(); h->fail_flags.release(); h->fail_list.release();
-  h->n_fail.release();
+  h->n_fail.release(); h->pair_t.release();
   if (h->h_nfail) hipHostFree(h->h_nfail);
   delete h;
 }
@@ -279,6 +291,8 @@ extern "C" int rihip_sq8_index_get_quantizer(void* handle, float* centre, float*
 extern "C" int rihip_sq8_index_get_codes(void* handle, int8_t* out) {
   Sq8Index* h = (Sq8Index*)handle;
   RIHIP_REQUIRE(h && out, RIHIP_ERR_ARG, "sq8_index_get_codes: bad arguments");
+  RIHIP_REQUIRE(!h->pq_residual, RIHIP_ERR_STATE,
+                "sq8_index_get_codes: the decoded codes of a residual PQ index are 16-bit (rihip_pq_index_get_decoded16)");
   return sq8_rows_out(h, nullptr, out);
 }
 

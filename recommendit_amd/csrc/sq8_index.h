@@ -27,6 +27,11 @@ struct Sq8Index {
   std::vector<int64_t> pq_trace;  // distortion of every assignment pass of the build (empty: injected codebooks, loaded)
   int64_t pq_peak_bytes = 0;      // device bytes at the build's peak (the transient SQ8 codes included)
   double pq_ms[3] = {0, 0, 0};    // host time of the build: range pass + SQ8 encode, codebook training, final assignment
+  // residual PQ (by_residual): the codebooks quantise c - K_l, K_l the list's centroid on the SQ8 grid; the decoded code
+  // K_l + entry is an int16 in [-254, 254] and the scan adds T[q, l] = sum_j n_j K_l[j] to the gathered dot product
+  int8_t* pq_list_codes = nullptr;   // [nlist, dpad], padding columns 0 (null: not a residual handle)
+  bool pq_residual = false;
+  int64_t pq_clamped = 0;            // residual values of the build that left [-127, 127] (0 after load)
   float* centre = nullptr;       // [dpad] (columns >= du: 0)
   float* scale = nullptr;         // [dpad] (columns >= du: 1)
   float* C = nullptr;             // [nlist, dk]
@@ -63,6 +68,7 @@ struct Sq8Index {
   DevBuf<int64_t> rr;
   DevBuf<int> ri, rnv, rcut;
   DevBuf<uint64_t> rkeys;
+  DevBuf<int> pair_t;                // residual PQ: T of every (query, probed list) pair of one pass, [nq * nprobe]
   DevBuf<int> count, probe_list, list_q, list_cnt, list_qoff, list_cur, work_off, plan, fail_flags, fail_list, n_fail;
   int* h_nfail = nullptr;   // pinned
 };
@@ -75,6 +81,9 @@ int sq8_build(Sq8Index* h, const IpIndex* src, const float* centre, const float*
 int sq8_upload_layout(Sq8Index* h, hipStream_t st);
 int64_t sq8_held_bytes(const Sq8Index* h);
 void sq8_free(Sq8Index* h);
+// the decoded rows (out_x f32 [N, du]) and / or the stored or decoded codes (out_c int8 [N, du]; int16 on a residual PQ
+// handle) in original row order on the host; either may be null
+int sq8_rows_out(Sq8Index* h, float* out_x, void* out_c);
 void sq8_drop_vectors(Sq8Index* h);
 void sq8_drop_tags(Sq8Index* h);
 
@@ -113,14 +122,17 @@ int sq8_rows_at_dk(Sq8Index* h, const float*& X, int64_t n, const char* misalign
 // doubles of scratch.  Maxima: the same bits for every nb.
 void sq8_launch_ranges(bool by_row, const float* X, const int8_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
                        const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st);
+// (the int16 decoded codes of a residual PQ handle)
+void sq8_launch_ranges(bool by_row, const float* X, const int16_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
+                       const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st);
 
-// ---- sq8_state.hip: one writer and one reader for the SQ8 and the PQ state file.  Both are magic[8], n_hdr int64 header
+// ---- sq8_state.hip: one writer and one reader for the SQ8, the PQ and the residual PQ state file.  All are magic[8], n_hdr int64 header
 // words {version 1, du, dk, dpad, N, Np, nlist, nprobe, format's own ...}, centre f32[dpad], scale f32[dpad], centroids
 // f32[nlist, dk], list lengths int64[nlist], row ids int64[Np], and the format's payload
 struct Sq8StateFormat {
   const char* magic;     // 8 characters
   const char* name;      // leads every message: "sq8_index" / "pq_index"
-  const char* kind;      // "an SQ8" / "a PQ"
+  const char* kind;      // "an SQ8" / "a PQ" / "a residual PQ"
   int n_extra;           // header words of its own behind the common eight (x: those words)
   bool (*extra_ok)(const int64_t* x, int64_t dpad);
   int64_t (*payload_bytes)(const int64_t* x, int64_t Np, int64_t dpad);
@@ -135,6 +147,8 @@ int sq8_state_load(const char* path, const Sq8StateFormat& f, void** handle);
 // ---- pq.hip: the decoded code matrix [Np, dpad] of a PQ handle in a fresh device allocation the caller frees (a
 // transient Np * dpad bytes)
 int pq_decode_all(const Sq8Index* h, int8_t** out_dev, hipStream_t st);
+// a residual PQ handle: its decoded codes K_l + entry as int16 [Np, dpad] (a transient 2 * Np * dpad bytes)
+int pq_decode_all16(const Sq8Index* h, int16_t** out_dev, hipStream_t st);
 
 __device__ __forceinline__ int sq8_code(float x, float m, float s) {
   float v = rintf((x - m) / s);            // one f32 subtraction, one correctly rounded f32 division, round to nearest even

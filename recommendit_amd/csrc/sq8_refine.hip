@@ -47,8 +47,9 @@ __global__ void sq8_scatter_rows_kernel(const float* __restrict__ X, const int64
 // rpp-th row of column c), f64, no atomics.  A maximum does not depend on the order it is taken in; the order is fixed
 // all the same.  The STORED code is read, so a clamped code of an injected quantiser counts with its full error.
 // BY_ROW: the f32 row of physical row r is X[row_ids[r]] (the insertion-order copy), else X[r] (a physical-order source).
-template <bool BY_ROW>
-__global__ __launch_bounds__(256) void sq8_range_part_kernel(const float* __restrict__ X, const int8_t* __restrict__ codes,
+// CT: int8, or the int16 decoded codes of a residual PQ handle (|c| <= 254: the product stays exact, 24 x 9 bits).
+template <bool BY_ROW, typename CT>
+__global__ __launch_bounds__(256) void sq8_range_part_kernel(const float* __restrict__ X, const CT* __restrict__ codes,
                                                              const int64_t* __restrict__ row_ids, int64_t n_rows, int dk, int dpad,
                                                              const float* __restrict__ centre, const float* __restrict__ scale,
                                                              double* part) {
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(128) void sq8_cert_kernel(const float* __restrict__
                                                        const int8_t* __restrict__ qhi, const int8_t* __restrict__ qlo,
                                                        const float* __restrict__ qt, const double* __restrict__ qb,
                                                        const int* __restrict__ n_valid, const int* __restrict__ s_cut,
-                                                       const float* __restrict__ out_scores, int k, int k_scan,
+                                                       const float* __restrict__ out_scores, int k, int k_scan, double cmax,
                                                        uint8_t* out_cert, double* out_bound) {
   __shared__ double term[5][128];
   __shared__ double sum[5];
@@ -204,9 +205,9 @@ __global__ __launch_bounds__(128) void sq8_cert_kernel(const float* __restrict__
   const double u = (double)dk * 0x1p-24;
   const double gamma = u / (1.0 - u);
   const double E1 = sum[0];
-  const double E2 = 127.0 * sum[1];
+  const double E2 = cmax * sum[1];   // cmax: the bound on |c_ij|, 127, or 254 on a residual PQ handle
   const double E3 = gamma * sum[2];
-  const double W = 127.0 * sum[4];
+  const double W = cmax * sum[4];
   const double mag = (((sum[3] + W) + sum[2]) + E1) + E2;
   const double slack = 0x1p-44 * mag + (double)dk * 0x1p-126;
   const double bound = ((E1 + E2) + E3) + slack;
@@ -246,7 +247,8 @@ int sq8_search_refined(Sq8Index* h, const float* Q, int64_t nq, int k, int k_sca
     RCCHK(launch_finalize(f, (unsigned)n, st));
     // (stage 1 left this pass's limbs, t and b in the handle's scratch)
     hipLaunchKernelGGL(sq8_cert_kernel, dim3((unsigned)n), dim3(128), 0, st, Qc, h->du, h->dk, h->dpad, h->centre, h->scale, h->ref_e,
-                       h->ref_a, h->qhi.p, h->qlo.p, h->qt.p, h->qb.p, h->rnv.p, h->rcut.p, out_s + q0 * k, k, k_scan, out_cert + q0,
+                       h->ref_a, h->qhi.p, h->qlo.p, h->qt.p, h->qb.p, h->rnv.p, h->rcut.p, out_s + q0 * k, k, k_scan, h->pq_residual ? 254.0 : 127.0,
+                       out_cert + q0,
                        out_bound ? out_bound + q0 : nullptr);
     RCCHK(check_launch("sq8 certificate"));
   }
@@ -269,8 +271,10 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
   const int nb = (int)std::min<int64_t>(1024, (n_src + 255) / 256);
   int* flag = nullptr; float* vec = nullptr; double* e = nullptr; double* a = nullptr; double* part = nullptr;
   int8_t* decoded = nullptr;   // a PQ handle: its decoded code matrix, a transient Np * dpad bytes
+  int16_t* decoded16 = nullptr;   // (a residual one: int16, twice that)
   auto work = [&]() -> int {
-    if (!h->codes) RCCHK(pq_decode_all(h, &decoded, st));
+    if (h->pq_residual) RCCHK(pq_decode_all16(h, &decoded16, st));
+    else if (!h->codes) RCCHK(pq_decode_all(h, &decoded, st));
     const int8_t* codes = h->codes ? h->codes : decoded;
     HIPCHK(hipMalloc((void**)&flag, sizeof(int)));
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), st));
@@ -286,13 +290,14 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
     HIPCHK(hipMalloc((void**)&part, sizeof(double) * (size_t)nb * 2 * dk));
     const int64_t nthr = n_src * (dk / 4);
     hipLaunchKernelGGL(sq8_scatter_rows_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, src->X, h->row_ids, n_src, dk, vec);
-    sq8_launch_ranges(false, src->X, codes, h->row_ids, n_src, dk, h->dpad, h->centre, h->scale, part, nb, e, a, st);
+    if (decoded16) sq8_launch_ranges(false, src->X, decoded16, h->row_ids, n_src, dk, h->dpad, h->centre, h->scale, part, nb, e, a, st);
+    else sq8_launch_ranges(false, src->X, codes, h->row_ids, n_src, dk, h->dpad, h->centre, h->scale, part, nb, e, a, st);
     RCCHK(check_launch("sq8 attach vectors"));
     HIPCHK(hipStreamSynchronize(st));   // the source may be dropped as soon as the call returns
     return RIHIP_OK;
   };
   const int rc = work();
-  hipFree(flag); hipFree(part); hipFree(decoded);
+  hipFree(flag); hipFree(part); hipFree(decoded); hipFree(decoded16);
   if (rc) { hipFree(vec); hipFree(e); hipFree(a); return rc; }   // the handle is as it was
   sq8_drop_vectors(h);
   h->vec = vec; h->ref_e = e; h->ref_a = a;
@@ -301,12 +306,24 @@ int sq8_attach(Sq8Index* h, const IpIndex* src, hipStream_t st) {
 
 }  // namespace
 
+namespace {
+template <typename CT>
+void launch_ranges(bool by_row, const float* X, const CT* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
+                   const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st) {
+  if (by_row) hipLaunchKernelGGL((sq8_range_part_kernel<true, CT>), dim3(nb), dim3(256), 0, st, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part);
+  else hipLaunchKernelGGL((sq8_range_part_kernel<false, CT>), dim3(nb), dim3(256), 0, st, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part);
+  hipLaunchKernelGGL(sq8_range_final_kernel, dim3(dk), dim3(256), 0, st, part, nb, dk, e_out, a_out);
+}
+}  // namespace
+
 namespace rihip_index {
 void sq8_launch_ranges(bool by_row, const float* X, const int8_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
                        const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st) {
-  if (by_row) hipLaunchKernelGGL(sq8_range_part_kernel<true>, dim3(nb), dim3(256), 0, st, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part);
-  else hipLaunchKernelGGL(sq8_range_part_kernel<false>, dim3(nb), dim3(256), 0, st, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part);
-  hipLaunchKernelGGL(sq8_range_final_kernel, dim3(dk), dim3(256), 0, st, part, nb, dk, e_out, a_out);
+  launch_ranges(by_row, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part, nb, e_out, a_out, st);
+}
+void sq8_launch_ranges(bool by_row, const float* X, const int16_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
+                       const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st) {
+  launch_ranges(by_row, X, codes, row_ids, n_rows, dk, dpad, centre, scale, part, nb, e_out, a_out, st);
 }
 }  // namespace rihip_index
 

@@ -27,6 +27,8 @@ struct Sq8LmArgs {
   const int* xrow;
   // product-quantised source (the PQ instantiations): codes is then the [Np, DP / PQ] matrix of entry numbers
   const int8_t* pq_book;     // [DP / PQ, 256, PQ]
+  // residual PQ (the residual instantiations): T of every (query, probed list) pair, indexed as list_q names a pair
+  const int* pair_t;         // [nq * nprobe]
 };
 
 __device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
@@ -35,7 +37,7 @@ __device__ __forceinline__ uint64_t sq8_key(int S, uint32_t row) {
 __device__ __forceinline__ int sq8_score_of_word(uint32_t hw) { return (int)(hw ^ 0x80000000u); }
 
 // sq8_scan_lm_kernel<dpad, fm, pq_dsub> over `grid` workgroups of 256: dpad 64 / 128, fm an FM_* of search_keys.h,
-// pq_dsub 0 (the int8 matrix) / 8 / 16 (entry numbers and codebooks)
-void sq8_launch_scan(int dpad, int fm, int pq_dsub, dim3 grid, hipStream_t st, const Sq8LmArgs& x);
+// pq_dsub 0 (the int8 matrix) / 8 / 16 (entry numbers and codebooks); residual (pq_dsub != 0 only): scores carry pair_t
+void sq8_launch_scan(int dpad, int fm, int pq_dsub, bool residual, dim3 grid, hipStream_t st, const Sq8LmArgs& x);
 
 }  // namespace rihip_index

@@ -1,5 +1,5 @@
 // The list-major int8 MFMA scan of the 8-bit index: sq8_scan_lm_kernel and its launcher.  The only unit that instantiates
-// the kernel (2 widths x 4 filter modes x 3 sources); sq8.hip drives it.
+// the kernel (2 widths x 4 filter modes x 3 sources, and the two PQ sources once more with residual scores); sq8.hip drives it.
 #pragma clang fp contract(off)   // as every unit of the 8-bit index (sq8_index.h)
 #include "common.h"
 
@@ -38,8 +38,13 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 // 16-byte read).  An entry lies in LDS in column order, so the lane holds the bytes the int8 matrix of the decoded rows
 // would have given it, in the same order: the B side does not change.  A row beyond its list's length decodes to entry 0
 // of every sub-space, not to zeros; n_ok keeps it out of every emission, as before.
-template <int DP, int FM = FM_NONE, int PQ = 0>
+//
+// RES (PQ instantiations only): the codebooks hold residuals against the list's centroid code K_l, so a row's score is
+// T[q, l] + the gathered dot product.  The work item is one list and its lane one query: the lane loads its pair's T once,
+// next to thr, and adds it wherever a score is formed.  Nothing else changes; with RES false the term is compiled out.
+template <int DP, int FM = FM_NONE, int PQ = 0, bool RES = false>
 __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
+  static_assert(!RES || PQ != 0, "residual scores exist on product-quantised storage only");
   constexpr bool FILT = FM == FM_TAGS || FM == FM_TAGS_MASK, XM = FM == FM_TAGS_MASK || FM == FM_MASK;
   constexpr int KS = DP / 32;
   constexpr int CW = PQ ? DP / PQ / 4 : 1;   // 32-bit words of entry numbers per row
@@ -83,6 +88,8 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     bl[ks] = *reinterpret_cast<const i32x4*>(a.qlo + (size_t)q * DP + ks * 32 + 16 * hh);
   }
   const int thr = a.thr ? sq8_score_of_word(f2ord(a.thr[q])) : (int)0x80000000;
+  int pt = 0;
+  if constexpr (RES) pt = a.pair_t[pair];
   uint64_t* my_cand = a.cand + (size_t)q * a.cap;
   uint64_t* my_dense = a.dense_cap > 0 ? a.cand + (size_t)pair * a.dense_cap : nullptr;
   const int64_t i0 = (int64_t)split * tpi;
@@ -141,6 +148,10 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
     if constexpr (XM) ok = ok && !((mw >> acc_row(r, lane)) & 1u);
     return ok;
   };
+  auto score = [&](int sh, int sl) -> int {
+    if constexpr (RES) return sh * 256 + sl + pt;
+    else return sh * 256 + sl;
+  };
   if constexpr (PQ != 0) load_words(i0, cw);
   else load_tile(i0, av);
 #pragma unroll 1
@@ -171,20 +182,20 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
           const int rr = acc_row(r, lane);
           const int64_t sl = i * TRS + rr;
           if (sl < a.dense_cap)
-            my_dense[sl] = (rr < n_ok && row_ok(r)) ? sq8_key(ah[r] * 256 + al[r], a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
+            my_dense[sl] = (rr < n_ok && row_ok(r)) ? sq8_key(score(ah[r], al[r]), a.dense_ids ? (uint32_t)a.row_ids[p0 + t_row0 + rr] : 0u) : 0ull;
         }
       } else {
         unsigned hits = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (acc_row(r, lane) < n_ok && ah[r] * 256 + al[r] >= thr && row_ok(r)) hits |= (1u << r);
+          if (acc_row(r, lane) < n_ok && score(ah[r], al[r]) >= thr && row_ok(r)) hits |= (1u << r);
         if (hits) {
           int pos = atomicAdd(&a.count[q * a.count_stride], __popc(hits));
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             if (hits & (1u << r)) {
               const int64_t v = p0 + t_row0 + acc_row(r, lane);
-              if (pos < a.cap) my_cand[pos] = sq8_key(ah[r] * 256 + al[r], (uint32_t)a.row_ids[v]);
+              if (pos < a.cap) my_cand[pos] = sq8_key(score(ah[r], al[r]), (uint32_t)a.row_ids[v]);
               ++pos;
             }
           }
@@ -212,9 +223,16 @@ __global__ __launch_bounds__(256, 2) void sq8_scan_lm_kernel(Sq8LmArgs a) {
 
 namespace rihip_index {
 
-void sq8_launch_scan(int dpad, int fm, int pq_dsub, dim3 grid, hipStream_t st, const Sq8LmArgs& x) {
+void sq8_launch_scan(int dpad, int fm, int pq_dsub, bool residual, dim3 grid, hipStream_t st, const Sq8LmArgs& x) {
   auto go = [&](auto FMv, auto PQv) {
     constexpr int FM = decltype(FMv)::value, PQ = decltype(PQv)::value;
+    if constexpr (PQ != 0) {
+      if (residual) {
+        if (dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM, PQ, true>), grid, dim3(256), 0, st, x);
+        else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM, PQ, true>), grid, dim3(256), 0, st, x);
+        return;
+      }
+    }
     if (dpad == 64) hipLaunchKernelGGL((sq8_scan_lm_kernel<64, FM, PQ>), grid, dim3(256), 0, st, x);
     else hipLaunchKernelGGL((sq8_scan_lm_kernel<128, FM, PQ>), grid, dim3(256), 0, st, x);
   };

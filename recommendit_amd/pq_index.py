@@ -9,8 +9,15 @@ SQ8Index -- ``mode=``, ``item_filter=``, ``exclude=`` on both ``exclusion=`` rou
 ``search_certified``, serving through GpuRecommendationPipeline -- returns what that SQ8Index would return, integer
 scores included, and ``codes()`` / ``reconstruct()`` return the decoded matrix those scores are stated over.
 
-Deviations from faiss: an own quantiser over SQ8 codes with int8 codebooks, no residual encoding
-against the IVF centroids (one integer score per row, comparable across lists), no faiss PQ file interop.
+Deviations from faiss: an own quantiser over SQ8 codes with int8 codebooks, residual encoding
+against the IVF centroids only on request, no faiss PQ file interop.
+
+``from_index(..., by_residual=True)`` (opt-in; an IVF source): the codebooks quantise each row's SQ8 code minus its
+list's centroid snapped to the same SQ8 grid (``list_codes()``).  The decoded code is then list code + entry, an int16 in
+[-254, 254] (``codes()`` returns int16), and the score splits into a per-(query, list) integer and the gathered dot
+product the scan already forms, so every search keeps its exact integer contract over that int16 matrix.  The
+certificate of a refined search uses 254 where it uses 127 otherwise.  A residual index has a file format of its own;
+``save`` writes it and ``load`` picks the reader by the file's first bytes.
 
 ``codes()``, ``reconstruct()`` and ``attach_vectors()`` decode the whole index on the device: a transient
 N * dpad bytes.  ``save`` / ``load`` are SQ8Index's on the PQ file format (``_SAVE`` / ``_LOAD``); each loader refuses the
@@ -42,13 +49,18 @@ class PQIndex(SQ8Index):
     @classmethod
     def from_index(cls, faiss_index: FAISSIndex, dsub: int = 8, n_iter: int = 10,
                    ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None, codebooks: Optional[np.ndarray] = None,
-                   keep_vectors: bool = False) -> "PQIndex":
+                   keep_vectors: bool = False, by_residual: bool = False) -> "PQIndex":
         """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  dsub: 8 or 16
         dimensions per sub-space; n_iter: Lloyd steps of the codebook training; ranges: (centre, scale) of the SQ8 stage,
         as SQ8Index.from_index; codebooks: int8 [M, 256, dsub] with M = dpad / dsub (dpad = 64 up to 64 dimensions, else
         128), entries in [-127, 127] -- injected codebooks skip the training, as ranges= skips the range pass.
-        keep_vectors / item tags: as SQ8Index.from_index."""
+        keep_vectors / item tags: as SQ8Index.from_index.  by_residual=True: quantise the residuals against the IVF
+        centroids (the module text above); injected codebooks are then residual codebooks.  ValueError on a flat source."""
         _check_source("PQIndex", faiss_index)
+        if not isinstance(by_residual, (bool, np.bool_)):
+            raise ValueError(f"PQIndex: by_residual={by_residual!r} must be True or False")
+        if by_residual and not faiss_index.index.is_ivf:
+            raise ValueError("PQIndex: by_residual=True needs an IVF index (a flat index has one list and no centroids)")
         if dsub not in (8, 16):
             raise ValueError(f"PQIndex: dsub={dsub!r} (8 or 16)")
         if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= int(n_iter) <= 1000:
@@ -65,10 +77,10 @@ class PQIndex(SQ8Index):
                 raise ValueError("PQIndex: codebook entries lie in [-127, 127]")
             book = np.ascontiguousarray(book)
         h = C.c_void_p()
-        L.check(L.lib().rihip_pq_index_from_ip_index(faiss_index.index._h, None if m is None else m.ctypes.data,
-                                                     None if s is None else s.ctypes.data, int(dsub), int(n_iter),
-                                                     None if book is None else book.ctypes.data, C.byref(h), L.stream_ptr()),
-                "pq_index_from_ip_index")
+        L.check(L.lib().rihip_pq_index_from_ip_index_residual(
+            faiss_index.index._h, None if m is None else m.ctypes.data, None if s is None else s.ctypes.data, int(dsub),
+            int(n_iter), None if book is None else book.ctypes.data, int(bool(by_residual)), C.byref(h), L.stream_ptr()),
+            "pq_index_from_ip_index")
         return cls._adopt(h.value, faiss_index, keep_vectors)
 
     # -- no live updates ------------------------------------------------------------------------------------------
@@ -94,6 +106,20 @@ class PQIndex(SQ8Index):
     def dsub(self) -> int:
         return self._dims()[0]
 
+    @property
+    def by_residual(self) -> bool:
+        """whether the codebooks quantise residuals against the IVF centroids"""
+        return self.index is not None and bool(L.lib().rihip_pq_index_is_residual(self.index._h))
+
+    def list_codes(self) -> np.ndarray:
+        """int8 [n_lists, dpad]: every list's centroid on the SQ8 grid, padding columns 0 (a residual index only)"""
+        h = self._built()
+        if not self.by_residual:
+            raise RuntimeError("PQIndex.list_codes: not a residual index (from_index(by_residual=True))")
+        out = np.empty((h.nlist, 64 if self.embed_dim <= 64 else 128), dtype=np.int8)
+        L.check(L.lib().rihip_pq_index_get_list_codes(h._h, out.ctypes.data), "pq_index_get_list_codes")
+        return out
+
     def pq_codes(self) -> np.ndarray:
         """uint8 [N, M]: the stored entry numbers in insertion order"""
         h = self._built()
@@ -112,24 +138,41 @@ class PQIndex(SQ8Index):
     def train_stats(self) -> Dict:
         """distortion: int64 [passes], the summed smallest distance of every assignment pass of the build (n_iter + 1
         values; one with injected codebooks; none after load); peak_bytes: device bytes at the build's peak, the
-        transient SQ8 codes included; *_ms: host time of the build's stages"""
+        transient SQ8 codes included; *_ms: host time of the build's stages; by_residual and residual_clamped: the
+        residual values of the build that left [-127, 127] and were clamped (0 after load and on a plain index)"""
         h = self._built()
         n = C.c_int(0)
         peak = L.c_i64(0)
         ms = (C.c_double * 3)()
         trace = (L.c_i64 * 1001)()
         L.check(L.lib().rihip_pq_index_train_stats(h._h, trace, 1001, C.byref(n), C.byref(peak), ms), "pq_index_train_stats")
+        clamped = L.c_i64(0)
+        L.check(L.lib().rihip_pq_index_residual_clamped(h._h, C.byref(clamped)), "pq_index_residual_clamped")
         return {"distortion": np.array(trace[:n.value], dtype=np.int64), "peak_bytes": int(peak.value),
-                "range_encode_ms": float(ms[0]), "train_ms": float(ms[1]), "assign_ms": float(ms[2])}
+                "range_encode_ms": float(ms[0]), "train_ms": float(ms[1]), "assign_ms": float(ms[2]),
+                "by_residual": self.by_residual, "residual_clamped": int(clamped.value)}
 
     def codes(self) -> np.ndarray:
         """int8 [N, embed_dim]: the DECODED codes (codebook entries) in insertion order -- the matrix the search contract
-        is stated over.  Decodes the whole index on the device: a transient N * dpad bytes."""
-        return super().codes()
+        is stated over.  Decodes the whole index on the device: a transient N * dpad bytes.  A residual index returns
+        int16 [N, embed_dim]: list code + entry, in [-254, 254] (a transient 2 * N * dpad bytes)."""
+        if not self.by_residual:
+            return super().codes()
+        h = self._built()
+        c = np.empty((h.ntotal, self.embed_dim), dtype=np.int16)
+        L.check(L.lib().rihip_pq_index_get_decoded16(h._h, c.ctypes.data), "pq_index_get_decoded16")
+        return c
 
     def reconstruct(self) -> np.ndarray:
         """f32 [N, embed_dim]: centre + scale * decoded code in insertion order (a transient N * dpad bytes on the device)"""
         return super().reconstruct()
+
+    # -- persistence ------------------------------------------------------------------------------------------------
+    @classmethod
+    def _loader(cls, load_path) -> str:
+        """the reader of the file's format: a residual index is saved under a magic of its own"""
+        with open(load_path, "rb") as f:
+            return "rihip_pq_index_load_residual" if f.read(8) == b"RIHIPPR1" else cls._LOAD
 
     # -- utilities --------------------------------------------------------------------------------------------------
     def stats(self) -> Dict:
@@ -139,5 +182,6 @@ class PQIndex(SQ8Index):
         dsub, m = self._dims()
         f32_row = 4 * (32 if self.embed_dim <= 32 else (64 if self.embed_dim <= 64 else 128))
         st.update({"bytes_per_vector": m, "compression": f32_row / m, "dsub": dsub, "n_subspaces": m,
-                   "codebook_bytes": m * 256 * dsub, "peak_build_bytes": self.train_stats()["peak_bytes"]})
+                   "codebook_bytes": m * 256 * dsub, "peak_build_bytes": self.train_stats()["peak_bytes"],
+                   "by_residual": self.by_residual})
         return st

@@ -771,6 +771,11 @@ class SQ8Index(ExcludingSearch):
         logger.info("Saved %s index to %s", self._KIND, save_path)
 
     @classmethod
+    def _loader(cls, load_path) -> str:
+        """the C entry point that reads the file (PQIndex picks between its two formats)"""
+        return cls._LOAD
+
+    @classmethod
     def load(cls, path: str) -> "SQ8Index":
         load_path = Path(path)
         if not load_path.exists():
@@ -779,7 +784,8 @@ class SQ8Index(ExcludingSearch):
             meta = pickle.load(f)  # sidecar written by save() above
         obj = cls(embed_dim=meta["embed_dim"], n_lists=meta["n_lists"], n_probe=meta["n_probe"])
         h = C.c_void_p()
-        L.check(getattr(L.lib(), cls._LOAD)(str(load_path).encode(), C.byref(h)), cls._LOAD[6:])
+        loader = cls._loader(load_path)
+        L.check(getattr(L.lib(), loader)(str(load_path).encode(), C.byref(h)), loader[6:])
         obj.index = _SQ8Handle(h.value, obj)
         obj.index.nprobe = meta["n_probe"]
         obj.item_ids = np.asarray(meta["item_ids"], dtype=np.int64)

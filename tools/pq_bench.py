@@ -16,7 +16,17 @@ kernel times of a kernel trace of one run per corpus (--gather-corpus random / s
 Embeddings leg: recall on the item embeddings of a short ml1m_like() training run (3 883 items, d = 64, exact index,
 queries = the user embeddings).  Recall is from one run and unpinned.
 
-python tools/pq_bench.py [--legs serve,flat,gather,embeddings] [--reps 20] [--warmup 3] [--n 1000000] [--iters 10]
+Residual legs (by_residual=True, the codebooks quantise the rows' codes minus their list's centroid code): every leg over
+an IVF index also builds and searches the residual PQ index of each dsub next to the plain one, in the same run, under
+the keys pqr8_ / pqr16_ (the kernel that fills T, sq8_pair_offset_kernel, is read from a kernel trace of such a run: HIP
+events around a whole search cannot separate it).  serve4096 is
+the serve leg at 4 096 queries; clustered is the serve leg over a clustered corpus (--n unit rows around 100 centres,
+lists trained on it); the embeddings leg adds an IVF index of the same embeddings (16 lists, all probed, so recall
+measures the codes and not the probing) with the plain and the residual PQ index over it.  --no-residual leaves the
+residual legs out (the plain legs then run exactly as before).
+
+python tools/pq_bench.py [--legs serve,serve4096,clustered,flat,gather,embeddings] [--reps 20] [--warmup 3] [--n 1000000]
+                         [--iters 10] [--no-residual]
 """
 import argparse
 import json
@@ -41,6 +51,8 @@ ap.add_argument("--n", type=int, default=1_000_000)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--epochs", type=int, default=2)
 ap.add_argument("--modes", default="auto,dense,thresholded")
+ap.add_argument("--no-residual", action="store_true", help="leave the by_residual legs out")
+ap.add_argument("--spread", type=float, default=0.25, help="clustered corpus: noise around a centre, relative to its norm")
 ap.add_argument("--gather-corpus", default="both", choices=["both", "random", "same"],
                 help="gather leg: one corpus only, so that a kernel trace of the run holds one kind of scan")
 args = ap.parse_args()
@@ -92,10 +104,10 @@ def quality(idx, q, ref, k, row, pre):
             row[f"{pre}refine{f}_certified"] = float(cert.float().mean().item())
 
 
-def build_pq(f32, dsub, row, pre, keep=True):
+def build_pq(f32, dsub, row, pre, keep=True, by_residual=False):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    pq = PQIndex.from_index(f32, dsub=dsub, n_iter=args.iters, keep_vectors=False)
+    pq = PQIndex.from_index(f32, dsub=dsub, n_iter=args.iters, keep_vectors=False, by_residual=by_residual)
     torch.cuda.synchronize()
     row[f"{pre}build_ms"] = (time.perf_counter() - t0) * 1e3
     ts, st = pq.train_stats(), pq.stats()
@@ -106,13 +118,18 @@ def build_pq(f32, dsub, row, pre, keep=True):
     row[f"{pre}peak_build_bytes"] = ts["peak_bytes"]
     row[f"{pre}bytes_per_vector"] = st["bytes_per_vector"]
     row[f"{pre}distortion_first_last"] = [int(ts["distortion"][0]), int(ts["distortion"][-1])]
+    if by_residual:
+        row[f"{pre}residual_clamped"] = ts["residual_clamped"]
     if keep:
         pq.attach_vectors(f32)
     return pq
 
 
-def leg(name, f32, nq, d):
+def leg(name, f32, nq, d, queries=None):
     q = unit(nq, d)
+    if queries is not None:   # around the given points instead of uniform on the sphere
+        q = queries(nq) + (args.spread / d ** 0.5) * torch.randn((nq, d), device=dev, generator=g)
+        q = (q / q.norm(dim=1, keepdim=True)).contiguous()
     k = min(K, f32.index.ntotal)
     row = {"f32_ms": timed(lambda: f32.batch_search_device(q, k=k, normalized=True))}
     _, ref = f32.batch_search_device(q, k=k, normalized=True)
@@ -122,9 +139,10 @@ def leg(name, f32, nq, d):
     quality(sq, q, ref, k, row, "sq8_")
     sq.drop_vectors()
     del sq
-    for dsub in (8, 16):
-        pre = f"pq{dsub}_"
-        pq = build_pq(f32, dsub, row, pre)
+    residual = bool(f32.index.is_ivf) and not args.no_residual
+    for dsub, by_res in [(d_, r_) for d_ in (8, 16) for r_ in ((False, True) if residual else (False,))]:
+        pre = f"pqr{dsub}_" if by_res else f"pq{dsub}_"
+        pq = build_pq(f32, dsub, row, pre, by_residual=by_res)
         for mode in filter(None, args.modes.split(",")):
             n0, r0 = pq.search_stats()
             row[f"{pre}{mode}_ms"] = timed(lambda: pq.batch_search_device(q, k=k, normalized=True, mode=mode))
@@ -191,6 +209,15 @@ def embeddings_leg():
     for dsub in (8, 16):
         pq = build_pq(f32, dsub, {}, "")
         quality(pq, q, ref, k, row, f"pq{dsub}_")
+    if not args.no_residual:
+        ivf = FAISSIndex(embed_dim=E.shape[1], n_lists=16, n_probe=16)
+        ivf.build_ivf_index(E, item_ids.tolist())
+        _, ref_ivf = ivf.batch_search_device(q, k=k, normalized=True)
+        row["ivf16_f32_recall@10_of_exact"] = recall(ref, ref_ivf, 10)
+        for dsub in (8, 16):
+            for by_res in (False, True):
+                pq = build_pq(ivf, dsub, {}, "", by_residual=by_res)
+                quality(pq, q, ref, k, row, f"ivf16_pq{'r' if by_res else ''}{dsub}_")
     out["ml1m_like item embeddings"] = row
     show("ml1m_like item embeddings", row)
 
@@ -201,6 +228,22 @@ for which in filter(None, args.legs.split(",")):
         idx.build_from_device(unit(args.n, 128), np.arange(1, args.n + 1))
         leg("serve ivf100/10 nq=256", idx, 256, 128)
         del idx
+    elif which == "serve4096":
+        idx = FAISSIndex(embed_dim=128, n_lists=100, n_probe=10)
+        idx.build_from_device(unit(args.n, 128), np.arange(1, args.n + 1))
+        leg("serve ivf100/10 nq=4096", idx, 4096, 128)
+        del idx
+    elif which == "clustered":
+        cen = unit(100, 128)
+        x = cen[torch.randint(0, 100, (args.n,), device=dev, generator=g)] + (args.spread / 128 ** 0.5) * torch.randn(
+            (args.n, 128), device=dev, generator=g)
+        x = (x / x.norm(dim=1, keepdim=True)).contiguous()
+        idx = FAISSIndex(embed_dim=128, n_lists=100, n_probe=10)
+        idx.build_from_device(x, np.arange(1, args.n + 1))
+        # queries: corpus-like points (fresh noise around the same centres)
+        for nq in (256, 4096):
+            leg(f"clustered ivf100/10 nq={nq}", idx, nq, 128, queries=lambda n: cen[torch.randint(0, 100, (n,), device=dev, generator=g)])
+        del idx, x
     elif which == "flat":
         idx = FAISSIndex(embed_dim=128, exact=True)
         idx.build_from_device(unit(args.n, 128), np.arange(1, args.n + 1))
