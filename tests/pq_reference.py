@@ -88,3 +88,44 @@ def decode(codes, book):
     for m in range(M):
         out[:, m * dsub:(m + 1) * dsub] = book[m][codes[:, m]]
     return out
+
+
+# ---- additions for tests/test_gpu_pq_paths.py: a faster exact trainer and the Lloyd step's sums ---------------------------
+def assign_blas(c, book):
+    """assign() through float64 matmuls: D = |c|^2 + |b|^2 - 2 <c, b>, every term an integer below 2^22, so each D is the
+    same integer in any summation order; the first of equal minima, as assign()"""
+    N = c.shape[0]
+    M, _, dsub = book.shape
+    codes = np.empty((N, M), dtype=np.uint8)
+    total = 0
+    rows = np.arange(N)
+    for m in range(M):
+        sub = c[:, m * dsub:(m + 1) * dsub].astype(np.float64)
+        b = book[m].astype(np.float64)
+        D = (sub * sub).sum(axis=1)[:, None] + (b * b).sum(axis=1)[None, :] - 2.0 * (sub @ b.T)
+        assert (D == np.rint(D)).all() and D.min() >= 0
+        e = np.argmin(D, axis=1)
+        codes[:, m] = e
+        total += int(D[rows, e].astype(np.int64).sum())
+    return codes, total
+
+
+def train_blas(c, dsub, n_iter):
+    """train() with assign_blas in place of assign: the same three results"""
+    book = init_book(c, dsub)
+    trace = []
+    for _ in range(n_iter):
+        codes, dist = assign_blas(c, book)
+        trace.append(dist)
+        book = lloyd_step(c, codes, book)
+    codes, dist = assign_blas(c, book)
+    trace.append(dist)
+    return book, codes, np.array(trace, dtype=np.int64)
+
+
+def entry_sums(c, codes, m, dsub):
+    """(sum int64 [256, dsub], cnt int64 [256]) of sub-space m over the rows given: what lloyd_step divides (all rows), or
+    the partial sums of one block of rows"""
+    s = np.zeros((ENTRIES, dsub), dtype=np.int64)
+    np.add.at(s, codes[:, m].astype(np.int64), c[:, m * dsub:(m + 1) * dsub].astype(np.int64))
+    return s, np.bincount(codes[:, m], minlength=ENTRIES).astype(np.int64)
