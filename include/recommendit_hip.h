@@ -840,7 +840,8 @@ int rihip_sq8_update_stats(void* handle, int64_t* out);     /* out: int64[4] */
  * Every rihip_sq8_* search, filter, exclude, refine, stats and id-map call takes the handle and returns what it returns
  * on the SQ8 index whose code matrix is the decoded one; rihip_sq8_index_get_codes / _reconstruct return that decoded
  * matrix (a transient N * dpad bytes on the device, as rihip_sq8_refine_attach_vectors takes for e_j / a_j).
- * rihip_sq8_update_apply returns RIHIP_ERR_STATE and changes nothing; rihip_sq8_index_save refuses the handle.
+ * rihip_sq8_update_apply returns RIHIP_ERR_STATE and changes nothing (rihip_pq_update_apply below updates the handle under
+ * frozen codebooks); rihip_sq8_index_save refuses the handle.
  * get_codes: host uint8 [N,M] in original row order; get_codebooks: host int8 [M,256,dsub]; dims: dsub and M.
  * train_stats: trace (up to cap values; *n_trace = how many the build recorded: n_iter + 1, 1 with injected codebooks, 0
  * after load), peak_bytes, ms[3] = host time of {range pass + SQ8 encode, training, final assignment}; any may be NULL.
@@ -883,7 +884,7 @@ int rihip_pq_index_load(const char* path, void** handle);          /* host path;
  *      proof reads as before: the integer score is within E2 / t of the decoded row's product with q because each of the d
  *      terms |q_j s_j - t n_j| is multiplied by a code of magnitude at most 254, and W bounds |t S| the same way.
  *   7. rihip_sq8_index_get_codes (int8) returns RIHIP_ERR_STATE on a residual handle; get_decoded16 returns the decoded
- *      matrix, host int16 [N, d] in original row order.  rihip_sq8_index_reconstruct works.  Live updates stay refused.
+ *      matrix, host int16 [N, d] in original row order.  rihip_sq8_index_reconstruct works.  Live updates: rihip_pq_update_apply below.
  * is_residual: 1 / 0.  get_list_codes: host int8 [nlist, dpad].  residual_clamped: the count of step 2 (0 after load, and
  * on a handle that is not residual).
  * save: rihip_pq_index_save writes a residual handle in a format of its own: "RIHIPPR1", the PQ header with a third
@@ -896,6 +897,35 @@ int rihip_pq_index_get_list_codes(void* handle, int8_t* out);      /* synchronou
 int rihip_pq_index_get_decoded16(void* handle, int16_t* out);      /* synchronous */
 int rihip_pq_index_residual_clamped(void* handle, int64_t* out);
 int rihip_pq_index_load_residual(const char* path, void** handle); /* host path; synchronous */
+
+/* ---- Product-quantised index: add / remove / replace items under frozen codebooks (faiss IndexIVFPQ::add after train) --
+ * What rihip_sq8_update_apply is to the SQ8 handle, for a handle with PQ storage (plain or residual, flat or IVF, dsub 8
+ * or 16).  rihip_sq8_update_apply itself keeps refusing such a handle; the caller chooses this entry point knowingly,
+ * because nothing is retrained: the centroids, the SQ8 quantiser (m, s), the list codes K_l and the codebooks stay as
+ * they are.  ONE repack of the entry-number matrix; a kept row keeps its M bytes, a new row x in list l (its arg-max
+ * list, lowest on ties; the one list of a flat-built handle) gets
+ *   c[j] = clamp(rintf((x_j - m_j) / s_j), -127, 127) for j < d, 0 in the padding columns,
+ *   on a residual handle r[j] = clamp((int)c[j] - (int)K_l[j], -127, 127) in place of c (each clamp counted),
+ *   byte[m] = the e of the smallest D = sum_j (c[m dsub + j] - book[m][e][j])^2 (i32), the lowest e on a tie.
+ * Parameters, outputs, checks, *bad_kind codes and refusal texts are those of rihip_sq8_update_apply; *n_clamped is the
+ * SQ8-grid clamp count of this call (the same integer).  The handle is left bit for bit in the state that
+ *   rihip_pq_index_from_ip_index_residual(ip, m, s, dsub, any n_iter, the handle's own codebooks, by_residual as the
+ *   handle) with ip an f32 index of the final corpus (same centroids, kept rows in their lists, new rows in theirs),
+ *   rihip_sq8_filter_set_tags of the final tag words, if the handle had tags, and
+ *   rihip_sq8_refine_attach_vectors(ip), if the handle had vectors
+ * would leave it in: entry numbers, row ids, list offsets and lengths, tags, vectors, e_j / a_j; saved files are byte
+ * for byte the same ("RIHIPPQ1" / "RIHIPPR1" unchanged).  With vectors the new state is decoded transiently (N' * dpad
+ * bytes, twice that on a residual handle) for e_j / a_j.  A refused or failed call leaves the handle searchable exactly
+ * as it was; the generation advances only on a real change.  RIHIP_ERR_STATE on a handle without PQ storage.
+ * stats: {updates applied, rows dropped, rows added, SQ8 code values clamped, residual values clamped, the summed smallest
+ * D over all added rows and sub-spaces} cumulative since the handle was made, then the last two of the last update that
+ * changed the index.  distortion_added / rows added against the build's last trace value / N is the drift signal of
+ * frozen codebooks.  rihip_sq8_update_assign and rihip_sq8_update_stats take the handle as before. */
+int rihip_pq_update_apply(void* handle, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                          const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add,
+                          int64_t* item_ids_out, int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped,
+                          int64_t* bad_id, int* bad_kind, void* stream);
+int rihip_pq_update_stats(void* handle, int64_t* out);      /* out: int64[8] */
 
 /* ---- LambdaMART forward --------------------------------------------------------------------
  * Replaces lgb.Booster(model_file=...) (src/models/ranker.py:219) and Booster.predict

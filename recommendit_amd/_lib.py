@@ -194,6 +194,9 @@ SIGNATURES = {
     "rihip_pq_index_get_decoded16": (C.c_int, [vp, vp]),
     "rihip_pq_index_residual_clamped": (C.c_int, [vp, C.POINTER(c_i64)]),
     "rihip_pq_index_load_residual": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
+    "rihip_pq_update_apply": (C.c_int, [vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp, C.POINTER(c_i64), C.POINTER(c_i64),
+                                        C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_int), vp]),
+    "rihip_pq_update_stats": (C.c_int, [vp, vp]),
     "rihip_gbdt_load_text": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rihip_gbdt_create_from_text": (C.c_int, [C.c_char_p, c_i64, C.POINTER(vp)]),
     "rihip_gbdt_destroy": (C.c_int, [vp]),

@@ -1,9 +1,10 @@
 // Handle of the 8-bit scalar-quantised index, the one function that makes a code, and what its units call of each other:
 // sq8_build.hip (quantiser, build, handle lifetime, accessors), sq8_scan.hip (the int8 scan), sq8.hip (search driver; plain,
 // filtered and excluding search), sq8_refine.hip (attached f32 rows, refined search, certificate), sq8_state.hip (state
-// files), sq8_update.hip (add / remove / replace) and pq.hip (the product-quantised storage of the same handle: training,
-// encoding, decoding).  All seven compile with `#pragma clang fp contract(off)` at their top: the quantisers, the query
-// transform, the decode, the refine and the certificate are specified operation by operation.
+// files), sq8_update.hip (add / remove / replace), pq.hip (the product-quantised storage of the same handle: training,
+// encoding, decoding) and pq_update.hip (add / remove / replace on that storage).  All eight compile with `#pragma clang fp
+// contract(off)` at their top: the quantisers, the query transform, the decode, the refine and the certificate are
+// specified operation by operation.
 #pragma once
 #include "common.h"
 #include "ip_index.h"
@@ -57,6 +58,9 @@ struct Sq8Index {
   double* ref_a = nullptr;           // [dk] a_j = max_i |x_ij|
   // updates (rihip_sq8_update_apply): calls that changed the index, rows dropped, rows added, code values clamped
   int64_t upd_stats[4] = {0, 0, 0, 0};
+  // a PQ handle's updates (rihip_pq_update_apply) next to those: residual values of added rows clamped, the summed
+  // smallest D of added rows (both cumulative), and the two of the last update that changed the index
+  int64_t pq_upd_stats[4] = {0, 0, 0, 0};
   // scratch
   DevBuf<int8_t> qhi, qlo, fhi, flo;
   DevBuf<float> qt, qpad, fQ, coarse, thr;
@@ -125,6 +129,34 @@ void sq8_launch_ranges(bool by_row, const float* X, const int8_t* codes, const i
 // (the int16 decoded codes of a residual PQ handle)
 void sq8_launch_ranges(bool by_row, const float* X, const int16_t* codes, const int64_t* row_ids, int64_t n_rows, int dk, int dpad,
                        const float* centre, const float* scale, double* part, int nb, double* e_out, double* a_out, hipStream_t st);
+
+// ---- sq8_update.hip: everything of an update that does not depend on how the handle stores its codes -- argument and id
+// checks, masks, renumbering, the list of every new row, grouping, the one host read in the middle of the call, the new
+// offsets, row ids, tag words, attached vectors and the swap -- with the storage's own stages called where they belong.
+struct Sq8UpdateCtx {   // what the driver hands a stage; device pointers unless said otherwise
+  Sq8Index* h; hipStream_t st;
+  const float* X_add; const uint32_t* add_tags; int64_t n_add;    // new rows at width dk; tag words (null: 0, or untagged)
+  const int* keep; const int* rscan; const int* pscan;            // keep flag and new number of an old row; kept physical rows before p
+  const int* tile_list_old;                                       // list of every old granule
+  const int* g_rows; const int* g_keys; const int* g_off;         // new rows grouped by list: row, list, list bounds [nlist+1]
+  unsigned long long* words;                                      // the storage's own n_words counters, zero before `encode`
+  // from `repack` on: the new layout (row_ids_new / tags_new are written by the storage's repack kernel)
+  const unsigned long long* cnt_keep; const int64_t* poff_new; int64_t n_keep, Np_new;
+  int64_t* row_ids_new; uint32_t* tags_new;                       // tags_new: null on an untagged handle
+  const float* vec_new; double* part; int nb; double* e_new; double* a_new;   // `ranges`: the compacted f32 rows and where e_j / a_j go
+};
+struct Sq8UpdateStorage {   // one per call, on the caller's stack; its destructor frees what `swap` did not hand over
+  const char* who = "";     // leads every message
+  int n_words = 0;          // counters of its own that travel to the host with the checks
+  virtual int encode(const Sq8UpdateCtx&) { return RIHIP_OK; }   // before the host read (n_add > 0): work on the new rows that counts
+  virtual int repack(const Sq8UpdateCtx&) = 0;                   // allocate the new code storage, write every row of [0, Np_new) once
+  virtual int ranges(const Sq8UpdateCtx&) = 0;                   // e_j / a_j of the new state (a handle with vectors)
+  virtual void swap(Sq8Index* h, const unsigned long long* words_host) = 0;   // install the new codes, book the counters: cannot fail
+  virtual ~Sq8UpdateStorage() {}
+};
+int sq8_update_run(Sq8Index* h, Sq8UpdateStorage& s, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                   const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add, int64_t* item_ids_out,
+                   int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped, int64_t* bad_id, int* bad_kind, hipStream_t st);
 
 // ---- sq8_state.hip: one writer and one reader for the SQ8, the PQ and the residual PQ state file.  All are magic[8], n_hdr int64 header
 // words {version 1, du, dk, dpad, N, Np, nlist, nprobe, format's own ...}, centre f32[dpad], scale f32[dpad], centroids

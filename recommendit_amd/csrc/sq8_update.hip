@@ -20,6 +20,10 @@
 //              of a physical row through its row id), without atomics.
 // Flat handles (nlist == 1) take the same kernels.  The new arrays are built next to the old ones and swapped in at the
 // end (peak device memory = old + new); a call that is refused or fails leaves the old index searchable.
+//
+// Only the repack, the ranges' code matrix and the counters depend on how the handle stores its codes.  Everything else
+// is sq8_update_run below, which a PQ handle's update (pq_update.hip) runs as well with stages of its own
+// (Sq8UpdateStorage in sq8_index.h); Sq8Codes here is the int8 matrix's.
 #pragma clang fp contract(off)   // the quantiser is specified operation by operation: no fused multiply-add
 #include "common.h"
 #include "recommendit_hip.h"
@@ -135,41 +139,75 @@ __global__ __launch_bounds__(256) void sq8_update_repack_kernel(const Sq8RepackA
   }
 }
 
-struct Owned {   // everything the call must free on every way out
+struct Owned {   // everything the driver must free on every way out
   UpdateScratch s; Grouper g;
-  int8_t* codes = nullptr; int64_t* rid = nullptr; uint32_t* tags = nullptr; int64_t* poff = nullptr; int* len = nullptr;
+  int64_t* rid = nullptr; uint32_t* tags = nullptr; int64_t* poff = nullptr; int* len = nullptr;
   float* vec = nullptr; double* e = nullptr; double* a = nullptr; double* part = nullptr;
   ~Owned() {
     hipFree(s.base); g.release();
-    hipFree(codes); hipFree(rid); hipFree(tags); hipFree(poff); hipFree(len); hipFree(vec); hipFree(e); hipFree(a); hipFree(part);
+    hipFree(rid); hipFree(tags); hipFree(poff); hipFree(len); hipFree(vec); hipFree(e); hipFree(a); hipFree(part);
+  }
+};
+
+// the int8 code matrix: new rows are encoded inside the repack, the ranges read the new matrix as it is
+struct Sq8Codes : Sq8UpdateStorage {
+  int8_t* codes = nullptr;
+  Sq8Codes() { who = "sq8_update_apply"; }
+  ~Sq8Codes() override { hipFree(codes); }
+  int repack(const Sq8UpdateCtx& c) override {
+    const Sq8Index* h = c.h;
+    const int L = h->dpad / 16;
+    HIPCHK(hipMalloc((void**)&codes, (size_t)c.Np_new * h->dpad));
+    Sq8RepackArgs a;
+    a.codes_old = h->codes; a.row_ids_old = h->row_ids; a.tags_old = h->tags; a.tile_list_old = c.tile_list_old; a.poff_old = h->list_poff;
+    a.Np_old = h->Np; a.keep = c.keep; a.rscan = c.rscan; a.pscan = c.pscan;
+    a.X_add = c.X_add; a.add_tags = c.add_tags; a.g_rows = c.g_rows; a.g_keys = c.g_keys; a.g_off = c.g_off; a.n_add = c.n_add;
+    a.centre = h->centre; a.scale = h->scale; a.cnt_keep = c.cnt_keep; a.poff_new = c.poff_new;
+    a.codes_new = codes; a.row_ids_new = c.row_ids_new; a.tags_new = c.tags_new; a.n_keep = c.n_keep; a.nlist = h->nlist; a.dk = h->dk; a.lanes = L;
+    const int64_t tot = (h->Np + c.n_add + (int64_t)h->nlist * TR) * L;
+    hipLaunchKernelGGL(sq8_update_repack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.st, a);
+    RIHIP_CHECK_LAUNCH();
+    return RIHIP_OK;
+  }
+  int ranges(const Sq8UpdateCtx& c) override {
+    sq8_launch_ranges(true, c.vec_new, codes, c.row_ids_new, c.Np_new, c.h->dk, c.h->dpad, c.h->centre, c.h->scale, c.part, c.nb, c.e_new,
+                      c.a_new, c.st);
+    RIHIP_CHECK_LAUNCH();
+    return RIHIP_OK;
+  }
+  void swap(Sq8Index* h, const unsigned long long*) override {
+    hipFree(h->codes);
+    h->codes = codes;
+    codes = nullptr;
   }
 };
 
 }  // namespace
 
-extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
-                                      const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add,
-                                      int64_t* item_ids_out, int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped,
-                                      int64_t* bad_id, int* bad_kind, void* stream) {
-  Sq8Index* h = (Sq8Index*)handle;
-  RIHIP_REQUIRE(!h || !h->pq_codes, RIHIP_ERR_STATE,
-                "sq8_update_apply: a PQ index is not updated in place (its codebooks are trained on the corpus): rebuild it");
-  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_update_apply: index is empty");
+namespace rihip_index {
+// h: a handle with storage and N > 0 (the caller's check, with its own text)
+int sq8_update_run(Sq8Index* h, Sq8UpdateStorage& stg, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                   const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add, int64_t* item_ids_out,
+                   int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped, int64_t* bad_id, int* bad_kind, hipStream_t st) {
   RIHIP_REQUIRE(item_ids && item_ids_out && n_total && n_dropped && n_clamped && bad_id && bad_kind && n_drop >= 0 && n_add >= 0 &&
-                (n_drop == 0 || drop_ids) && (n_add == 0 || (X_add && add_ids)), RIHIP_ERR_ARG, "sq8_update_apply: bad arguments");
+                (n_drop == 0 || drop_ids) && (n_add == 0 || (X_add && add_ids)), RIHIP_ERR_ARG, "%s: bad arguments", stg.who);
   *bad_kind = 0; *bad_id = 0; *n_total = h->N; *n_dropped = 0; *n_clamped = 0;
   if (n_drop == 0 && n_add == 0) return RIHIP_OK;
   const int64_t N = h->N, Np = h->Np;
-  const int dk = h->dk, dpad = h->dpad, L = dpad / 16, nlist = h->nlist;
+  const int dk = h->dk, nlist = h->nlist;
   RIHIP_REQUIRE(N + n_add + (int64_t)TR * (nlist + 1) < (1ll << 31) && n_drop < (1ll << 31), RIHIP_ERR_ARG,
-                "sq8_update_apply: %lld + %lld rows exceed the 2^31 row limit", (long long)N, (long long)n_add);
-  hipStream_t st = (hipStream_t)stream;
+                "%s: %lld + %lld rows exceed the 2^31 row limit", stg.who, (long long)N, (long long)n_add);
   // zero-padded to dk, as the source index held them
-  if (n_add > 0) RCCHK(sq8_rows_at_dk(h, X_add, n_add, "sq8_update_apply: the rows must be 16-byte aligned", st));
+  if (n_add > 0) {
+    char misaligned[96];
+    snprintf(misaligned, sizeof(misaligned), "%s: the rows must be 16-byte aligned", stg.who);
+    RCCHK(sq8_rows_at_dk(h, X_add, n_add, misaligned, st));
+  }
 
   Owned o;
   UpdateScratch& s = o.s;
-  const int64_t nhb = HB_LISTS + 2 * (int64_t)nlist + 1;
+  const int64_t n_lists_hb = HB_LISTS + 2 * (int64_t)nlist + 1;   // the block of index_update_kernels.h ...
+  const int64_t nhb = n_lists_hb + stg.n_words;                    // ... and behind it the storage's own counters
   const size_t o_hb = s.plan<unsigned long long>(nhb), o_sdrop = s.plan<int64_t>(n_drop), o_sadd = s.plan<int64_t>(n_add);
   const size_t o_keep = s.plan<int>(N + 1), o_rscan = s.plan<int>(N + 1), o_pkeep = s.plan<int>(Np + 1), o_pscan = s.plan<int>(Np + 1);
   const size_t o_anew = s.plan<int>(n_add), o_zoff = s.plan<int>(nlist + 1), o_tl = s.plan<int>(Np / TR);
@@ -181,10 +219,11 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
   const size_t t_bytes = std::max(std::max(t_sort_d, t_sort_a), std::max(t_scan_r, t_scan_p));
   const size_t o_temp = s.plan<char>((int64_t)t_bytes);
   if (hipMalloc((void**)&s.base, s.used) != hipSuccess) {
-    rihip_set_error("sq8_update_apply: device allocation of %lld bytes failed", (long long)s.used);
+    rihip_set_error("%s: device allocation of %lld bytes failed", stg.who, (long long)s.used);
     return RIHIP_ERR_HIP;
   }
   unsigned long long* hb = s.at<unsigned long long>(o_hb);
+  if (stg.n_words) HIPCHK(hipMemsetAsync(hb + n_lists_hb, 0, sizeof(unsigned long long) * stg.n_words, st));
   int64_t* sdrop = s.at<int64_t>(o_sdrop);
   int64_t* sadd = s.at<int64_t>(o_sadd);
   int* keep = s.at<int>(o_keep);
@@ -213,7 +252,7 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
   RIHIP_CHECK_LAUNCH();
   { size_t tb = t_bytes; HIPCHK(rocprim::exclusive_scan(temp, tb, (const int*)keep, rscan, 0, (size_t)(N + 1), rocprim::plus<int>(), st)); }
 
-  // 2. kept rows per list, list of every new row, clamp count
+  // 2. kept rows per list, list of every new row, clamp count, the storage's own work on the new rows
   const int* g_rows = nullptr; const int* g_keys = nullptr; const int* g_off = zoff;
   hipLaunchKernelGGL(index_update_pmask_kernel, dim3((unsigned)((Np + 1 + 255) / 256)), dim3(256), 0, st, h->row_ids, Np, keep, pkeep);
   hipLaunchKernelGGL(sq8_update_tile_list_kernel, dim3((unsigned)((Np / TR + 255) / 256)), dim3(256), 0, st, h->list_poff, nlist,
@@ -230,6 +269,12 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
     hipLaunchKernelGGL(sq8_update_clamp_kernel, dim3((unsigned)((n_add * dk + 255) / 256)), dim3(256), 0, st, X_add, n_add, h->du, dk,
                        h->centre, h->scale, hb + HB_SPARE);
   }
+  const bool tagged = h->tags != nullptr, with_vec = h->vec != nullptr;
+  Sq8UpdateCtx cx{};
+  cx.h = h; cx.st = st; cx.X_add = X_add; cx.add_tags = tagged ? add_tags : nullptr; cx.n_add = n_add;
+  cx.keep = keep; cx.rscan = rscan; cx.pscan = pscan; cx.tile_list_old = tl_old;
+  cx.g_rows = g_rows; cx.g_keys = g_keys; cx.g_off = g_off; cx.words = hb + n_lists_hb;
+  if (n_add) RCCHK(stg.encode(cx));
   hipLaunchKernelGGL(index_update_list_count_kernel, dim3((unsigned)((nlist + 1 + 255) / 256)), dim3(256), 0, st, pscan,
                      h->list_poff, g_off, nlist, hb);
   RIHIP_CHECK_LAUNCH();
@@ -265,9 +310,7 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
     poff[c + 1] = poff[c] + (len_n[c] + TR - 1) / TR * TR;
   }
   const int64_t Np_n = poff[nlist];   // > 0: n_new > 0
-  const bool tagged = h->tags != nullptr, with_vec = h->vec != nullptr;
   const int nb = (int)std::min<int64_t>(4096, (Np_n + 255) / 256);   // blocks of the range pass (a maximum: any split gives the same bits)
-  HIPCHK(hipMalloc((void**)&o.codes, (size_t)Np_n * dpad));
   HIPCHK(hipMalloc((void**)&o.rid, sizeof(int64_t) * (size_t)Np_n));
   HIPCHK(hipMalloc((void**)&o.poff, sizeof(int64_t) * (nlist + 1)));
   HIPCHK(hipMalloc((void**)&o.len, sizeof(int) * nlist));
@@ -281,40 +324,50 @@ extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, con
   HIPCHK(hipMemcpyAsync(o.poff, poff.data(), sizeof(int64_t) * (nlist + 1), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(o.len, len32.data(), sizeof(int) * nlist, hipMemcpyHostToDevice, st));
 
-  // 5. result ids, repack, vectors and their ranges
+  // 5. result ids, the storage's repack, vectors and their ranges
   hipLaunchKernelGGL(index_update_ids_kernel, dim3((unsigned)((N + n_add + 255) / 256)), dim3(256), 0, st, item_ids, N, keep, rscan,
                      add_ids, n_add, n_keep, item_ids_out);
-  Sq8RepackArgs a;
-  a.codes_old = h->codes; a.row_ids_old = h->row_ids; a.tags_old = h->tags; a.tile_list_old = tl_old; a.poff_old = h->list_poff;
-  a.Np_old = Np; a.keep = keep; a.rscan = rscan; a.pscan = pscan;
-  a.X_add = X_add; a.add_tags = tagged ? add_tags : nullptr; a.g_rows = g_rows; a.g_keys = g_keys; a.g_off = g_off; a.n_add = n_add;
-  a.centre = h->centre; a.scale = h->scale; a.cnt_keep = hb + HB_LISTS; a.poff_new = o.poff;
-  a.codes_new = o.codes; a.row_ids_new = o.rid; a.tags_new = o.tags; a.n_keep = n_keep; a.nlist = nlist; a.dk = dk; a.lanes = L;
-  const int64_t tot = (Np + n_add + (int64_t)nlist * TR) * L;
-  hipLaunchKernelGGL(sq8_update_repack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a);
   RIHIP_CHECK_LAUNCH();
+  cx.cnt_keep = hb + HB_LISTS; cx.poff_new = o.poff; cx.n_keep = n_keep; cx.Np_new = Np_n; cx.row_ids_new = o.rid; cx.tags_new = o.tags;
+  RCCHK(stg.repack(cx));
   if (with_vec) {
     const int d4 = dk / 4;
     const int64_t tv = (N + n_add) * d4;
     hipLaunchKernelGGL(index_update_compact_kernel, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, st, h->vec, N, keep, rscan, X_add,
                        n_add, n_keep, d4, o.vec);
-    sq8_launch_ranges(true, o.vec, o.codes, o.rid, Np_n, dk, dpad, h->centre, h->scale, o.part, nb, o.e, o.a, st);
     RIHIP_CHECK_LAUNCH();
+    cx.vec_new = o.vec; cx.part = o.part; cx.nb = nb; cx.e_new = o.e; cx.a_new = o.a;
+    RCCHK(stg.ranges(cx));
   }
   HIPCHK(hipStreamSynchronize(st));   // (the host vectors go away; the caller's rows may go away after the call)
 
   // 6. swap
   rihip_bump_generation();
-  hipFree(h->codes); hipFree(h->row_ids); hipFree(h->list_poff); hipFree(h->list_len_dev); hipFree(h->tags);
+  hipFree(h->row_ids); hipFree(h->list_poff); hipFree(h->list_len_dev); hipFree(h->tags);
   hipFree(h->vec); hipFree(h->ref_e); hipFree(h->ref_a);
   hipFree(h->inv_pos); h->inv_pos = nullptr;   // (a new physical order)
-  h->codes = o.codes; h->row_ids = o.rid; h->list_poff = o.poff; h->list_len_dev = o.len; h->tags = o.tags;
+  h->row_ids = o.rid; h->list_poff = o.poff; h->list_len_dev = o.len; h->tags = o.tags;
   h->vec = o.vec; h->ref_e = o.e; h->ref_a = o.a;
-  o.codes = nullptr; o.rid = nullptr; o.poff = nullptr; o.len = nullptr; o.tags = nullptr; o.vec = nullptr; o.e = nullptr; o.a = nullptr;
+  o.rid = nullptr; o.poff = nullptr; o.len = nullptr; o.tags = nullptr; o.vec = nullptr; o.e = nullptr; o.a = nullptr;
   h->N = n_new; h->Np = Np_n; h->list_len = len_n; h->id_map = nullptr;
   *n_total = n_new; *n_dropped = n_gone; *n_clamped = (int64_t)hbh[HB_SPARE];
   h->upd_stats[0] += 1; h->upd_stats[1] += n_gone; h->upd_stats[2] += n_add; h->upd_stats[3] += *n_clamped;
+  stg.swap(h, hbh.data() + n_lists_hb);
   return RIHIP_OK;
+}
+}  // namespace rihip_index
+
+extern "C" int rihip_sq8_update_apply(void* handle, const int64_t* item_ids, const int64_t* drop_ids, int64_t n_drop,
+                                      const float* X_add, const int64_t* add_ids, const uint32_t* add_tags, int64_t n_add,
+                                      int64_t* item_ids_out, int64_t* n_total, int64_t* n_dropped, int64_t* n_clamped,
+                                      int64_t* bad_id, int* bad_kind, void* stream) {
+  Sq8Index* h = (Sq8Index*)handle;
+  RIHIP_REQUIRE(!h || !h->pq_codes, RIHIP_ERR_STATE,
+                "sq8_update_apply: a PQ index is not updated in place (its codebooks are trained on the corpus): rebuild it");
+  RIHIP_REQUIRE(h && h->codes && h->N > 0, RIHIP_ERR_STATE, "sq8_update_apply: index is empty");
+  Sq8Codes stg;
+  return sq8_update_run(h, stg, item_ids, drop_ids, n_drop, X_add, add_ids, add_tags, n_add, item_ids_out, n_total, n_dropped, n_clamped,
+                        bad_id, bad_kind, (hipStream_t)stream);
 }
 
 extern "C" int rihip_sq8_update_assign(void* handle, const float* X, int64_t n, int32_t* assign_out, void* stream) {

@@ -21,8 +21,14 @@ certificate of a refined search uses 254 where it uses 127 otherwise.  A residua
 
 ``codes()``, ``reconstruct()`` and ``attach_vectors()`` decode the whole index on the device: a transient
 N * dpad bytes.  ``save`` / ``load`` are SQ8Index's on the PQ file format (``_SAVE`` / ``_LOAD``); each loader refuses the
-other's file.  A PQ index is not updated in place (its codebooks are trained on the corpus): ``add_items``,
-``remove_items`` and ``update_items`` raise NotImplementedError -- rebuild with ``from_index``.
+other's file.
+
+Live catalogue (opt-in): by default a PQ index is not updated in place (its codebooks are trained on the corpus):
+``add_items``, ``remove_items`` and ``update_items`` raise NotImplementedError -- rebuild with ``from_index``.  With
+``from_index(..., frozen_updates=True)`` or ``pq.frozen_updates = True`` they work as on SQ8Index, as one repack of the
+entry-number matrix under the FROZEN centroids, quantiser, list codes and codebooks (csrc/pq_update.hip); the index ends
+bit for bit where a from-scratch build of the final corpus with those injected would, and ``update_stats()`` carries
+the drift signal of the frozen codebooks.
 
 There is no NumPy or torch path for training, encoding or search: everything runs in csrc/pq.hip and the SQ8 index's
 units (csrc/sq8.hip over csrc/sq8_scan.hip for the search).
@@ -30,6 +36,7 @@ units (csrc/sq8.hip over csrc/sq8_scan.hip for the search).
 from __future__ import annotations
 
 import ctypes as C
+import logging
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -38,25 +45,32 @@ from . import _lib as L
 from .faiss_index import FAISSIndex
 from .sq8_index import SQ8Index, _check_ranges, _check_source
 
-_REBUILD = "a PQIndex is not updated in place (its codebooks are trained on the corpus): rebuild it with PQIndex.from_index"
+logger = logging.getLogger(__name__)
+
+_REBUILD = ("a PQIndex is not updated in place (its codebooks are trained on the corpus): rebuild it with PQIndex.from_index, "
+            "or set frozen_updates=True to add, remove and replace items under the codebooks it has")
 
 
 class PQIndex(SQ8Index):
     _KIND = "PQ"
     _SAVE, _LOAD = "rihip_pq_index_save", "rihip_pq_index_load"    # save() / load(): SQ8Index's, on the PQ file format
+    _frozen_updates = False                                        # the property below
 
     # -- build ----------------------------------------------------------------------------------------------------
     @classmethod
     def from_index(cls, faiss_index: FAISSIndex, dsub: int = 8, n_iter: int = 10,
                    ranges: Optional[Tuple[np.ndarray, np.ndarray]] = None, codebooks: Optional[np.ndarray] = None,
-                   keep_vectors: bool = False, by_residual: bool = False) -> "PQIndex":
+                   keep_vectors: bool = False, by_residual: bool = False, frozen_updates: bool = False) -> "PQIndex":
         """Encode the vectors of a built FAISSIndex (IVF: its lists and centroids; exact: one list).  dsub: 8 or 16
         dimensions per sub-space; n_iter: Lloyd steps of the codebook training; ranges: (centre, scale) of the SQ8 stage,
         as SQ8Index.from_index; codebooks: int8 [M, 256, dsub] with M = dpad / dsub (dpad = 64 up to 64 dimensions, else
         128), entries in [-127, 127] -- injected codebooks skip the training, as ranges= skips the range pass.
         keep_vectors / item tags: as SQ8Index.from_index.  by_residual=True: quantise the residuals against the IVF
-        centroids (the module text above); injected codebooks are then residual codebooks.  ValueError on a flat source."""
+        centroids (the module text above); injected codebooks are then residual codebooks.  ValueError on a flat source.
+        frozen_updates=True: allow add_items / remove_items / update_items under the frozen codebooks (the property)."""
         _check_source("PQIndex", faiss_index)
+        if not isinstance(frozen_updates, (bool, np.bool_)):
+            raise ValueError(f"PQIndex: frozen_updates={frozen_updates!r} must be True or False")
         if not isinstance(by_residual, (bool, np.bool_)):
             raise ValueError(f"PQIndex: by_residual={by_residual!r} must be True or False")
         if by_residual and not faiss_index.index.is_ivf:
@@ -81,20 +95,71 @@ class PQIndex(SQ8Index):
             faiss_index.index._h, None if m is None else m.ctypes.data, None if s is None else s.ctypes.data, int(dsub),
             int(n_iter), None if book is None else book.ctypes.data, int(bool(by_residual)), C.byref(h), L.stream_ptr()),
             "pq_index_from_ip_index")
-        return cls._adopt(h.value, faiss_index, keep_vectors)
+        obj = cls._adopt(h.value, faiss_index, keep_vectors)
+        obj.frozen_updates = frozen_updates
+        return obj
 
-    # -- no live updates ------------------------------------------------------------------------------------------
+    # -- live catalogue under frozen codebooks (opt-in) -------------------------------------------------------------------
+    # With frozen_updates on, the four calls are SQ8Index's over rihip_pq_update_apply (csrc/pq_update.hip): ONE repack of
+    # the entry-number matrix under the index's own centroids, SQ8 quantiser, list codes and codebooks, none of which is
+    # retrained (faiss IndexIVFPQ adds after train() in the same way).  Kept rows keep their bytes, new rows are encoded
+    # against the frozen codebooks, and the index ends bit for bit where from_index(f32 index of the final corpus with the
+    # same centroids and lists, dsub=self.dsub, ranges=self.quantizer(), codebooks=self.codebooks(),
+    # by_residual=self.by_residual) + set_item_tags + attach_vectors would leave it; saved files are byte-identical.
+    # Normalisation, add_items_device, the upsert tag rules, assign_lists and the refusals are SQ8Index's.
+    @property
+    def frozen_updates(self) -> bool:
+        """whether add_items / remove_items / update_items work on this index (under its frozen codebooks) instead of
+        raising NotImplementedError.  A Python-side switch: it is in no file, so a loaded index opts in again."""
+        return self._frozen_updates
+
+    @frozen_updates.setter
+    def frozen_updates(self, on) -> None:
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"PQIndex: frozen_updates={on!r} must be True or False")
+        self._frozen_updates = bool(on)
+
+    def _update_entry(self) -> str:
+        return "rihip_pq_update_apply" if self._frozen_updates else self._UPDATE
+
+    def _log_update(self, n_dropped: int, n_add: int) -> None:
+        st = self.update_stats()
+        logger.info("PQ index updated: %d rows dropped, %d added, %d code values clamped, %d residual values clamped, "
+                    "distortion %d", n_dropped, n_add, self._last_clamped, st["last_residual_clamped"], st["last_distortion"])
+
+    def _frozen(self) -> None:
+        if not self._frozen_updates:
+            raise NotImplementedError(_REBUILD)
+
     def add_items(self, embeddings, item_ids, tags=None):
-        raise NotImplementedError(_REBUILD)
+        self._frozen()
+        return super().add_items(embeddings, item_ids, tags=tags)
 
     def add_items_device(self, x_dev, item_ids, tags=None):
-        raise NotImplementedError(_REBUILD)
+        self._frozen()
+        return super().add_items_device(x_dev, item_ids, tags=tags)
 
     def remove_items(self, item_ids):
-        raise NotImplementedError(_REBUILD)
+        self._frozen()
+        return super().remove_items(item_ids)
 
     def update_items(self, embeddings, item_ids, tags=None):
-        raise NotImplementedError(_REBUILD)
+        self._frozen()
+        return super().update_items(embeddings, item_ids, tags=tags)
+
+    def update_stats(self) -> Dict:
+        """SQ8Index.update_stats() plus, cumulative since the handle was made, residual_clamped (residual values of added
+        rows that left [-127, 127]; 0 on a plain index) and distortion_added (the summed smallest distance D over all
+        added rows and sub-spaces), and last_residual_clamped / last_distortion of the last update that changed the
+        index.  The drift signal of frozen codebooks: compare distortion_added / added, the mean distortion of an added
+        row, against train_stats()["distortion"][-1] / N_build, that of a row the codebooks were trained on; a ratio
+        well above 1 says the new rows no longer look like the training corpus and a rebuild is due.  After load the
+        trace is empty, so only the first half exists."""
+        out = (C.c_int64 * 8)()
+        L.check(L.lib().rihip_pq_update_stats(self._built()._h, out), "pq_update_stats")
+        return {"updates": int(out[0]), "dropped": int(out[1]), "added": int(out[2]), "clamped": int(out[3]),
+                "last_clamped": self._last_clamped, "residual_clamped": int(out[4]), "distortion_added": int(out[5]),
+                "last_residual_clamped": int(out[6]), "last_distortion": int(out[7])}
 
     # -- trained state ----------------------------------------------------------------------------------------------
     def _dims(self) -> Tuple[int, int]:

@@ -148,6 +148,7 @@ def _check_ranges(cls_name: str, ranges, d: int):
 class SQ8Index(ExcludingSearch):
     _KIND = "SQ8"                                  # in messages; PQIndex: "PQ"
     _SAVE, _LOAD = "rihip_sq8_index_save", "rihip_sq8_index_load"
+    _UPDATE = "rihip_sq8_update_apply"             # add_items / remove_items / update_items
     _EXCL_ABI = {"mask_words": "rihip_sq8_exclude_mask_words", "mask": "rihip_sq8_exclude_mask",
                  "budget": "rihip_sq8_exclude_set_exclusion_budget", "nonzero": "rihip_sq8_exclude_scratch_nonzero",
                  "stats": "rihip_sq8_exclude_exclusion_stats"}
@@ -265,18 +266,18 @@ class SQ8Index(ExcludingSearch):
         out = torch.empty(n_old + n_add, dtype=torch.int64, device=dev)
         n_total, n_dropped, n_clamped = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         bad_id, bad_kind = C.c_int64(0), C.c_int(0)
-        rc = L.lib().rihip_sq8_update_apply(self.index._h, self._item_ids_dev.data_ptr(), L.ptr(drop) if n_drop else None,
-                                            n_drop, L.ptr(x) if n_add else None, L.ptr(add) if n_add else None,
-                                            L.ptr(t_dev), n_add, out.data_ptr(), C.byref(n_total), C.byref(n_dropped),
-                                            C.byref(n_clamped), C.byref(bad_id), C.byref(bad_kind), L.stream_ptr())
+        entry = self._update_entry()
+        rc = getattr(L.lib(), entry)(self.index._h, self._item_ids_dev.data_ptr(), L.ptr(drop) if n_drop else None,
+                                     n_drop, L.ptr(x) if n_add else None, L.ptr(add) if n_add else None,
+                                     L.ptr(t_dev), n_add, out.data_ptr(), C.byref(n_total), C.byref(n_dropped),
+                                     C.byref(n_clamped), C.byref(bad_id), C.byref(bad_kind), L.stream_ptr())
         if rc != 0 and bad_kind.value != 0:
             raise ValueError(L.lib().rihip_last_error().decode("utf-8", "replace"))
-        L.check(rc, "sq8_update_apply")
+        L.check(rc, entry[6:])
         if n_dropped.value == 0 and n_add == 0:
             return 0, 0
-        logger.info("SQ8 index updated: %d rows dropped, %d added, %d code values clamped", n_dropped.value, n_add,
-                    n_clamped.value)
         self._last_clamped = int(n_clamped.value)
+        self._log_update(int(n_dropped.value), n_add)
         self._item_ids_dev = out[:n_total.value]
         self.item_ids = self._item_ids_dev.cpu().numpy()
         self._id_map_stale = True
@@ -286,6 +287,14 @@ class SQ8Index(ExcludingSearch):
             self._tags = np.ascontiguousarray(np.concatenate([old_tags[keep]] + ([tags] if n_add else [])), dtype=np.uint32)
             assert self._tags.shape[0] == n_total.value
         return int(n_dropped.value), n_add
+
+    def _update_entry(self) -> str:
+        """the C entry point _apply_update calls (PQIndex: its own, once frozen_updates is on)"""
+        return self._UPDATE
+
+    def _log_update(self, n_dropped: int, n_add: int) -> None:
+        logger.info("SQ8 index updated: %d rows dropped, %d added, %d code values clamped", n_dropped, n_add,
+                    self._last_clamped)
 
     def _normalised(self, embeddings: np.ndarray) -> torch.Tensor:
         embeddings = np.asarray(embeddings)
